@@ -22,6 +22,7 @@ Extra objects on the line:
                   reference's outputs) timed on this box's host cores over the same views; the reference itself
                   is a Python interpreter loop measured at 0.0835 Mvox/s.
   gn, frame    -- BASELINE config 3 (10 GN iterations at 256^3 / 512 nodes) and the composed per-frame loop.
+  dump_outputs -- with --dump-outputs DIR only: where the volumes the timed steps left were written (see dump_outputs).
 """
 import argparse
 import json
@@ -65,7 +66,43 @@ def parse():
     ap.add_argument("--global-iters", type=int, default=None, help="frame legs: rigid-mode steps in front of the node iterations (default: SlabFrame's)")
     ap.add_argument("--gn-mode", default="auto", choices=("auto", "sharded", "replicated"), help="N > 1: how the warp solve runs")
     ap.add_argument("--gn-solves", type=int, default=5, help="timed solves of 10 GN iterations each")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the volumes they left (tsdf.npy, weight.npy: float32) to DIR; see dump_outputs")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
+
+
+DUMP_VOXELS = 1 << 22          # per array: 16 MB of float32, so tsdf.npy + weight.npy stay far below 64 MB
+DUMP_SEED = 20240607
+
+
+def dump_outputs(torch, out_dir, T, Wt, n_grid, x_range, plane, rank, world):
+    """--dump-outputs: what the timed steps hand their caller, the TSDF volume T and the weight volume W they update in place,
+    as DIR/tsdf.npy and DIR/weight.npy (float32, the volumes' own dtype).  They hold every step run into them: the warm-up, the
+    eager timed pass and, when a graph was captured, the replayed pass too.  A grid of at most DUMP_VOXELS voxels is written
+    whole (shape nx x R x R); a larger one as the voxels at a fixed sample of flat grid indices: DUMP_VOXELS indices drawn
+    without replacement by np.random.default_rng(DUMP_SEED) from the whole grid's n_grid voxels, in ascending order.  The sample
+    depends only on the grid size, so two builds give comparable files.  With several ranks every rank writes the sampled voxels
+    of its own axis-0 slab as tsdf.rank<r>.npy / weight.rank<r>.npy; concatenated in rank order they are the 1-GPU sample."""
+    os.makedirs(out_dir, exist_ok=True)
+    lo, hi = x_range[0] * plane, x_range[1] * plane
+    if n_grid <= DUMP_VOXELS:
+        sel = None
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n_grid, size=DUMP_VOXELS, replace=False))
+        idx = idx[(idx >= lo) & (idx < hi)] - lo
+        sel = torch.from_numpy(idx).to(T.device)
+    suffix = "" if world == 1 else ".rank%d" % rank
+    files = []
+    for name, vol in (("tsdf", T), ("weight", Wt)):
+        a = (vol if sel is None else vol.reshape(-1).index_select(0, sel)).float().cpu().numpy()
+        path = os.path.join(out_dir, name + suffix + ".npy")
+        np.save(path, a)
+        files.append(os.path.basename(path))
+    return {"dir": os.path.abspath(out_dir), "files": files, "voxels": int(a.size),
+            "sample": None if sel is None else {"of_voxels": n_grid, "seed": DUMP_SEED}}
 
 
 def gn_leg(args, torch, dist, scene, rank, world, barrier):
@@ -603,6 +640,9 @@ def main():
             dt, kern_ms, launch_mode = dt_graph, kern_ms_graph, "hipGraph replay of the %d steps" % args.steps
 
     value = vox_per_step * args.steps / dt / 1e6
+    dumped = None
+    if args.dump_outputs:                     # outside the timed region; before any other leg runs on this device
+        dumped = dump_outputs(torch, args.dump_outputs, T, Wt, res[0] * R * R, x_range, R * R, rank, world)
     # ---- roofline of the dominant kernel (this rank's slab).  `achieved` counts the bytes the launch really moves
     # (see moved_bytes; cross-checked by the PMC `traffic`), not the 16 B/voxel of SURVEY section 8(d):
     # that figure credits packs no view updates, which the kernel never loads, and is kept as `algorithmic_*`.
@@ -649,6 +689,8 @@ def main():
                                 "pair of volumes (134 MB) sits in the 256 MiB Infinity Cache; k1_512 below is the out-of-cache figure "
                                 "(profiles/r3_k1_experiments.txt, DESIGN.md section 3)"},
     }
+    if dumped is not None:
+        out["dump_outputs"] = dumped
 
     # measured ceilings of THIS access pattern, hand-written (tools/ubench/rmw_stream.hip, built by __graft_entry__.build): a float4
     # copy and an in-place read-modify-write of two 512^3 float32 volumes (far beyond the 256 MiB Infinity Cache) as 1-KiB rows and
