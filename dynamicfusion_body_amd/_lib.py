@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("DFH_LIB_PATH") or os.path.join(_PKG, "libdfusion_hip.
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dfusion_hip.h")
 
 F32, F64 = 0, 1
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -126,6 +126,11 @@ _SIGNATURES = {
                            ctypes.c_long, _vp]),
     "dfh_mc_reorder_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long]),
     "dfh_mc_reorder": (_int, [_vp, _vp, _vp, _vp, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dfh_render_workspace_bytes": (ctypes.c_size_t, [_int, _int, _int, ctypes.c_long]),
+    "dfh_render_raster": (_int, [_vp, ctypes.c_long, _vp, ctypes.c_long, _int, _c_double_p, _c_double_p, _int, _int, _dbl, _c_double_p,
+                                 _dbl, _dbl, _vp, ctypes.c_size_t, _vp]),
+    "dfh_render_resolve": (_int, [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _int, _c_double_p, _c_double_p, _int, _int, _dbl,
+                                  _c_double_p, _dbl, _dbl, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -1,0 +1,313 @@
+// Multi-view triangle rasterizer: depth, face-id and normal maps of one triangle mesh in V views of H x W pixels, the
+// "model-to-frame prediction" of DynamicFusion / KinectFusion.  No reference counterpart (the reference never renders its
+// model); the semantics are stated in include/dfusion_hip.h (dfh_render_*) and restated in numpy by tests/render_np.py.
+//
+// Work decomposition (deterministic whatever the schedule: one 64-bit key per pixel, (float depth bits) << 32 | face,
+// reduced with atomicMin -- the nearest surface wins, ties go to the lowest face id):
+//   render_small_kernel   one lane per (triangle, view): projection, set-up, and a walk of the clamped bounding box when it
+//                         holds at most kRenderSmallPixels pixels (marching-cubes meshes seen at about one voxel per pixel:
+//                         triangles of a pixel or less); larger boxes are appended to a list
+//   render_large_kernel   a fixed grid of workgroups pulls the listed (triangle, view) pairs; the 256 lanes of a workgroup
+//                         tile the pair's box (a triangle covering the whole image is 256 pixels per lane-step, not one lane's
+//                         million)
+//   render_resolve_kernel one lane per pixel: the key -> depth (-z, the reference's storage convention) and face id; the
+//                         normal is re-interpolated from the winning face (same arithmetic as the raster pass)
+// Everything that decides coverage and depth runs in fp64 with -ffp-contract=off, so the numpy restatement with the same
+// operation order gives the same bits.
+#include "dfh_common.h"
+
+#include <cmath>
+
+namespace dfh {
+
+constexpr int kRenderBlock = 256;
+constexpr int kRenderMaxViews = 16;
+// Boxes up to 64 pixels (8 x 8) are walked by one lane.  A marching-cubes triangle at about one voxel per pixel has a box of
+// 1-4 pixels, so a wave's lanes finish together; a lane that walks 64 pixels holds its wave for ~64 iterations, the price of
+// the rare larger triangle without a second launch's list round trip.  Every box pixel that passes the edge test costs one
+// 64-bit atomicMin to a scattered address.  The rate of 64-bit umin on gfx950 is not measured; for float adds with every lane
+// on a different row MI355X_MICROARCH.md gives 0.08 TB/s, 17x below the coalesced rate, and that is the shape here.  A plain
+// load of the key in front of the atomic skips it when the stored key is already smaller: keys only decrease, so a stale
+// value can only be larger than the true one and the skip never loses a write.
+constexpr int kRenderSmallPixels = 64;
+constexpr unsigned long long kRenderEmpty = ~0ull;
+
+struct RenderView {
+    double k[5];              // K00 K01 K02 K11 K12
+    double r[12];             // lw, 3 x 4 row-major (world -> camera)
+};
+
+struct RenderParams {
+    int nv, H, W;
+    long nverts, nfaces;
+    double scale, half, center[3], znear;
+    RenderView view[kRenderMaxViews];
+};
+
+// One triangle in one view after projection: screen positions, camera depths, area.
+struct Tri {
+    double u[3], v[3], z[3];
+    double A;
+    int x0, x1, y0, y1;       // clamped bounding box of pixel centres (inclusive)
+};
+
+__device__ __forceinline__ void render_project(const RenderParams &p, const RenderView &vw, const double *__restrict__ P, double &u,
+                                               double &v, double &z) {
+    const double w0 = p.scale * (P[0] - p.half) + p.center[0];
+    const double w1 = p.scale * (P[1] - p.half) + p.center[1];
+    const double w2 = p.scale * (P[2] - p.half) + p.center[2];
+    const double *r = vw.r;
+    const double c0 = r[0] * w0 + r[1] * w1 + r[2] * w2 + r[3];
+    const double c1 = r[4] * w0 + r[5] * w1 + r[6] * w2 + r[7];
+    const double c2 = r[8] * w0 + r[9] * w1 + r[10] * w2 + r[11];
+    u = (vw.k[0] * c0 + vw.k[1] * c1 + vw.k[2] * c2) / c2;
+    v = (vw.k[3] * c1 + vw.k[4] * c2) / c2;
+    z = c2;
+}
+
+// Edge value of edge (a, b) at (x, y).  Evaluated from the lexicographically smaller end point (and negated when that is b),
+// so the two triangles that share an edge get exactly opposite values and a closed mesh leaves no pixel uncovered.
+__device__ __forceinline__ double render_edge(double ua, double va, double ub, double vb, double x, double y) {
+    if (ua < ub || (ua == ub && va < vb)) return (x - ua) * (vb - va) - (y - va) * (ub - ua);
+    return -((x - ub) * (va - vb) - (y - vb) * (ua - ub));
+}
+
+// false: the triangle draws nothing in this view (a vertex at c2 <= znear, a non-finite screen coordinate, zero or non-finite
+// area, an empty clamped box, or a vertex index outside [0, nverts))
+__device__ __forceinline__ bool render_setup(const RenderParams &p, const RenderView &vw, const double *__restrict__ verts,
+                                             const int *__restrict__ faces, long f, Tri &t) {
+    for (int i = 0; i < 3; ++i) {
+        const int vi = faces[3 * f + i];
+        if (vi < 0 || vi >= p.nverts) return false;
+        render_project(p, vw, verts + 3 * (size_t)vi, t.u[i], t.v[i], t.z[i]);
+        if (!(t.z[i] > p.znear) || !isfinite(t.u[i]) || !isfinite(t.v[i])) return false;
+    }
+    t.A = (t.u[2] - t.u[0]) * (t.v[1] - t.v[0]) - (t.v[2] - t.v[0]) * (t.u[1] - t.u[0]);
+    if (!isfinite(t.A) || t.A == 0.0) return false;
+    const double xl = fmax(0.0, ceil(fmin(fmin(t.u[0], t.u[1]), t.u[2])));
+    const double xh = fmin((double)(p.W - 1), floor(fmax(fmax(t.u[0], t.u[1]), t.u[2])));
+    const double yl = fmax(0.0, ceil(fmin(fmin(t.v[0], t.v[1]), t.v[2])));
+    const double yh = fmin((double)(p.H - 1), floor(fmax(fmax(t.v[0], t.v[1]), t.v[2])));
+    if (!(xl <= xh) || !(yl <= yh)) return false;
+    t.x0 = (int)xl; t.x1 = (int)xh; t.y0 = (int)yl; t.y1 = (int)yh;
+    return true;
+}
+
+// Barycentric weights (edge value / A) at pixel (x, y); false if the pixel is not covered.
+__device__ __forceinline__ bool render_bary(const Tri &t, int x, int y, double (&l)[3]) {
+    const double fx = (double)x, fy = (double)y;
+    const double e0 = render_edge(t.u[1], t.v[1], t.u[2], t.v[2], fx, fy);
+    const double e1 = render_edge(t.u[2], t.v[2], t.u[0], t.v[0], fx, fy);
+    const double e2 = render_edge(t.u[0], t.v[0], t.u[1], t.v[1], fx, fy);
+    const bool in = t.A > 0.0 ? (e0 >= 0.0 && e1 >= 0.0 && e2 >= 0.0) : (e0 <= 0.0 && e1 <= 0.0 && e2 <= 0.0);
+    if (!in) return false;
+    l[0] = e0 / t.A; l[1] = e1 / t.A; l[2] = e2 / t.A;
+    return true;
+}
+
+// The pixel's key, or kRenderEmpty if it is not covered (or its perspective-correct depth is not a finite positive float).
+__device__ __forceinline__ unsigned long long render_key(const Tri &t, int x, int y, long f) {
+    double l[3];
+    if (!render_bary(t, x, y, l)) return kRenderEmpty;
+    const double s = l[0] / t.z[0] + l[1] / t.z[1] + l[2] / t.z[2];
+    if (!(s > 0.0)) return kRenderEmpty;
+    const float zf = (float)(1.0 / s);
+    if (!isfinite(zf)) return kRenderEmpty;
+    return ((unsigned long long)__float_as_uint(zf) << 32) | (unsigned)f;
+}
+
+__device__ __forceinline__ void render_store(unsigned long long *__restrict__ keys, size_t pix, unsigned long long key) {
+    if (key < keys[pix]) atomicMin(keys + pix, key);
+}
+
+__global__ __launch_bounds__(kRenderBlock) void render_small_kernel(const double *__restrict__ verts, const int *__restrict__ faces,
+                                                                    RenderParams p, unsigned long long *__restrict__ keys,
+                                                                    unsigned *__restrict__ list_n, unsigned *__restrict__ list) {
+    const long i = (long)blockIdx.x * kRenderBlock + threadIdx.x;
+    if (i >= (long)p.nv * p.nfaces) return;
+    const int view = (int)(i / p.nfaces);
+    const long f = i - (long)view * p.nfaces;
+    Tri t;
+    if (!render_setup(p, p.view[view], verts, faces, f, t)) return;
+    const long bw = t.x1 - t.x0 + 1, bh = t.y1 - t.y0 + 1;
+    if (bw * bh > kRenderSmallPixels) {
+        list[atomicAdd(list_n, 1u)] = (unsigned)i;        // capacity nv * nfaces: never overflows
+        return;
+    }
+    unsigned long long *kv = keys + (size_t)view * p.H * p.W;
+    for (int y = t.y0; y <= t.y1; ++y)
+        for (int x = t.x0; x <= t.x1; ++x) {
+            const unsigned long long key = render_key(t, x, y, f);
+            if (key != kRenderEmpty) render_store(kv, (size_t)y * p.W + x, key);
+        }
+}
+
+__global__ __launch_bounds__(kRenderBlock) void render_large_kernel(const double *__restrict__ verts, const int *__restrict__ faces,
+                                                                    RenderParams p, unsigned long long *__restrict__ keys,
+                                                                    const unsigned *__restrict__ list_n,
+                                                                    const unsigned *__restrict__ list) {
+    const unsigned n = *list_n;
+    for (unsigned e = blockIdx.x; e < n; e += gridDim.x) {
+        const long i = list[e];
+        const int view = (int)(i / p.nfaces);
+        const long f = i - (long)view * p.nfaces;
+        Tri t;
+        if (!render_setup(p, p.view[view], verts, faces, f, t)) continue;     // (workgroup-uniform: same inputs for every lane)
+        const long bw = t.x1 - t.x0 + 1, npx = bw * (t.y1 - t.y0 + 1);
+        unsigned long long *kv = keys + (size_t)view * p.H * p.W;
+        for (long q = threadIdx.x; q < npx; q += kRenderBlock) {
+            const int y = t.y0 + (int)(q / bw), x = t.x0 + (int)(q - (q / bw) * bw);
+            const unsigned long long key = render_key(t, x, y, f);
+            if (key != kRenderEmpty) render_store(kv, (size_t)y * p.W + x, key);
+        }
+    }
+}
+
+__global__ __launch_bounds__(kRenderBlock) void render_resolve_kernel(const double *__restrict__ verts, const double *__restrict__ normals,
+                                                                      const int *__restrict__ faces, RenderParams p,
+                                                                      const unsigned long long *__restrict__ keys, float *__restrict__ depth,
+                                                                      int *__restrict__ face_out, float *__restrict__ nrm_out) {
+    const long i = (long)blockIdx.x * kRenderBlock + threadIdx.x;
+    const long hw = (long)p.H * p.W;
+    if (i >= (long)p.nv * hw) return;
+    const unsigned long long key = keys[i];
+    if (key == kRenderEmpty) {
+        depth[i] = 0.0f;
+        face_out[i] = -1;
+        if (nrm_out) nrm_out[3 * i] = nrm_out[3 * i + 1] = nrm_out[3 * i + 2] = 0.0f;
+        return;
+    }
+    const int f = (int)(unsigned)(key & 0xFFFFFFFFull);
+    depth[i] = -__uint_as_float((unsigned)(key >> 32));
+    face_out[i] = f;
+    if (!nrm_out) return;
+    const int view = (int)(i / hw);
+    const long pix = i - (long)view * hw;
+    const int y = (int)(pix / p.W), x = (int)(pix - (long)y * p.W);
+    const RenderView &vw = p.view[view];
+    Tri t;
+    double l[3];
+    double n[3] = {0.0, 0.0, 0.0};
+    if (render_setup(p, vw, verts, faces, f, t) && render_bary(t, x, y, l)) {      // (always true: this face wrote the key)
+        const double a0 = l[0] / t.z[0], a1 = l[1] / t.z[1], a2 = l[2] / t.z[2];
+        const double *n0 = normals + 3 * (size_t)faces[3 * f], *n1 = normals + 3 * (size_t)faces[3 * f + 1],
+                     *n2 = normals + 3 * (size_t)faces[3 * f + 2];
+        const double m0 = a0 * n0[0] + a1 * n1[0] + a2 * n2[0];
+        const double m1 = a0 * n0[1] + a1 * n1[1] + a2 * n2[1];
+        const double m2 = a0 * n0[2] + a1 * n1[2] + a2 * n2[2];
+        const double *r = vw.r;
+        n[0] = r[0] * m0 + r[1] * m1 + r[2] * m2;
+        n[1] = r[4] * m0 + r[5] * m1 + r[6] * m2;
+        n[2] = r[8] * m0 + r[9] * m1 + r[10] * m2;
+        const double len = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+        if (len > 0.0) { n[0] /= len; n[1] /= len; n[2] /= len; }
+        else n[0] = n[1] = n[2] = 0.0;
+    }
+    nrm_out[3 * i] = (float)n[0];
+    nrm_out[3 * i + 1] = (float)n[1];
+    nrm_out[3 * i + 2] = (float)n[2];
+}
+
+struct RenderWorkspace {
+    unsigned long long *keys;
+    unsigned *list_n, *list;
+    size_t bytes;
+};
+
+static RenderWorkspace render_workspace(int nv, int H, int W, long nfaces, void *base) {
+    RenderWorkspace w;
+    size_t off = 0;
+    char *b = static_cast<char *>(base);
+    auto take = [&](size_t n) { char *r = b ? b + off : nullptr; off += (n + 15) & ~(size_t)15; return r; };
+    w.keys = reinterpret_cast<unsigned long long *>(take((size_t)nv * H * W * sizeof(unsigned long long)));
+    w.list_n = reinterpret_cast<unsigned *>(take(sizeof(unsigned)));
+    w.list = reinterpret_cast<unsigned *>(take((size_t)nv * nfaces * sizeof(unsigned)));
+    w.bytes = off;
+    return w;
+}
+
+static bool render_sizes_ok(int nv, int H, int W, long nfaces) {
+    return nv >= 1 && nv <= kRenderMaxViews && H >= 1 && W >= 1 && nfaces >= 0 && nfaces < (1L << 31) &&
+           (long)nv * nfaces < (1L << 32) && (long)nv * H * W < (1L << 38);
+}
+
+static int render_params(const char *who, int nv, const double *K, const double *lw, int H, int W, long nverts, long nfaces,
+                         double scale, const double center[3], double half, double znear, RenderParams &p) {
+    DFH_REQUIRE(render_sizes_ok(nv, H, W, nfaces), "%s: bad sizes (views %d in [1, %d], H %d, W %d, faces %ld)", who, nv, kRenderMaxViews,
+                H, W, nfaces);
+    DFH_REQUIRE(nverts >= 0 && nverts < (1L << 31), "%s: bad vertex count %ld", who, nverts);
+    DFH_REQUIRE(K && lw && center, "%s: null host parameter", who);
+    DFH_REQUIRE(znear > 0.0, "%s: znear must be > 0", who);
+    p.nv = nv; p.H = H; p.W = W; p.nverts = nverts; p.nfaces = nfaces;
+    p.scale = scale; p.half = half; p.znear = znear;
+    for (int c = 0; c < 3; ++c) p.center[c] = center[c];
+    for (int v = 0; v < nv; ++v) {
+        const double *k = K + 9 * v;
+        DFH_REQUIRE(k[3] == 0.0 && k[6] == 0.0 && k[7] == 0.0 && k[8] == 1.0,
+                    "%s: K of view %d must be upper-triangular with last row (0, 0, 1)", who, v);
+        p.view[v].k[0] = k[0]; p.view[v].k[1] = k[1]; p.view[v].k[2] = k[2]; p.view[v].k[3] = k[4]; p.view[v].k[4] = k[5];
+        for (int j = 0; j < 12; ++j) p.view[v].r[j] = lw[12 * v + j];
+    }
+    return DFH_OK;
+}
+
+}  // namespace dfh
+
+extern "C" {
+
+size_t dfh_render_workspace_bytes(int n_views, int H, int W, long n_faces) {
+    using namespace dfh;
+    if (!render_sizes_ok(n_views, H, W, n_faces)) return 0;
+    return render_workspace(n_views, H, W, n_faces, nullptr).bytes;
+}
+
+int dfh_render_raster(const double *verts, long n_verts, const int *faces, long n_faces, int n_views, const double *K, const double *lw,
+                      int H, int W, double scale, const double center[3], double half, double znear, void *workspace,
+                      size_t workspace_bytes, void *stream) {
+    using namespace dfh;
+    RenderParams p;
+    const int rc = render_params("dfh_render_raster", n_views, K, lw, H, W, n_verts, n_faces, scale, center, half, znear, p);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(workspace, "dfh_render_raster: null workspace");
+    DFH_REQUIRE(workspace_bytes >= dfh_render_workspace_bytes(n_views, H, W, n_faces), "dfh_render_raster: workspace too small");
+    DFH_REQUIRE(n_faces == 0 || (faces && verts), "dfh_render_raster: null mesh");
+    const RenderWorkspace w = render_workspace(n_views, H, W, n_faces, workspace);
+    hipStream_t s = (hipStream_t)stream;
+    DFH_HIP_CHECK(hipMemsetAsync(w.keys, 0xFF, (size_t)n_views * H * W * sizeof(unsigned long long), s));
+    DFH_HIP_CHECK(hipMemsetAsync(w.list_n, 0, sizeof(unsigned), s));
+    const long npairs = (long)n_views * n_faces;
+    if (npairs == 0) return DFH_OK;
+    const long nb = (npairs + kRenderBlock - 1) / kRenderBlock;
+    DFH_REQUIRE(nb < (1L << 31), "dfh_render_raster: too many triangles");
+    hipLaunchKernelGGL(render_small_kernel, dim3((unsigned)nb), dim3(kRenderBlock), 0, s, verts, faces, p, w.keys, w.list_n, w.list);
+    int dev = 0;
+    DFH_HIP_CHECK(hipGetDevice(&dev));
+    DeviceInfo &di = device_info(dev);
+    if (di.n_cu == 0) DFH_HIP_CHECK(hipDeviceGetAttribute(&di.n_cu, hipDeviceAttributeMultiprocessorCount, dev));
+    const long ng = nb < 4L * di.n_cu ? nb : 4L * di.n_cu;    // the large pairs' count stays on the device: a fixed grid pulls them
+    hipLaunchKernelGGL(render_large_kernel, dim3((unsigned)ng), dim3(kRenderBlock), 0, s, verts, faces, p, w.keys, w.list_n, w.list);
+    DFH_HIP_CHECK(hipGetLastError());
+    return DFH_OK;
+}
+
+int dfh_render_resolve(const double *verts, const double *normals, long n_verts, const int *faces, long n_faces, int n_views,
+                       const double *K, const double *lw, int H, int W, double scale, const double center[3], double half, double znear,
+                       const void *workspace, size_t workspace_bytes, float *depth_out, int *face_out, float *normal_out, void *stream) {
+    using namespace dfh;
+    RenderParams p;
+    const int rc = render_params("dfh_render_resolve", n_views, K, lw, H, W, n_verts, n_faces, scale, center, half, znear, p);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(workspace, "dfh_render_resolve: null workspace");
+    DFH_REQUIRE(workspace_bytes >= dfh_render_workspace_bytes(n_views, H, W, n_faces), "dfh_render_resolve: workspace too small");
+    DFH_REQUIRE(depth_out && face_out, "dfh_render_resolve: null output");
+    DFH_REQUIRE((normals == nullptr) == (normal_out == nullptr), "dfh_render_resolve: normals and normal_out go together");
+    DFH_REQUIRE(n_faces == 0 || (faces && verts), "dfh_render_resolve: null mesh");
+    const RenderWorkspace w = render_workspace(n_views, H, W, n_faces, const_cast<void *>(workspace));
+    const long npix = (long)n_views * H * W;
+    hipLaunchKernelGGL(render_resolve_kernel, dim3((unsigned)((npix + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0,
+                       (hipStream_t)stream, verts, normals, faces, p, w.keys, depth_out, face_out, normal_out);
+    DFH_HIP_CHECK(hipGetLastError());
+    return DFH_OK;
+}
+
+}  // extern "C"

@@ -338,8 +338,50 @@ class Fusion:
         return mat.tolil()
 
     def write_live_frame_mesh(self, path, filename, warpfield_path):
-        """Reference core/fusion.py:589-590: an empty stub there too."""
-        pass
+        """Reference core/fusion.py:588-590 ("Process a warp field file and write the live frame mesh"; an empty stub there): the
+        canonical mesh warped into the live frame (live_frame_mesh) with the nodes of `warpfield_path` (a file of
+        write_warp_field; None / "" = the current `_nodes`), written in write_canonical_mesh's layout.  Returns the file path."""
+        nodes = _io.read_warp_field(warpfield_path) if warpfield_path else None
+        verts, faces, normals = self.live_frame_mesh(nodes)
+        fpath = os.path.join(path, filename)
+        self._write_mesh_file(fpath, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy())
+        return fpath
+
+    def live_frame_mesh(self, nodes=None):
+        """The canonical surface in the live frame, on the device: (verts (V,3) fp64, faces (F,3) int32, normals (V,3) fp64) CUDA
+        tensors.  Marching cubes of the canonical volume as write_canonical_mesh extracts it, each vertex's `_knn` nearest nodes
+        (solve.sample_knn), then the warp of solve()'s data term -- reference `warp(v, normal=n, m_lw=_lw)` per vertex
+        (solve.warp_points).  nodes: reference-shaped 4-tuples (vertex index, position, DQ, weight) as io.read_warp_field returns
+        them; None = `_nodes`.  With no nodes only `_lw` is applied."""
+        self._ensure_volumes()
+        verts, faces, normals = self._canonical_mesh_device()
+        nodes = self._nodes if nodes is None else nodes
+        lw = np.asarray(self._lw, dtype=np.float64)
+        if len(nodes) == 0:
+            vp, vn = _solve.warp_points(verts, normals, lw)
+            return vp, faces, vn
+        pos = np.array([np.asarray(n[1], dtype=np.float64) for n in nodes]).reshape(-1, 3)
+        dq = np.array([np.asarray(n[2], dtype=np.float64) for n in nodes]).reshape(-1, 8)
+        w = np.array([float(n[3]) for n in nodes], dtype=np.float64)
+        if len(pos) < self._knn:
+            raise ValueError('the warp field has %d nodes, fewer than knn = %d' % (len(pos), self._knn))
+        if verts.shape[0] == 0:
+            return verts.to(torch.float64), faces, normals.to(torch.float64)
+        nbr, _ = _solve.sample_knn(verts, pos, w, self._knn)
+        vp, vn = _solve.warp_points(verts, normals, lw, nbr=nbr, node_dq=dq, node_pos=pos, node_w=w)
+        return vp, faces, vn
+
+    def render_live_frame(self, lws, H, W, K=None, scale=1.0, center=np.zeros(3), nodes=None):
+        """Depth / normal / face-id maps of live_frame_mesh(nodes) in the views `lws` (one 3x4 world->camera matrix or a list; one
+        launch), voxels mapped to world by K1's rule (scale, center, half = canonical resolution / 2).  K defaults to `_K`.
+        Returns mesh.render's (depth, normal, face)."""
+        if K is None:
+            K = getattr(self, '_K', None)
+        if K is None:
+            raise ValueError('render_live_frame needs the intrinsics: pass K or set _K')
+        verts, faces, normals = self.live_frame_mesh(nodes)
+        half = self._T.shape[0] / 2.0
+        return _mesh.render(verts, faces, normals, K, lws, H, W, scale=scale, center=center, half=half)
 
     def _write_back(self, sv):
         new_dq = sv.node_dq.cpu().numpy()
@@ -385,7 +427,16 @@ class Fusion:
         """Reference core/fusion.py:577-587: index-space OBJ, `v` / `vn` / `f a b c` (1-based)."""
         self._ensure_volumes()
         verts, faces, normals, values = _mesh.marching_cubes(self._T, None, 1, as_numpy=True)
-        with open(os.path.join(path, filename), 'w') as f:
+        self._write_mesh_file(os.path.join(path, filename), verts, faces, normals)
+
+    def _canonical_mesh_device(self):
+        """The extraction of write_canonical_mesh, left on the device: (verts, faces, normals)."""
+        verts, faces, normals, _ = _mesh.marching_cubes(self._T, None, 1)
+        return verts, faces, normals
+
+    @staticmethod
+    def _write_mesh_file(fpath, verts, faces, normals):
+        with open(fpath, 'w') as f:
             f.write("".join('v %f %f %f\n' % (v[0], v[1], v[2]) for v in verts))
             f.write("".join('vn %f %f %f\n' % (n[0], n[1], n[2]) for n in normals))
             f.write("".join('f %d %d %d\n' % (t[0] + 1, t[1] + 1, t[2] + 1) for t in faces))
@@ -529,7 +580,7 @@ class Fusion:
 def _lend_nonrigid_methods():
     from .fusion_dm import FusionDM
     for name in ("node_arrays", "_gather_nodes", "_locations", "dq_blend", "_dqb_warp", "warp", "_vertex_state", "computef",
-                 "computeSparsity", "construct_graph", "_dq_blend_kdtree", "update_graph"):
+                 "computeSparsity", "construct_graph", "_dq_blend_kdtree", "update_graph", "live_frame_mesh", "render_live_frame"):
         if name not in FusionDM.__dict__:
             setattr(FusionDM, name, Fusion.__dict__[name])
 

@@ -272,9 +272,21 @@ class FusionDM:
         from . import io as _io
         return _io.write_warp_field(self._nodes, path, filename, self._itercounter)
 
+    def _canonical_mesh_device(self):
+        """The extraction of write_canonical_mesh, left on the device: (verts, faces, normals)."""
+        verts, faces, normals, _ = _mesh.marching_cubes(self._T, 0.0, 1)
+        return verts, faces, normals
+
     def write_live_frame_mesh(self, path, filename, warpfield_path):
-        """Reference core/fusion_dm.py:357-358: an empty stub there too."""
-        pass
+        """Reference core/fusion_dm.py:356-358 ("Process a warp field file and write the live frame mesh"; an empty stub there):
+        live_frame_mesh with the nodes of `warpfield_path` (a file of write_warp_field; None / "" = the current `_nodes`), written
+        like write_canonical_mesh (world coordinates through `_IND`).  Returns the file path."""
+        from . import io as _io
+        nodes = _io.read_warp_field(warpfield_path) if warpfield_path else None
+        verts, faces, normals = self.live_frame_mesh(nodes)
+        fpath = os.path.join(path, filename)
+        _mesh.write_obj(fpath, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), ind=self._IND)
+        return fpath
 
     def average_edge_dist_in_face(self, f):
         """Reference core/fusion_dm.py:360-364."""

@@ -126,3 +126,101 @@ def read_obj(fpath):
                 F.append([int(x.split("/")[0]) for x in t[1:4]])
     return (np.array(V, dtype=np.float64).reshape(-1, 3), np.array(F, dtype=np.int64).reshape(-1, 3),
             np.array(N, dtype=np.float64).reshape(-1, 3))
+
+
+def _view_table(K, lws):
+    """(K rows, lw rows, n_views) as flat fp64 numpy arrays: K one 3x3 (shared) or one per view; lws one 3x4 or a list."""
+    lw = np.asarray(lws, dtype=np.float64)
+    if lw.ndim == 2:
+        lw = lw[None]
+    if lw.ndim != 3 or lw.shape[1:] != (3, 4) or len(lw) == 0:
+        raise ValueError("lws must be one 3x4 world->camera matrix or a list of them, got shape %s" % (np.shape(lws),))
+    Km = np.asarray(K, dtype=np.float64)
+    if Km.shape == (3, 3):
+        Km = np.broadcast_to(Km, (len(lw), 3, 3))
+    if Km.shape != (len(lw), 3, 3):
+        raise ValueError("K must be 3x3 (or one 3x3 per view), got shape %s" % (np.shape(K),))
+    if not (np.all(Km[:, 1, 0] == 0) and np.all(Km[:, 2, :2] == 0) and np.all(Km[:, 2, 2] == 1)):
+        raise ValueError("K must be upper-triangular with last row (0, 0, 1)")
+    return np.ascontiguousarray(Km).reshape(-1), np.ascontiguousarray(lw).reshape(-1), len(lw)
+
+
+class render_workspace:
+    """Device scratch of dfh_render_raster / dfh_render_resolve for a (views, H, W, faces) size: the per-pixel keys and the list of
+    large triangles.  mesh.render allocates one per call; a caller that renders the same size repeatedly may pass its own."""
+
+    def __init__(self, n_views, H, W, n_faces, device=None):
+        nbytes = _lib.load().dfh_render_workspace_bytes(int(n_views), int(H), int(W), int(n_faces))
+        if nbytes == 0:
+            raise ValueError("bad render size (views %d, %dx%d, %d faces)" % (n_views, H, W, n_faces))
+        self.nbytes = nbytes
+        self.buf = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device or "cuda")
+
+
+def render(verts, faces, normals, K, lws, H, W, scale=1.0, center=0.0, half=0.0, znear=1e-3, workspace=None, stages=None):
+    """Rasterise one triangle mesh into V views (csrc/dfh_render.hip, semantics in include/dfusion_hip.h): vertices (N,3) in
+    voxel-index space, world = scale * (p - half) + center (K1's voxel -> world map), `lws` one 3x4 world->camera matrix or a list
+    of V (one launch for all), K 3x3.  numpy arrays or CUDA tensors.  normals may be None.
+    Returns (depth (V,H,W) fp32 = -z, 0 where no surface; normal (V,H,W,3) fp32 in the camera frame or None; face (V,H,W) int32,
+    -1 where no surface) as CUDA tensors.  stages: optional callable(name) called after each of the two passes is enqueued
+    (for timing tools)."""
+    require_gpu()
+    lib = _lib.load()
+    Kf, lwf, nv = _view_table(K, lws)
+    H, W = int(H), int(W)
+    dev = torch.device("cuda", torch.cuda.current_device())
+
+    def f64(a, what):
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+        t = t.to(device=dev, dtype=torch.float64).contiguous()
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("%s must be (n,3), got shape %s" % (what, tuple(t.shape)))
+        return t
+    V = f64(verts, "verts")
+    Nn = None if normals is None else f64(normals, "normals")
+    if Nn is not None and Nn.shape[0] != V.shape[0]:
+        raise ValueError("normals and verts disagree in length")
+    F = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(faces)))
+    F = F.to(device=dev, dtype=torch.int32).contiguous()
+    if F.dim() != 2 or F.shape[1] != 3:
+        raise ValueError("faces must be (n,3), got shape %s" % (tuple(F.shape),))
+    ctr = np.broadcast_to(np.asarray(center, dtype=np.float64), (3,))
+    if workspace is None:
+        workspace = render_workspace(nv, H, W, F.shape[0], dev)
+    depth = torch.empty((nv, H, W), dtype=torch.float32, device=dev)
+    face = torch.empty((nv, H, W), dtype=torch.int32, device=dev)
+    normal = None if Nn is None else torch.empty((nv, H, W, 3), dtype=torch.float32, device=dev)
+    Ka, La, Ca = _lib.darr(Kf, 9 * nv), _lib.darr(lwf, 12 * nv), _lib.darr(ctr, 3)
+    ws, nbytes = workspace.buf.data_ptr(), workspace.buf.numel() * 8
+    _lib.check(lib.dfh_render_raster(V.data_ptr(), V.shape[0], F.data_ptr(), F.shape[0], nv, Ka, La, H, W, float(scale), Ca, float(half),
+                                     float(znear), ws, nbytes, current_stream_ptr()), "dfh_render_raster")
+    if stages is not None:
+        stages("raster")
+    _lib.check(lib.dfh_render_resolve(V.data_ptr(), 0 if Nn is None else Nn.data_ptr(), V.shape[0], F.data_ptr(), F.shape[0], nv, Ka, La,
+                                      H, W, float(scale), Ca, float(half), float(znear), ws, nbytes, depth.data_ptr(), face.data_ptr(),
+                                      0 if normal is None else normal.data_ptr(), current_stream_ptr()), "dfh_render_resolve")
+    if stages is not None:
+        stages("resolve")
+    return depth, normal, face
+
+
+def depth_error(rendered, observed, gate):
+    """Rendered against observed depth maps (reference storage convention: negative, 0 = none), per view: a list of dicts
+    {n_valid: pixels valid in both, n_within: those with |difference| <= gate, mean, median: of |difference| over the valid
+    pixels (torch's median: the lower middle value; nan when there are none)}.  (V,H,W) or (H,W) tensors / arrays."""
+    r = rendered if isinstance(rendered, torch.Tensor) else torch.from_numpy(np.asarray(rendered))
+    o = observed if isinstance(observed, torch.Tensor) else torch.from_numpy(np.asarray(observed))
+    o = o.to(device=r.device, dtype=torch.float64)
+    r = r.to(torch.float64)
+    if r.shape != o.shape:
+        raise ValueError("rendered %s and observed %s maps differ in shape" % (tuple(r.shape), tuple(o.shape)))
+    if r.dim() == 2:
+        r, o = r[None], o[None]
+    out = []
+    for v in range(r.shape[0]):
+        valid = (r[v] != 0) & (o[v] != 0)
+        d = (r[v] - o[v])[valid].abs()
+        n = int(d.numel())
+        out.append({"n_valid": n, "n_within": int((d <= gate).sum()) if n else 0,
+                    "mean": float(d.mean()) if n else float("nan"), "median": float(d.median()) if n else float("nan")})
+    return out

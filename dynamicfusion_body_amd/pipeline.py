@@ -11,7 +11,7 @@ import torch
 
 from . import _lib, kernels
 from .device import HostScalar, current_stream_ptr, dtype_code, require_gpu
-from .solve import WarpSolver, sample_knn
+from .solve import WarpSolver, sample_knn, warp_points
 
 
 def extract_surface_samples(T, Wt, band, x0=0, max_samples=None):
@@ -258,6 +258,23 @@ class SlabFrame:
         self._first = True                               # K3 stores its per-voxel neighbourhoods again on the next call
         self.refresh_samples()
         return n_new
+
+    def render_live(self, lws, H, W):
+        """Depth / normal / face-id maps of the loop's current live model in the views `lws` (one 3x4 world->camera matrix or a
+        list; one launch): marching cubes of the canonical volume T at level 0, warped by the solver's node field (node_pos /
+        node_dq / node_w, each vertex's knn nearest nodes) and the loop's identity `lw`, rendered with this frame's K / scale /
+        center / half (mesh.render).  Single rank only: with the volume cut into slabs the meshes would need halo planes and the
+        ranks' z-buffers a merge, which is not implemented (ValueError)."""
+        if self.ws > 1:
+            raise ValueError("render_live renders one rank's whole grid; the %d-rank slab partition is not supported" % self.ws)
+        from . import mesh as _mesh
+        verts, faces, normals, _ = _mesh.marching_cubes(self.T, 0.0, 1)
+        sv = self.fs.solver
+        if verts.shape[0] > 0:
+            nbr, _ = sample_knn(verts, sv.node_pos, sv.node_w, self.knn)
+            verts, normals = warp_points(verts, normals, self.ident_lw, nbr=nbr, node_dq=sv.node_dq, node_pos=sv.node_pos,
+                                         node_w=sv.node_w)
+        return _mesh.render(verts, faces, normals, self.K, lws, H, W, scale=self.scale, center=self.center, half=self.R / 2)
 
     def step(self, depth, lw_cam, gn_iters=10, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.5, stage_ms=None,
              update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None):

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DFH_ABI_VERSION 4
+#define DFH_ABI_VERSION 5
 
 #define DFH_F32 0
 #define DFH_F64 1
@@ -563,6 +563,43 @@ size_t dfh_mc_reorder_workspace_bytes(long n_verts, long n_faces);
 int dfh_mc_reorder(const float *verts_in, const float *normals_in, const float *values_in, int *faces, long n_verts, long n_faces,
                    float *verts_out, float *normals_out, float *values_out, long *used_out, void *workspace,
                    size_t workspace_bytes, void *stream);
+
+/* ---- rasterizer: depth / face-id / normal maps of a triangle mesh in V views (no reference counterpart) -----------------
+ * The model-to-frame prediction of DynamicFusion: the (warped) model as the cameras would see it.  One mesh, V views of
+ * H x W pixels (1 <= V <= 16), one call.  Semantics (restated in numpy by tests/render_np.py; everything in fp64, no
+ * fused multiply-add, operations in the order written):
+ *  - vertices (n_verts x 3 fp64) are in voxel-index space; world w = scale * (p - half) + center (K1's map,
+ *    dfh_integrate_depth); camera c = R w + t with lw = [R | t] (3 x 4 row-major per view, world -> camera), each row
+ *    summed as ((r0 w0 + r1 w1) + r2 w2) + t.
+ *  - K (3 x 3 row-major per view) must be upper-triangular with last row (0, 0, 1) (else DFH_E_BADARG);
+ *    u = (K00 c0 + K01 c1 + K02 c2) / c2, v = (K11 c1 + K12 c2) / c2.  Pixel centres sit at integer (u, v) (the
+ *    convention of scene.render_depth); outputs are indexed [view][v][u].
+ *  - A triangle (faces: n_faces x 3 int32) draws nothing in a view if a vertex index lies outside [0, n_verts), any vertex
+ *    has c2 <= znear or a non-finite u / v, or its area A = E01(u2, v2) is 0 or not finite, where
+ *    E_ab(x, y) = (x - u_a)(v_b - v_a) - (y - v_a)(u_b - u_a).  There is NO clipping: a triangle crossing znear is dropped.
+ *  - Pixels tested: the bounding box [ceil(min u), floor(max u)] x [ceil(min v), floor(max v)] clamped to the image.
+ *    Edge values e0 = E12, e1 = E20, e2 = E01 at the pixel centre, each evaluated from the lexicographically smaller (u, v)
+ *    end point of its edge (E_ab as written if (u_a, v_a) < (u_b, v_b), else -E_ba) so that triangles sharing an edge get
+ *    exactly opposite values.  Covered: all three have A's sign or are 0 (inclusive, no back-face culling: a closed mesh is
+ *    watertight).  lambda_i = e_i / A; s = (lambda0 / z0 + lambda1 / z1) + lambda2 / z2 (z_i = c2 of vertex i); the pixel
+ *    is dropped unless s > 0 and (float)(1 / s) is finite; z = (float)(1 / s), perspective-correct.
+ *  - Z-buffer: one uint64 key per pixel, (bits of z) << 32 | face, reduced with a 64-bit atomicMin (positive floats order
+ *    like their bit patterns): the nearest surface wins, ties go to the lowest face id, independent of scheduling.
+ *  - Resolve: depth (V x H x W fp32) = -z (the reference's storage convention: negative, 0 = no surface, so a rendered map
+ *    can be fused like a camera's); face (V x H x W int32) = winning face, -1 where none; normal (V x H x W x 3 fp32, only
+ *    with normals, n_verts x 3 fp64): m = (a0 n0 + a1 n1) + a2 n2 with a_i = lambda_i / z_i of the winning face, rotated
+ *    into the camera frame by R and normalised (0 where there is no surface or the vector is 0).
+ * dfh_render_raster clears the key buffer of `workspace` (dfh_render_workspace_bytes(n_views, H, W, n_faces) bytes: the keys
+ * and the list of triangles whose box exceeds 64 pixels, which a second launch rasterises workgroup by workgroup) and fills it;
+ * dfh_render_resolve reads it and writes the maps (same mesh, views and map as the raster call).  Both only enqueue on
+ * `stream`; K / lw / center are host arrays read during the call. */
+size_t dfh_render_workspace_bytes(int n_views, int H, int W, long n_faces);
+int dfh_render_raster(const double *verts, long n_verts, const int *faces, long n_faces, int n_views, const double *K, const double *lw,
+                      int H, int W, double scale, const double center[3], double half, double znear, void *workspace,
+                      size_t workspace_bytes, void *stream);
+int dfh_render_resolve(const double *verts, const double *normals, long n_verts, const int *faces, long n_faces, int n_views,
+                       const double *K, const double *lw, int H, int W, double scale, const double center[3], double half, double znear,
+                       const void *workspace, size_t workspace_bytes, float *depth_out, int *face_out, float *normal_out, void *stream);
 
 #ifdef __cplusplus
 }
