@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("DFH_LIB_PATH") or os.path.join(_PKG, "libdfusion_hip.
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dfusion_hip.h")
 
 F32, F64 = 0, 1
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -112,7 +112,7 @@ _SIGNATURES = {
     "dfh_apply_twist": (_int, [_vp, _vp, _int, _dbl, _vp]),
     "dfh_relax_twists": (_int, [_vp, _int, _dbl, _vp]),
     "dfh_gn_global_sampled_bytes": (ctypes.c_size_t, [_int, _int]),
-    "dfh_gn_global_sampled_views": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _int, _c_double_p, _dbl, _vp, _int, _int, _int, _c_double_p,
+    "dfh_gn_global_sampled_views": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _int, _c_double_p, _dbl, _vp, _int, _int, _int, _int, _c_double_p,
                                            _c_double_p, _dbl, _c_double_p, _dbl, _dbl, _int, _dbl, _int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dfh_gn_global_apply": (_int, [_vp, _dbl, _int, _vp, _vp, _vp]),
     "dfh_gn_global_step_bytes": (ctypes.c_size_t, []),

@@ -1240,6 +1240,9 @@ __global__ __launch_bounds__(256) void dqb_reach_kernel(const DqbParams p, const
             if (bz < p.nbz) rs[bz] = (e2 & grp) == grp ? 2 : ((e1 & grp) == grp ? 1 : 0);
         }
     }
+    // bricks beyond the live volume's last word along z (LZ < Z): nothing live there, never constant -- written, not left as
+    // whatever the workspace held (a stale reach would mark them safe and stream tdist into voxels that sample outside)
+    for (int bz = k.WZ * 16 + lane; bz < p.nbz; bz += 64) rs[bz] = 0;
 }
 
 // Per brick: the bound D, the reach it asks for and the verdict (Sb = 1: its voxels take the constant-live stream; 0: the warp

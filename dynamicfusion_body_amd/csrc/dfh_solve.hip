@@ -910,7 +910,7 @@ __device__ void gn_reg_pairs(int block, const int *__restrict__ node_nbr, int N,
 struct AssocArgs {
     AssocParams ap;
     const float *depth;
-    const AssocView *views;     // non-null: n_views float32 views from a dfh_gn_pack_views table (depth / ap.lw_cam unused)
+    const AssocView *views;     // non-null: n_views views from a dfh_gn_pack_views table, of the kernel's depth type (depth / ap.lw_cam unused)
     int n_views;
     int cull;                   // 1: drop, per tile, the views none of its samples can be valid in (tile_view_mask)
 };
@@ -2475,21 +2475,25 @@ __device__ __forceinline__ void apply_twist_one(double *__restrict__ d, double o
     d[4] = nd.w; d[5] = nd.x; d[6] = nd.y; d[7] = nd.z;
 }
 
-// dq <- exp(factor * log(dq)): the node's rigid motion scaled towards the identity (factor in [0, 1]) along its own screw.
-// log of a dual quaternion (q | qe) with q = |q| (cos(t/2), sin(t/2) n): omega = t n, v = 2 vec(qe q*) / |q|^2 -- the inverse of
-// apply_twist_one's exp for a unit q; a non-unit q (the solve never renormalises) comes back unit.
+// dq <- exp(factor * log(dq)): the node's rotation vector and translation both scaled by factor in [0, 1] -- a decoupled scaling of
+// the two, not a scaling along the motion's screw.  log of a dual quaternion (q | qe) with q = |q| (cos(t/2), sin(t/2) n):
+// omega = t n, v = 2 vec(qe q*) / |q|^2 -- the inverse of apply_twist_one's exp for a unit q; a non-unit q (the solve never
+// renormalises) comes back unit.  q and -q are the same motion: the DQ is taken with w >= 0 (v is bilinear in (q, qe): the sign
+// cancels there), so t is in [0, pi] -- with w < 0 the angle would be 2 pi - t the other way round, and scaling it a different
+// rotation.  Restated in oracle/gn_np.relax_twists.
 __global__ __launch_bounds__(256) void relax_twist_kernel(double *__restrict__ node_dq, int N, double factor) {
     const int a = blockIdx.x * 256 + threadIdx.x;
     if (a >= N) return;
     double *d = node_dq + 8 * (size_t)a;
-    const double w = d[0], x = d[1], y = d[2], z = d[3];
+    const double sg = d[0] < 0.0 ? -1.0 : 1.0;
+    const double w = sg * d[0], x = sg * d[1], y = sg * d[2], z = sg * d[3];
     const double n2 = (w * w + x * x) + (y * y + z * z);
     if (!(n2 > 1e-300) || !(n2 < 1e300)) return;                               // (zero / non-finite: left alone)
     const double vn = sqrt(x * x + y * y + z * z);
-    const double th = 2.0 * atan2(vn, w);                                      // rotation angle, (-2 pi, 2 pi]
+    const double th = 2.0 * atan2(vn, w);                                      // rotation angle, [0, pi]
     const double k = vn > 1e-12 ? th / vn : 2.0 / sqrt(n2);                    // omega = k (x, y, z)
     // (0, v) = 2 qe q* / |q|^2
-    const double e0 = d[4], e1 = d[5], e2 = d[6], e3 = d[7];
+    const double e0 = sg * d[4], e1 = sg * d[5], e2 = sg * d[6], e3 = sg * d[7];
     const double inv = 2.0 / n2;
     const double vx = inv * (-e0 * x + e1 * w - e2 * z + e3 * y);
     const double vy = inv * (-e0 * y + e2 * w - e3 * x + e1 * z);
@@ -2577,7 +2581,7 @@ constexpr int kGlobalGrid = 1536;                   // workgroups of the rows ke
 // accumulates X^T X with v_mfma_f64_16x16x4 (16 steps of four samples per tile; A_g and g_g are its entries (i <= j < 6) and
 // (i, 6)); the accumulator is four doubles per lane where 27 running sums per thread made the kernel a 256-VGPR one: one wave
 // per SIMD, a tile's whole chain of dependent loads exposed -- 65 us for config 3's 762 tiles, 131 us for config 5's 5.2 k.
-template <int K>
+template <int K, typename DepthT>
 __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(3, 8))) void gn_global_rows_kernel(const double *__restrict__ spos, const double *__restrict__ snrm,
                                                               const int *__restrict__ nbr, const double *__restrict__ wts,
                                                               const double *__restrict__ node_dq, const BuildParams p, int stride, long n_sub,
@@ -2608,7 +2612,8 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(3, 8))) v
             const D3 x1 = dqb_warp_exact(bh, pfx, pfy, pfz);
             const D3 xp = dqb_warp_exact(p.lw.q, round_f32(x1.x), round_f32(x1.y), round_f32(x1.z));
             double c[3];
-            const bool ok = aa.views ? associate_views<float>(aa.ap, aa.views, aa.n_views, xp, c) : associate_point<float>(aa.ap, aa.depth, xp, c);
+            const bool ok = aa.views ? associate_views<DepthT>(aa.ap, aa.views, aa.n_views, xp, c)
+                                     : associate_point<DepthT>(aa.ap, reinterpret_cast<const DepthT *>(aa.depth), xp, c);
             if (ok) {
                 double Jrow[6 * K];
                 double r = data_row_from(node_dq, idx, w, K, p.lw.q, bh, nb, pfx, pfy, pfz, xp, snrm[3 * (size_t)s], snrm[3 * (size_t)s + 1],
@@ -3758,16 +3763,17 @@ int dfh_gn_global_apply(const double *sums29, double lm_rel, int n_nodes, double
 }
 
 int dfh_gn_global_sampled_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights, int n_samples, int knn,
-                                double *node_dq, int n_nodes, const double lw_dq[8], double huber_delta, const void *views, int n_views, int H, int W,
-                                const double K[9], const double Kinv[9], double scale, const double center[3], double half, double max_dist,
-                                int stride, double lm_rel, int n_steps, double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes,
-                                void *stream) {
+                                double *node_dq, int n_nodes, const double lw_dq[8], double huber_delta, const void *views, int n_views,
+                                int depth_dtype, int H, int W, const double K[9], const double Kinv[9], double scale, const double center[3],
+                                double half, double max_dist, int stride, double lm_rel, int n_steps, double *xi_out, double *sums_out,
+                                void *scratch, size_t scratch_bytes, void *stream) {
     using namespace dfh;
     DFH_REQUIRE(n_steps >= 0 && n_steps <= 100 && stride >= 1, "dfh_gn_global_sampled_views: %d steps, stride %d", n_steps, stride);
     if (n_steps == 0) return DFH_OK;
     DFH_REQUIRE(n_samples >= 0 && node_dq && lw_dq && views && K && Kinv && center && scratch, "dfh_gn_global_sampled_views: null pointer");
     DFH_REQUIRE(n_samples == 0 || (sample_pos && sample_nrm && nbr && weights), "dfh_gn_global_sampled_views: null sample array");
-    DFH_REQUIRE(knn == 4, "dfh_gn_global_sampled_views: knn = 4 only (the frame loop's)");
+    DFH_REQUIRE(knn >= 1 && knn <= 8, "dfh_gn_global_sampled_views: knn = %d (1..8)", knn);
+    DFH_REQUIRE(depth_dtype == DFH_F32 || depth_dtype == DFH_F64, "dfh_gn_global_sampled_views: bad depth_dtype");
     DFH_REQUIRE(n_views >= 1 && n_views <= DFH_GN_MAX_VIEWS && n_nodes >= 1 && lm_rel >= 0.0 && huber_delta >= 0.0, "dfh_gn_global_sampled_views: bad arguments");
     DFH_REQUIRE(scratch_bytes >= dfh_gn_global_sampled_bytes(n_samples, stride), "dfh_gn_global_sampled_views: scratch too small");
     DFH_REQUIRE(!sums_out || n_steps == 1, "dfh_gn_global_sampled_views: sums_out (the caller reduces over ranks and applies) takes one step per call");
@@ -3787,10 +3793,24 @@ int dfh_gn_global_sampled_views(const double *sample_pos, const double *sample_n
     double *tile_part = static_cast<double *>(scratch);
     double *sums = sums_out ? sums_out : tile_part + (size_t)kGlobalVals * kGlobalGrid;
     hipStream_t st = (hipStream_t)stream;
+    const bool f64 = depth_dtype == DFH_F64;
     for (int g = 0; g < n_steps; ++g) {
-        if (n_wg > 0)
-            hipLaunchKernelGGL(gn_global_rows_kernel<4>, dim3((unsigned)n_wg), dim3(kTile), 0, st, sample_pos, sample_nrm, nbr, weights,
-                               (const double *)node_dq, bp, stride, n_sub, tile_part, aa);
+        if (n_wg > 0) {
+#define DFH_GLOBAL_ROWS(KK)                                                                                                        \
+    case KK:                                                                                                                       \
+        if (f64)                                                                                                                   \
+            hipLaunchKernelGGL((gn_global_rows_kernel<KK, double>), dim3((unsigned)n_wg), dim3(kTile), 0, st, sample_pos, sample_nrm, \
+                               nbr, weights, (const double *)node_dq, bp, stride, n_sub, tile_part, aa);                            \
+        else                                                                                                                       \
+            hipLaunchKernelGGL((gn_global_rows_kernel<KK, float>), dim3((unsigned)n_wg), dim3(kTile), 0, st, sample_pos, sample_nrm, \
+                               nbr, weights, (const double *)node_dq, bp, stride, n_sub, tile_part, aa);                            \
+        break
+            switch (knn) {
+                DFH_GLOBAL_ROWS(1); DFH_GLOBAL_ROWS(2); DFH_GLOBAL_ROWS(3); DFH_GLOBAL_ROWS(4);
+                DFH_GLOBAL_ROWS(5); DFH_GLOBAL_ROWS(6); DFH_GLOBAL_ROWS(7); DFH_GLOBAL_ROWS(8);
+            }
+#undef DFH_GLOBAL_ROWS
+        }
         if (sums_out) hipLaunchKernelGGL(gn_global_finish_kernel<false>, dim3(1), dim3(1024), 0, st, (const double *)tile_part, n_wg, sums, lm_rel, n_nodes, node_dq, xi_out);
         else hipLaunchKernelGGL(gn_global_finish_kernel<true>, dim3(1), dim3(1024), 0, st, (const double *)tile_part, n_wg, sums, lm_rel, n_nodes, node_dq, xi_out);
     }

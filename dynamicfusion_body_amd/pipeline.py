@@ -11,7 +11,7 @@ import torch
 
 from . import _lib, kernels
 from .device import HostScalar, current_stream_ptr, dtype_code, require_gpu
-from .solve import WarpSolver, sample_knn, warp_points
+from .solve import WarpSolver, relax_twists, sample_knn, warp_points
 
 
 def extract_surface_samples(T, Wt, band, x0=0, max_samples=None):
@@ -351,13 +351,13 @@ class SlabFrame:
         kernels.fuse_volume_dqb(self.T, self.Wt, live_full, sv.node_pos, sv.node_dq, sv.node_w, self.knn, self.ident_lw, self.tvox,
                                 res=(R, R, R), x_range=(self.a, self.b), workspace=self.ws_dqb, rebuild_candidates=self._first)
         self._first = False
-        # the warp field decays towards the identity once the TSDF update has used it (dfh_relax_twists: every node's motion
-        # scaled by `relax` along its own screw).  Fusion.updateTSDF writes most of the motion into the canonical volume every
+        # the warp field decays towards the identity once the TSDF update has used it (solve.relax_twists: every node's rotation
+        # vector and translation scaled by `relax`).  Fusion.updateTSDF writes most of the motion into the canonical volume every
         # frame, and without a term that pulls a node back the field random-walks over hundreds of frames
         # (tools/soak.py; tests/test_gpu_pipeline.py::test_soak_300_frames).  relax = 1 keeps round 3's behaviour.
         rx = self.RELAX if relax is None else float(relax)
         if rx != 1.0:
-            _lib.check(_lib.load().dfh_relax_twists(sv.node_dq.data_ptr(), int(sv.N), rx, current_stream_ptr()), "dfh_relax_twists")
+            relax_twists(sv.node_dq, rx)
         if self.updated is None:
             self.updated = torch.cuda.Event()
         self.updated.record()                  # the canonical slab of this frame is final from here on (a consumer on another

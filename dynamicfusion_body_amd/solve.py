@@ -146,6 +146,18 @@ def sample_knn(sample_pos, node_pos, node_w, knn, bricks=None):
     return nbr, wts
 
 
+def relax_twists(node_dq, factor):
+    """node_dq <- exp(factor log node_dq) in place (dfh_relax_twists; asynchronous): every node's rotation vector and translation
+    scaled by `factor` in [0, 1] (the frame loop's per-frame decay of the warp field).  node_dq: a contiguous (N, 8) fp64 CUDA
+    tensor.  factor = 1 leaves it untouched; zero or non-finite DQs are left alone.  Restated in oracle/gn_np.relax_twists."""
+    if not (isinstance(node_dq, torch.Tensor) and node_dq.is_cuda and node_dq.dtype == torch.float64 and node_dq.dim() == 2
+            and node_dq.shape[1] == 8 and node_dq.is_contiguous()):
+        raise ValueError("node_dq must be a contiguous (N, 8) float64 CUDA tensor")
+    _lib.check(_lib.load().dfh_relax_twists(node_dq.data_ptr(), int(node_dq.shape[0]), float(factor), current_stream_ptr()),
+               "dfh_relax_twists")
+    return node_dq
+
+
 def solve_rigid_gn(x0, verts, normals, corr, valid=None, iters=10, lm=0.0):
     """Gauss-Newton on 0.5*|FusionDM.computef_lw(x)|^2 over the 6-DoF left twist of x.
     Returns (x, [cost before each step])."""
@@ -576,8 +588,11 @@ class WarpSolver:
         return depth, lw_cam, False
 
     def _views_table(self, depths, lw_cams):
-        """Device table of a frame's views (dfh_gn_pack_views: extrinsics, their inverses, depth pointers), rebuilt only when
-        the depth tensors or the extrinsics change (a frame's iterations share it).  Returns (table, n_views, H, W)."""
+        """Device table of a frame's views (dfh_gn_pack_views: extrinsics, their inverses, depth pointers; float32 maps: also the
+        16 x 16-pixel cells' depth ranges, dfh_gn_pack_views_cells), rebuilt only when the depth tensors, their contents or the
+        extrinsics change (a frame's iterations share it).  Contents: the key holds every tensor's version counter, which torch
+        bumps on each in-place write (copy_, fill_, indexing assignment, out= ops); writes that bypass torch -- a kernel or a
+        copy through the raw data_ptr -- are not seen, and such a caller must pass new tensors.  Returns (table, n_views, H, W)."""
         for d in depths:
             if not (isinstance(d, torch.Tensor) and d.is_cuda and d.dim() == 2 and d.is_contiguous()):
                 raise ValueError("depth must be a contiguous 2-D CUDA tensor")
@@ -585,7 +600,8 @@ class WarpSolver:
                 raise ValueError("the depth maps of one frame must share a shape and a dtype")
         n = len(depths)
         lw = np.ascontiguousarray(np.stack([np.asarray(m, dtype=np.float64).reshape(12) for m in lw_cams]))
-        key = (tuple(int(d.data_ptr()) for d in depths), lw.tobytes(), current_stream_ptr())
+        # (the tensors' versions: a depth map refreshed in place -- copy_, fill_, ... -- has new cells)
+        key = (tuple(int(d.data_ptr()) for d in depths), tuple(int(d._version) for d in depths), lw.tobytes(), current_stream_ptr())
         if getattr(self, "_views_key", None) != key:
             ptrs = (ctypes.c_void_p * n)(*[int(d.data_ptr()) for d in depths])
             Hh, Ww = (int(v) for v in depths[0].shape)
@@ -809,7 +825,8 @@ class WarpSolver:
             self._gs_ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device="cuda")
         sharded = self.distributed and (_dist.world()[1] > 1 or self.force_collective)
         args = (self.spos.data_ptr(), self.snrm.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(), self.S, self.knn, self.node_dq.data_ptr(),
-                self.N, _lib.darr(lw_dq, 8), float(huber), tab.data_ptr(), nv, H, W, _lib.darr(K, 9), _lib.darr(Kinv, 9), float(scale),
+                self.N, _lib.darr(lw_dq, 8), float(huber), tab.data_ptr(), nv, dtype_code(depth[0] if many else depth), H, W,
+                _lib.darr(K, 9), _lib.darr(Kinv, 9), float(scale),
                 _lib.darr(np.asarray(center, dtype=np.float64), 3), float(half), float(max_dist), int(stride), float(lm_rel))
         if not sharded:
             _lib.check(self.lib.dfh_gn_global_sampled_views(*args, int(n_steps), self.global_xi.data_ptr(), 0, self._gs_ws.data_ptr(),

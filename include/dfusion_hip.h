@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DFH_ABI_VERSION 5
+#define DFH_ABI_VERSION 6
 
 #define DFH_F32 0
 #define DFH_F64 1
@@ -485,8 +485,10 @@ int dfh_pcg_status_peek(void *stream, long *aborted_solves_out);
 
 /* node_dq[a] <- exp(step * xi[a]) (x) node_dq[a]; exp = rotation exp(omega), translation v. */
 int dfh_apply_twist(double *node_dq, const double *xi, int n_nodes, double step, void *stream);
-/* node_dq[a] <- exp(factor * log(node_dq[a])), 0 <= factor <= 1: every node's rigid motion scaled towards the identity along its
- * own screw (a unit dual quaternion comes back; zero / non-finite entries are left alone).  The composed frame loop calls it once
+/* node_dq[a] <- exp(factor * log(node_dq[a])), 0 <= factor <= 1: every node's rotation vector and translation scaled by factor
+ * towards the identity (a decoupled scaling of the two; q and -q relax alike: the log is taken with w >= 0, rotation angles in
+ * [0, pi]; a unit dual quaternion comes back; entries whose |q|^2 is not inside (1e-300, 1e300), zero or non-finite ones, are left
+ * alone; factor = 1 launches nothing).  Restated in oracle/gn_np.relax_twists.  The composed frame loop calls it once
  * per frame after the TSDF update (pipeline.SlabFrame.step(relax=...)): Fusion.updateTSDF moves the canonical surface most of
  * the way to the live one every frame (core/fusion.py:180-190: the live sample weighs wi ~ tens against a canonical weight that
  * starts at the view count), so what the field carried is largely in the volume afterwards -- without this decay nothing ever
@@ -506,15 +508,16 @@ int dfh_relax_twists(double *node_dq, int n_nodes, double factor, void *stream);
  * common left twist only rotates its residuals).  n_steps steps, each three short launches (rows, the 29 sums -- 21 upper entries
  * of A_g, 6 of g_g, objective, valid count -- and solve + apply); xi_out (8 doubles, may be NULL): the last step's twist | its
  * objective | its valid-sample count.  scratch: dfh_gn_global_sampled_bytes(n_samples, stride) bytes.  Sums in a fixed order: the
- * same bits every run.  knn = 4.  sums_out != NULL (n_steps = 1): only the 29 sums of THIS rank's samples are produced (32 doubles)
+ * same bits every run.  knn 1..8; depth_dtype (DFH_F32 / DFH_F64): the element type of the views' depth maps, as in
+ * dfh_gn_associate_views (the table holds pointers only).  sums_out != NULL (n_steps = 1): only the 29 sums of THIS rank's samples are produced (32 doubles)
  * -- the caller all-reduces them over ranks and calls dfh_gn_global_apply: every rank then applies the same twist.
  * Restated in oracle/gn_np.global_step_sampled. */
 size_t dfh_gn_global_sampled_bytes(int n_samples, int stride);
 int dfh_gn_global_sampled_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights, int n_samples, int knn,
-                                double *node_dq, int n_nodes, const double lw_dq[8], double huber_delta, const void *views, int n_views, int H, int W,
-                                const double K[9], const double Kinv[9], double scale, const double center[3], double half, double max_dist,
-                                int stride, double lm_rel, int n_steps, double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes,
-                                void *stream);
+                                double *node_dq, int n_nodes, const double lw_dq[8], double huber_delta, const void *views, int n_views,
+                                int depth_dtype, int H, int W, const double K[9], const double Kinv[9], double scale, const double center[3],
+                                double half, double max_dist, int stride, double lm_rel, int n_steps, double *xi_out, double *sums_out,
+                                void *scratch, size_t scratch_bytes, void *stream);
 int dfh_gn_global_apply(const double *sums29, double lm_rel, int n_nodes, double *node_dq, double *xi_out, void *stream);
 size_t dfh_gn_global_step_bytes(void);
 int dfh_gn_global_step(const double *vals, int n_blocks, const double *rhs, int n_nodes, double lm_rel, double *node_dq, double *xi_out,

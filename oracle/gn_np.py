@@ -62,6 +62,31 @@ def apply_twists(dqs, xi):
     return dq_mul(twist_exp_dq(xi), dqs)
 
 
+def relax_twists(dqs, f):
+    """The frame loop's per-frame decay of the warp field (dfh_relax_twists): every DQ's rigid motion, as (rotation vector omega,
+    translation t), scaled by f -- exp(f [omega, t]) -- a decoupled scaling of the two, not a scaling along the motion's screw.
+    q and -q are the same motion, so a DQ with w < 0 is negated first and the angle theta = 2 atan2(|vec q|, w) lies in [0, pi];
+    t = 2 vec(qe q*) / |q|^2, so a non-unit DQ relaxes like its normalised self and a unit one comes back.  A DQ whose |q|^2 is 0
+    or not finite -- in the kernel's terms: not inside (1e-300, 1e300) -- is left unchanged.  (dfh_relax_twists launches nothing
+    for f = 1: node_dq stays as it is, which is this function's result up to the sign and the normalisation.)"""
+    d = np.array(dqs, dtype=np.float64).reshape(-1, 8)
+    out = d.copy()
+    n2 = np.sum(d[:, :4] * d[:, :4], axis=1)
+    ok = (n2 > 1e-300) & (n2 < 1e300)
+    if not ok.any():
+        return out.reshape(np.shape(dqs))
+    x = d[ok]
+    x = np.where(x[:, :1] < 0.0, -x, x)
+    q, qe, n2 = x[:, :4], x[:, 4:], n2[ok]
+    vn = np.sqrt(np.sum(q[:, 1:] * q[:, 1:], axis=1))
+    th = 2.0 * np.arctan2(vn, q[:, 0])
+    k = np.where(vn > 0.0, th / np.where(vn > 0.0, vn, 1.0), 2.0 / np.sqrt(n2))
+    om = k[:, None] * q[:, 1:]
+    t = 2.0 * qmul(qe, qconj(q))[:, 1:] / n2[:, None]
+    out[ok] = twist_exp_dq(float(f) * np.concatenate([om, t], axis=1))
+    return out.reshape(np.shape(dqs))
+
+
 def warp_closed(q, p):
     """dqb_warp without the float32 rounding: vec(r P r*) + 2 vec(d r*)."""
     r, d = q[..., :4], q[..., 4:]

@@ -81,6 +81,45 @@ def test_twist_exp_first_order_and_group():
     assert np.allclose(M[:3, 3], big[0, 3:])
 
 
+def _random_motions(rng, n, max_angle=0.97 * np.pi):
+    """Unit DQs with rotation angles in (0, max_angle) about random axes and translations of a few units."""
+    ax = rng.normal(size=(n, 3))
+    ax /= np.linalg.norm(ax, axis=1, keepdims=True)
+    ang = rng.uniform(0.0, max_angle, size=n)
+    return G.twist_exp_dq(np.concatenate([ax * ang[:, None], rng.normal(scale=2.0, size=(n, 3))], axis=1)), ang
+
+
+def test_relax_twists_restatement():
+    """oracle relax_twists (what dfh_relax_twists computes): f = 1 is the same rigid motion, f = 0 the identity, q and -q relax
+    alike, relaxing by a then b is relaxing by a b (rotations below pi), a scaled DQ relaxes like its normalised self, and a
+    zero or non-finite DQ is left unchanged -- all to 1e-12."""
+    rng = np.random.default_rng(21)
+    dq, ang = _random_motions(rng, 400)
+    pts = rng.uniform(-20.0, 20.0, size=(400, 3))
+    for stored in (dq, -dq):
+        one = G.relax_twists(stored, 1.0)
+        assert np.abs(G.warp_closed(one, pts) - G.warp_closed(dq, pts)).max() <= 1e-12
+        assert np.abs(one - dq).max() <= 1e-12                                 # (and in the w >= 0 half)
+        assert np.array_equal(G.relax_twists(stored, 0.0), np.tile([1.0, 0, 0, 0, 0, 0, 0, 0], (400, 1)))
+    for f in (0.3, 0.8):
+        a = G.relax_twists(dq, f)
+        assert np.abs(G.relax_twists(-dq, f) - a).max() <= 1e-12
+        # the relaxed rotation angle is f theta, about the same axis
+        assert np.abs(2.0 * np.arctan2(np.linalg.norm(a[:, 1:4], axis=1), a[:, 0]) - f * ang).max() <= 1e-12
+        for s in (0.5, 1.03, 1e3):
+            assert np.abs(G.relax_twists(s * dq, f) - a).max() <= 1e-12, s
+            assert np.abs(G.relax_twists(-s * dq, f) - a).max() <= 1e-12, s
+    for a_, b_ in ((0.8, 0.8), (0.3, 0.5), (0.9, 0.25)):
+        assert np.abs(G.relax_twists(G.relax_twists(dq, a_), b_) - G.relax_twists(dq, a_ * b_)).max() <= 1e-12
+    # the translation part is the twist's: f = 0.5 of a pure translation t is t / 2
+    t = rng.normal(size=(5, 3))
+    pure_t = G.twist_exp_dq(np.concatenate([np.zeros((5, 3)), t], axis=1))
+    assert np.abs(G.warp_closed(G.relax_twists(pure_t, 0.5), np.zeros((5, 3))) - 0.5 * t).max() <= 1e-12
+    bad = np.array([[0.0] * 8, [np.nan, 0, 0, 0, 1, 0, 0, 0], [np.inf, 1, 0, 0, 0, 0, 0, 0], [0, 0, -np.inf, 0, 0, 0, 0, 0]])
+    out = G.relax_twists(bad, 0.5)
+    assert np.array_equal(np.isnan(out), np.isnan(bad)) and np.array_equal(out[~np.isnan(bad)], bad[~np.isnan(bad)])
+
+
 def test_gn_descends_and_converges(golden):
     """Noise-free correspondences generated by a known warp field.  The problem is badly
     conditioned (200 point-to-plane rows for 120 unknowns, weak regulariser): undamped GN

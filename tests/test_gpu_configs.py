@@ -493,3 +493,108 @@ def test_rigid_mode_step_variants_and_oracle():
     fs.global_iteration(depths, lws, rw=0.0, max_dist=2.0, huber=0.5, lm_rel=0.1, n_iters=1, built=True)
     xi_b = sv.global_xi.cpu().numpy()[:6]
     assert np.abs(xi_b - xi_all).max() <= 1e-9 * max(1.0, np.abs(xi_all).max()), (xi_b, xi_all)
+
+
+_RIGID_SCENE = {}
+
+
+def _rigid_scene():
+    """test_rigid_mode_step_variants_and_oracle's R = 96 scene, built once: canonical volume, Fibonacci nodes, three live views of
+    the displaced sphere rendered in float64 (float32 copies alongside), a perturbed start field."""
+    if not _RIGID_SCENE:
+        R, N = 96, 128
+        K, Kinv, (H, W), scale, center, tdist, T, Wt = canonical(R, "C2")
+        node_pos, node_w = scene.fibonacci_nodes(N, R)
+        lws = [scene.view_extrinsic(a) for a in (0.0, 40.0, -40.0)]
+        off = np.array([0.5, -0.3, 0.2]) * scale
+        live64 = [scene.render_depth(K, lw, H, W, dtype=np.float64, invalid_frac=0.0, sphere_offset=off) for lw in lws]
+        # (the back wall of view 0 lies at a float32-exact depth: every depth is moved by 1 .. 2 parts in 2^31, below float32's ulp)
+        rng = np.random.default_rng(11)
+        live64 = [d * (1.0 + rng.uniform(1.0, 2.0, size=d.shape) * 2.0 ** -31) for d in live64]
+        dq0 = G.apply_twists(np.tile(IDENT, (N, 1)), np.random.default_rng(4).normal(scale=[1e-3] * 3 + [0.1] * 3, size=(N, 6)))
+        _RIGID_SCENE.update(R=R, N=N, K=K, Kinv=Kinv, H=H, W=W, scale=scale, center=center, T=T, Wt=Wt, node_pos=node_pos,
+                            node_w=node_w, lws=lws, live64=live64, dq0=dq0)
+    return _RIGID_SCENE
+
+
+@pytest.mark.parametrize("knn", [1, 3, 4, 8])
+@pytest.mark.parametrize("depth_dtype", [np.float32, np.float64])
+def test_rigid_mode_step_every_depth_dtype_and_knn(depth_dtype, knn):
+    """The rigid-mode step (dfh_gn_global_sampled_views) on every input the node iterations accept: float32 and float64 depth maps
+    (the float64 values are NOT float32-representable: a step that read them as float32, or cast them, fails), knn 1 .. 8, one and
+    three views, stride 1 and 3 -- against oracle/gn_np.global_step_sampled: twist to 1e-9 relative, valid count exact, node DQs
+    to 1e-9.  All-zero depth maps (no valid row): no step, no error."""
+    s = _rigid_scene()
+    R, N, K, Kinv, scale, center = s["R"], s["N"], s["K"], s["Kinv"], s["scale"], s["center"]
+    fs = FrameSolver(K, scale, center, R / 2, knn=knn, pcg_iters=10, distributed=False)
+    fs.set_graph(s["node_pos"], np.tile(IDENT, (N, 1)), s["node_w"])
+    assert fs.set_canonical(s["T"], s["Wt"], band=2.0) > 5000
+    sv = fs.solver
+    pos, nrm, nbr, _ = host_arrays(sv)
+    assert nbr.shape[1] == knn
+    lives = [d.astype(depth_dtype) for d in s["live64"]]
+    if depth_dtype == np.float64:
+        valid = lives[0] != 0
+        assert np.mean(lives[0][valid] != lives[0][valid].astype(np.float32)) > 0.99
+    depths = [torch.from_numpy(d).cuda() for d in lives]
+    dq0 = s["dq0"]
+    for views in ((0,), (0, 1, 2)):
+        lws_v, lives_v = [s["lws"][v] for v in views], [lives[v] for v in views]
+        arg_d = [depths[v] for v in views] if len(views) > 1 else depths[views[0]]
+        arg_lw = lws_v if len(views) > 1 else lws_v[0]
+
+        def assoc(w):
+            c, v, _ = G.associate_depth_views(w, K, Kinv, lws_v, lives_v, scale, center, R / 2, 2.0)
+            return c, v
+        for stride in (1, 3):
+            sv.node_dq.copy_(torch.from_numpy(dq0).cuda())
+            fs.global_iteration(arg_d, arg_lw, max_dist=2.0, huber=0.5, lm_rel=0.1, n_iters=1, stride=stride)
+            xi = sv.global_xi.cpu().numpy()
+            dq_o, xi_o, n_o = G.global_step_sampled(dq0, pos, nrm, nbr, s["node_pos"], s["node_w"], IDENT, assoc, 0.5, 0.1, stride=stride)
+            tag = (depth_dtype.__name__, knn, len(views), stride)
+            assert int(xi[7]) == n_o and n_o > 300, (tag, int(xi[7]), n_o)
+            assert np.abs(xi[:6] - xi_o).max() <= 1e-9 * max(1.0, np.abs(xi_o).max()), (tag, xi[:6], xi_o)
+            assert np.abs(sv.node_dq.cpu().numpy() - dq_o).max() <= 1e-9, tag
+            assert np.linalg.norm(xi_o[3:]) > 0.01, tag                      # (a real step: the live sphere is 0.6 voxel away)
+    # no valid row at all: no step (twist 0, node DQs as they were), no error
+    zeros = [torch.zeros_like(d) for d in depths]
+    for arg_d, arg_lw in ((zeros[0], s["lws"][0]), (zeros, s["lws"])):
+        sv.node_dq.copy_(torch.from_numpy(dq0).cuda())
+        fs.global_iteration(arg_d, arg_lw, max_dist=2.0, huber=0.5, lm_rel=0.1, n_iters=2, stride=1)
+        xi = sv.global_xi.cpu().numpy()
+        assert int(xi[7]) == 0 and np.array_equal(xi[:6], np.zeros(6))
+        assert np.array_equal(sv.node_dq.cpu().numpy(), dq0)
+
+
+def test_frame_step_with_knn3_and_float64_depth():
+    """SlabFrame.step with its defaults (two rigid-mode steps in front of the node iterations) runs with knn = 3, the reference's
+    value; and a frame fed float64 depth maps whose values are float32-exact ends where the same frame fed the float32 maps does
+    (node DQs to 1e-9; the paths differ -- separate association and build for float64, the fused build for float32 -- but are
+    pinned bit-identical elsewhere, so the two are expected to agree bit for bit; the test prints whether they do)."""
+    R, N = 64, 96
+    H, W, fx, cx, cy = scene.CAMERAS["C2"]
+    K = scene.intrinsics(fx, cx, cy)
+    scale, center, tdist = scene.grid_params(R)
+    node_pos, node_w = scene.fibonacci_nodes(N, R)
+    lws = [scene.view_extrinsic(a) for a in (0.0, 40.0, -40.0)]
+    first = [torch.from_numpy(scene.render_depth(K, lw, H, W, dtype=np.float32, invalid_frac=0.0)).cuda() for lw in lws]
+    off = np.array([0.4, -0.25, 0.15]) * scale
+    live32 = [scene.render_depth(K, lw, H, W, dtype=np.float32, invalid_frac=0.0, sphere_offset=off) for lw in lws]
+    out = {}
+    for knn, dt in ((3, np.float32), (4, np.float32), (4, np.float64)):
+        sf = SlabFrame(K, scale, center, R, tdist / scale, node_pos, node_w, knn=knn, pcg_iters=10, band=2.0, distributed=False)
+        for d, lw in zip(first, lws):
+            sf.integrate(d, lw)
+        sf.refresh_samples()
+        ds = [torch.from_numpy(d.astype(dt)).cuda() for d in live32]
+        counts = [sf.step(ds, lws), sf.step(ds[0], lws[0])]
+        torch.cuda.synchronize()
+        dq = sf.fs.solver.node_dq.cpu().numpy()
+        assert np.isfinite(dq).all() and min(counts) > 1000, (knn, dt)
+        assert np.abs(dq[:, 4:]).max() > 1e-3, (knn, dt)                   # the field moved
+        out[(knn, dt)] = (counts, dq, sf.T.clone(), sf.Wt.clone())
+    a, b = out[(4, np.float32)], out[(4, np.float64)]
+    assert a[0] == b[0]
+    assert np.abs(a[1] - b[1]).max() <= 1e-9
+    print("float64 vs float32 depth: node DQs bit-identical %s, canonical volume bit-identical %s"
+          % (np.array_equal(a[1], b[1]), torch.equal(a[2], b[2]) and torch.equal(a[3], b[3])))

@@ -364,15 +364,19 @@ def test_dqb_float32_paths_give_the_same_bits(field):
 
 
 # ------------------------------------------------------------------------------ K3: the constant-live skip (round 4)
-def _skip_scene(res, N, tdist, field, seed=3):
+def _skip_scene(res, N, tdist, field, seed=3, live_res=None):
+    """live_res: the live volume's extent (default: the canonical grid's), the same sphere sampled on that grid."""
     from dynamicfusion_body_amd.dq import twist_exp_dq
     rng = np.random.default_rng(seed)
-    gx, gy, gz = (torch.arange(r, device="cuda", dtype=torch.float32) for r in res)
     c = [r / 2 for r in res]
-    d = torch.sqrt((gx[:, None, None] - c[0]) ** 2 + (gy[None, :, None] - c[1]) ** 2 + (gz[None, None, :] - c[2]) ** 2)
+
+    def dist(shape):
+        gx, gy, gz = (torch.arange(r, device="cuda", dtype=torch.float32) for r in shape)
+        return torch.sqrt((gx[:, None, None] - c[0]) ** 2 + (gy[None, :, None] - c[1]) ** 2 + (gz[None, None, :] - c[2]) ** 2)
+    d = dist(res)
     rad = 0.3 * min(res)
     # a live volume as K1 leaves it: the truncation value away from the surface (in front of it and where nothing was seen)
-    live = torch.clamp(d - rad + 0.7, -tdist, tdist).contiguous()
+    live = torch.clamp((d if live_res is None else dist(live_res)) - rad + 0.7, -tdist, tdist).contiguous()
     T0 = torch.clamp(d - rad, -tdist, tdist).contiguous()
     W0 = (torch.rand(res, device="cuda") < 0.7).float() * 2.0                  # (zeros: the first-touch rule)
     W0[: res[0] // 3] = 9.0                                                    # saturated, T at tdist far out: the stream's "nothing changes" shortcut
@@ -454,3 +458,91 @@ def test_dqb_skip_bound_holds_for_every_voxel():
         assert bool((disp[finite] <= bound[finite]).all()), float((disp[finite] / bound[finite]).max())
         tightest.append(float((disp[finite] / bound[finite]).max()))
     assert max(tightest) > 0.3, tightest                                       # ... and the bound is not vacuous
+
+
+# ------------------------------------------------------------------------------ K3: live volume of another size than the canonical grid
+@pytest.mark.parametrize("res,live_res", [((24, 20, 40), (24, 20, 28)), ((24, 20, 40), (24, 20, 52)), ((24, 20, 40), (15, 20, 40)),
+                                          ((24, 20, 40), (31, 20, 40)), ((24, 20, 40), (24, 13, 40)), ((24, 20, 40), (24, 27, 40)),
+                                          ((20, 24, 36), (26, 17, 45))])
+def test_dqb_live_volume_of_another_size_vs_oracle(res, live_res):
+    """K3 (skip off) with a live volume smaller and larger than the canonical grid along each axis, against the fp64 oracle with
+    the bars and the mask check of test_dqb_vs_oracle: a voxel whose warped position falls outside the live volume takes no
+    update, one inside samples the live volume at its own extents."""
+    from dynamicfusion_body_amd import _lib
+    rng = np.random.default_rng(sum(live_res))
+    N, k, tdist = 40, 4, 2.0
+    node_pos = rng.uniform(0, np.array(res) - 1, size=(N, 3))
+    node_dq = np.array([small_dq(rng, 0.02, 0.6, 1 + 0.02 * rng.normal()) for _ in range(N)])
+    node_w = rng.uniform(2.0, 5.0, size=N)
+    lw = small_dq(rng, 0.01, 0.3, 0.99)
+    T0 = sphere_volume(res, np.array(res) / 2.0, min(res) / 3.0, tdist)
+    W0 = (rng.random(res) < 0.6) * rng.uniform(0.5, 3.0, size=res)
+    live = sphere_volume(live_res, np.array(res) / 2.0 + 0.4, min(res) / 3.1, tdist) + 0.01 * rng.normal(size=live_res)
+    To, Wo = T0.copy(), W0.copy()
+    _, _, mask = O.update_tsdf_dqb(To, Wo, live, node_pos, node_dq, node_w, k, lw, tdist, wmax=7.0, return_mask=True)
+    pos = np.stack(np.meshgrid(*[np.arange(r, dtype=np.float64) for r in res], indexing="ij"), axis=-1).reshape(-1, 3)
+    loc = O.knn_bruteforce(pos, node_pos, k)
+    wp = O.warp(pos, node_dq[loc], node_pos[loc], node_w[loc], m_lw=lw).reshape(res + (3,))
+    outside = (wp.min(axis=-1) < 0) | (wp > np.array(live_res) - 1).any(axis=-1)
+    assert outside.any() and (~outside).any() and not (mask & outside).any()
+    T32, W32, live32 = (a.astype(np.float32).astype(np.float64) for a in (T0, W0, live))
+    To32, Wo32 = T32.copy(), W32.copy()
+    _, _, mask32 = O.update_tsdf_dqb(To32, Wo32, live32, node_pos, node_dq, node_w, k, lw, tdist, wmax=7.0, return_mask=True)
+    try:
+        _lib.set_option("k3_skip", 0)
+        for vol_dtype in (torch.float64, torch.float32):
+            T, W = dev(T0, vol_dtype), dev(W0, vol_dtype)
+            ws = kernels.dqb_workspace(res, knn=k, n_nodes=N, level=2)
+            for rebuild in (True, False):                                          # search + store, then the stored neighbourhoods
+                T, W = dev(T0, vol_dtype), dev(W0, vol_dtype)
+                kernels.fuse_volume_dqb(T, W, dev(live, vol_dtype), node_pos, node_dq, node_w, k, lw, tdist, 7.0, workspace=ws,
+                                        rebuild_candidates=rebuild)
+                Tn, Wn = T.cpu().numpy().astype(np.float64), W.cpu().numpy().astype(np.float64)
+                if vol_dtype == torch.float64:
+                    assert np.array_equal((Tn != T0) | (Wn != W0), mask), rebuild
+                    assert np.abs(Wn - Wo).max() <= 1e-12 and np.abs(Tn - To).max() <= 1e-12
+                else:                                                              # float32: one rounding from the oracle on float32 inputs
+                    assert np.array_equal((Tn != T32) | (Wn != W32), mask32), rebuild
+                    assert (np.abs(Wn - Wo32) <= f32_tol(1) * (1 + np.abs(Wo32))).all(), rebuild
+                    assert (np.abs(Tn - To32) <= f32_tol(1) * (1 + np.abs(To32))).all(), rebuild
+        assert mask.any() and (~mask).any()
+    finally:
+        _lib.set_option("k3_skip", None)
+
+
+@pytest.mark.parametrize("res,live_res", [((32, 32, 512), (32, 32, 192)), ((32, 32, 512), (32, 32, 256)), ((32, 32, 512), (32, 32, 320)),
+                                          ((32, 32, 256), (32, 32, 384)), ((32, 32, 256), (24, 40, 256)), ((32, 32, 256), (40, 22, 200))])
+def test_dqb_constant_live_skip_with_a_live_volume_of_another_size(res, live_res):
+    """The constant-live skip with a live volume of another extent than the canonical grid: shorter along z (192 and 256 of 512:
+    canonical bricks beyond the live volume's last 64-cell word along z -- dqb_reach_kernel must call them "not constant", not
+    leave whatever the workspace held), 320 (a control: two words cover the grid), longer along z, and other x / y extents.  The
+    workspace starts filled with 0x02 bytes (a stale "constant within two cells" everywhere).  Same bits as with the skip off, as in
+    test_dqb_constant_live_skip_gives_the_same_bits."""
+    from dynamicfusion_body_amd import _lib
+    N, k, tdist = 150, 4, 4.0
+    live, T0, W0, node_pos, node_w, dqs = _skip_scene(res, N, tdist, "gentle", live_res=live_res)
+    ident = np.array([1.0, 0, 0, 0, 0, 0, 0, 0])
+    try:
+        for a, b in ((0, res[0]), (res[0] // 4, res[0] // 4 * 3)):
+            outs = {}
+            for skip in (1, 0):
+                ws = kernels.dqb_workspace(res, (a, b), knn=k, n_nodes=N, level=2)
+                ws.view(torch.uint8).fill_(2)
+                T, W = T0[a:b].clone(), W0[a:b].clone()
+                _lib.set_option("k3_skip", skip)
+                kernels.fuse_volume_dqb(T, W, live, node_pos, dqs, node_w, k, ident, tdist, 9.0, res=res, x_range=(a, b), workspace=ws,
+                                        rebuild_candidates=True)
+                for _ in range(2):
+                    kernels.fuse_volume_dqb(T, W, live, node_pos, dqs, node_w, k, ident, tdist, 9.0, res=res, x_range=(a, b), workspace=ws,
+                                            rebuild_candidates=False)
+                torch.cuda.synchronize()
+                outs[skip] = (T, W)
+                if skip:
+                    tabs = kernels.dqb_skip_tables(ws, res, live_res, N, x_range=(a, b))
+                    assert tabs["ok"]
+                    share = float(tabs["S"].float().mean())
+            assert torch.equal(outs[1][0], outs[0][0]) and torch.equal(outs[1][1], outs[0][1]), (res, live_res, (a, b), share)
+            assert not (torch.equal(outs[0][0], T0[a:b]) and torch.equal(outs[0][1], W0[a:b]))        # (the calls did something)
+            assert share > 0.05, share
+    finally:
+        _lib.set_option("k3_skip", None)

@@ -362,3 +362,74 @@ def test_soak_300_frames():
         sv.solve_linear(1e-2, 1e-2)
         xs.append(sv.dx.clone())
     assert all(torch.equal(x, xs[0]) for x in xs[1:]) and bool(torch.isfinite(xs[0]).all())
+
+
+class _CountingLib:
+    """A stand-in for WarpSolver.lib that counts the packings of the views' table."""
+
+    def __init__(self, lib):
+        self._lib, self.packs = lib, 0
+
+    def __getattr__(self, name):
+        fn = getattr(self._lib, name)
+        if name not in ("dfh_gn_pack_views", "dfh_gn_pack_views_cells"):
+            return fn
+
+        def counted(*args):
+            self.packs += 1
+            return fn(*args)
+        return counted
+
+
+@pytest.mark.parametrize("n_views", [1, 3, 4])
+def test_views_table_follows_depth_maps_refreshed_in_place(n_views):
+    """The views' table (WarpSolver._views_table: depth pointers, extrinsics and, for float32 maps, the 16 x 16-pixel cells' depth
+    ranges by which the fused build drops views per tile) is cached across a frame's calls.  A caller that refreshes its depth
+    tensors in place (copy_) and keeps its extrinsics must not get the previous frame's cells: frame A all zeros (every cell
+    empty, every view dropped), then frame B copied into the same tensors -- the rigid-mode step and the node iterations give the
+    same bits as a fresh solver fed newly allocated frame-B tensors (the builds cull views per tile from four views on: with one
+    or three a stale table gives the right answer by luck, and only the packing count tells).  And the cache still hits:
+    iterations on untouched tensors pack the table once."""
+    R, N, k = 64, 48, 4
+    K, (H, W), scale, center, tdist, T, Wt = build_canonical(R, "C1")
+    node_pos, node_w = scene.fibonacci_nodes(N, R)
+    ident = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0, 0]), (N, 1))
+    lws = [scene.view_extrinsic(a) for a in (0.0, 40.0, -40.0, 20.0)][:n_views]
+    off = np.array([0.6, -0.4, 0.3]) * scale
+    frame_b = [scene.render_depth(K, lw, H, W, dtype=np.float32, invalid_frac=0.01, seed=5, sphere_offset=off) for lw in lws]
+    dq0 = G.apply_twists(ident, np.random.default_rng(8).normal(scale=[2e-3] * 3 + [0.1] * 3, size=(N, 6)))
+
+    def solver():
+        fs = FrameSolver(K, scale, center, R / 2, knn=k, pcg_iters=10, distributed=False)
+        fs.set_graph(node_pos, ident, node_w)
+        fs.set_canonical(T, Wt, band=2.0)
+        fs.solver.lib = _CountingLib(fs.solver.lib)
+        return fs
+
+    def arg(ds):
+        return (ds, lws) if n_views > 1 else (ds[0], lws[0])
+
+    def frame(fs, ds):
+        sv = fs.solver
+        sv.node_dq.copy_(torch.from_numpy(dq0).cuda())
+        fs.global_iteration(*arg(ds), max_dist=2.0, huber=0.5, lm_rel=0.1, n_iters=2, stride=1)
+        xi = sv.global_xi.clone()
+        fs.gn_iteration(*arg(ds), max_dist=2.0, huber=0.5, n_iters=3)
+        torch.cuda.synchronize()
+        return xi, sv.node_dq.clone(), sv.cost_count.clone()
+
+    fresh = solver()
+    want = frame(fresh, [torch.from_numpy(d).cuda() for d in frame_b])
+    assert int(want[2][1]) > 1000 and int(want[0][7]) > 1000
+    assert fresh.solver.lib.packs == 1                                        # the frame's five iterations: one table
+    fs = solver()
+    ds = [torch.zeros((H, W), dtype=torch.float32, device="cuda") for _ in lws]
+    fs.gn_iteration(*arg(ds), max_dist=2.0, huber=0.5, n_iters=1)             # frame A: nothing to see
+    torch.cuda.synchronize()
+    assert fs.solver.cost()[1] == 0 and fs.solver.lib.packs == 1
+    for d, b in zip(ds, frame_b):
+        d.copy_(torch.from_numpy(b))                                          # frame B, in place; extrinsics unchanged
+    got = frame(fs, ds)
+    for a, b, name in zip(got, want, ("global_xi", "node_dq", "cost / count")):
+        assert torch.equal(a, b), name
+    assert fs.solver.lib.packs == 2

@@ -768,3 +768,91 @@ def test_icp_compute_live_tsdf_recovers_rigid_motion():
     assert abs(M[2, 3] - t_true[2]) < 0.15
     assert M[0, 3] * t_true[0] > 0 and M[1, 3] * t_true[1] > 0 and np.abs(M[:2, 3]).max() < 1.5 * np.abs(t_true[:2]).max()
     assert (Wt > 1).any()                                          # the second view was fused in
+
+
+def _relax_pool(rng):
+    """DQs for dfh_relax_twists: (pool (n, 8), index of every special case by name).  Random unit motions (half stored as -q),
+    rotations a hair either side of pi, rotation vectors at and below 1e-12 with a translation, pure translations, scaled DQs,
+    zero and non-finite DQs, and rotations by exactly pi (w = 0: the relaxed motion is ambiguous)."""
+    def motion(axis, angle, t):
+        axis = np.asarray(axis, dtype=np.float64) / np.linalg.norm(axis)
+        return G.twist_exp_dq(np.concatenate([axis * angle, np.asarray(t, dtype=np.float64)]))
+    rows, names = [], []
+
+    def add(name, dq):
+        rows.append(np.asarray(dq, dtype=np.float64)); names.append(name)
+    add("ten_degrees_as_-q", -motion([0.2, -1.0, 0.4], np.deg2rad(10.0), [0.3, -0.2, 1.1]))
+    for eps in (1e-3, 1e-6, 1e-10):
+        ax, t = rng.normal(size=3), rng.normal(size=3)
+        a = motion(ax, np.pi - eps, t)                                          # w = sin(eps / 2) > 0
+        add("below_pi", a); add("below_pi", -a)
+        b = motion(ax, np.pi + eps, t)                                          # w < 0: the same as pi - eps about -axis
+        add("above_pi", b); add("above_pi", -b)
+    for vn in (1e-12, 3e-13, 1e-15):
+        q = np.array([1.0, vn, -0.5 * vn, 0.25 * vn])
+        t = rng.normal(size=3)
+        dq = np.concatenate([q, 0.5 * G.qmul(G.pure(t), q)])
+        add("tiny_rotation", dq); add("tiny_rotation", -dq); add("tiny_rotation", 1.7 * dq)
+    for t in rng.normal(scale=3.0, size=(3, 3)):
+        dq = np.concatenate([[1.0, 0, 0, 0, 0], 0.5 * t])
+        add("translation", dq); add("translation", -dq)
+    for s in (0.5, 1.03, 1e3, -0.5, -1e3):
+        add("scaled", s * motion(rng.normal(size=3), rng.uniform(0.1, 3.0), rng.normal(size=3)))
+    add("pi", motion([0.0, 0.0, 1.0], np.pi, [0.5, 0.0, -1.0]) * np.array([0.0, 1, 1, 1, 1, 1, 1, 1]))
+    add("pi", np.array([0.0, 0.6, 0.0, -0.8, 0.1, 0.2, 0.3, 0.4]))
+    add("unchanged", np.zeros(8))
+    add("unchanged", np.array([np.nan, 0, 0, 0, 0, 0, 0, 0]))
+    add("unchanged", np.array([0.6, np.inf, 0, 0, 1, 2, 3, 4]))
+    add("unchanged", np.array([-np.inf, 0, 0, 0, 0, 0, 0, 0]))
+    add("unchanged", np.array([1e200, 1e200, 0, 0, 0, 0, 0, 0]))           # (|q|^2 overflows)
+    n_rand = 4099 - len(rows)
+    ax = rng.normal(size=(n_rand, 3)); ax /= np.linalg.norm(ax, axis=1, keepdims=True)
+    ang = rng.uniform(0.0, 0.99 * np.pi, size=n_rand)
+    rnd = G.twist_exp_dq(np.concatenate([ax * ang[:, None], rng.normal(scale=2.0, size=(n_rand, 3))], axis=1))
+    rnd[::2] *= -1.0                                                            # half of them stored as -q
+    pool = np.concatenate([np.stack(rows), rnd])
+    names = np.array(names + ["random"] * n_rand)
+    return pool, names
+
+
+@pytest.mark.parametrize("n", [1, 255, 257, 4099])
+def test_relax_twists_vs_oracle(n):
+    """dfh_relax_twists (solve.relax_twists; the frame loop's per-frame decay) against oracle/gn_np.relax_twists to 1e-12 absolute:
+    a DQ stored as -q relaxes like q (a 10-degree rotation as -q relaxed by 0.8 is 8 degrees, not -80), rotations either side of
+    pi, vanishing rotation vectors, pure translations, scaled DQs; zero / non-finite DQs come back bit for bit, a rotation by
+    exactly pi finite and unit; factor 1 launches nothing (node_dq bit for bit); N = 0 is a no-op, a factor outside [0, 1] an
+    error."""
+    rng = np.random.default_rng(77)
+    pool, names = _relax_pool(rng)
+    assert int((names != "random").sum()) < 255                                # every special case is in the 255 and up; N = 1: the -q case
+    dq0, nm = pool[:n], names[:n]
+    for f in (0.0, 0.3, 0.8, 1.0):
+        d = torch.from_numpy(dq0).cuda()
+        solve.relax_twists(d, f)
+        out = d.cpu().numpy()
+        if f == 1.0:
+            assert np.array_equal(out.view(np.int64), dq0.view(np.int64))
+            continue
+        want = G.relax_twists(dq0, f)
+        same = nm == "unchanged"
+        assert np.array_equal(out[same].view(np.int64), dq0[same].view(np.int64))
+        amb = nm == "pi"
+        if amb.any():
+            q, qe = out[amb, :4], out[amb, 4:]
+            assert np.isfinite(out[amb]).all()
+            assert np.abs(np.sum(q * q, axis=1) - 1.0).max() <= 1e-12 and np.abs(np.sum(q * qe, axis=1)).max() <= 1e-12
+        cmp = ~(same | amb)
+        err = np.abs(out[cmp] - want[cmp]).max(axis=1)
+        worst = int(np.argmax(err))
+        assert err[worst] <= 1e-12, (f, nm[cmp][worst], err[worst], dq0[cmp][worst], out[cmp][worst], want[cmp][worst])
+    if n == 1:                                                                  # the worked example: 10 degrees -> 8
+        d = torch.from_numpy(dq0).cuda()
+        solve.relax_twists(d, 0.8)
+        q = d.cpu().numpy()[0]
+        assert abs(np.rad2deg(2.0 * np.arctan2(np.linalg.norm(q[1:4]), abs(q[0]))) - 8.0) <= 1e-9
+        assert q[0] > 0.0
+        solve.relax_twists(torch.empty((0, 8), dtype=torch.float64, device="cuda"), 0.5)
+        for bad in (-0.1, 1.5, float("nan")):
+            with pytest.raises(ValueError):
+                solve.relax_twists(d, bad)
+        torch.cuda.synchronize()
