@@ -86,8 +86,9 @@ __global__ __launch_bounds__(256) void fuse_volume_rigid_kernel(VolT *__restrict
 // K2 fast path for fp32 volumes.  A rigid dual quaternion acts on a point as an affine map
 // q = M i + t (M = |r|^2 R(r), t = 2 vec(d r*), folded on the host in fp64), so the per-voxel DQ
 // chain collapses to three FMAs per voxel; the trilinear blend uses FMA lerps.  The two decisions
-// (inside the live volume, s > -tdist) are guarded: within 1e-9 of a boundary the voxel is
-// re-evaluated with the exact chain, so the masks are those of the fp64 path.
+// (inside the live volume, s > -tdist) and the sampler's cell (its value jumps across y / z cell
+// boundaries) are guarded: within 1e-9 of a boundary the voxel is re-evaluated with the exact
+// chain, so the masks and the sampled cells are those of the fp64 path.
 struct RigidFastParams {
     double M[9], t[3];
 };
@@ -149,6 +150,11 @@ __global__ __launch_bounds__(256) void fuse_volume_rigid_fast_kernel(float *__re
         (void)edge;
         double sv = 0.0;
         if (ok) {
+            // cell boundaries, as in K3's dqb_fast_warp: the sampler's y / z fractions blend along the other axis, so the sample
+            // jumps where a coordinate crosses an integer, and this affine map need not round to the side the DQ chain rounds to
+            // (a quarter turn with an integer translation puts every sample within an ulp of a lattice point)
+            const double fx = qx - floor(qx), fy = qy - floor(qy), fz = qz - floor(qz);
+            redo = redo | !(fmin(fmin(fmin(fx, fy), fz), fmin(fmin(1.0 - fx, 1.0 - fy), 1.0 - fz)) > 1e-9);
             sv = sample_fast(live, p.LY, p.LZ, qx, qy, qz);
             const double margin = sv + p.tdist;
             ok = margin > 0.0;

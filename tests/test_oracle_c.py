@@ -1,6 +1,8 @@
-"""CPU: the C restatement (oracle/oracle_c.c) bit for bit against the numpy oracle and against
-the reference's own outputs (golden g2, g6)."""
+"""CPU: the C restatement (oracle/oracle_c.c) against the numpy oracle and against
+the reference's own outputs (golden g2, g3, g4, g6): A1 (fuse_depths) and A3 (rigid TSDF fusion) bit for bit,
+A4 (DQB TSDF fusion) with identical masks and values within 1e-12 (libm exp() against numpy's)."""
 import numpy as np
+import pytest
 
 from oracle import oracle_c as C
 from oracle import oracle_np as O
@@ -48,3 +50,181 @@ def test_c_oracle_matches_numpy_oracle_and_g6(golden):
     O.fuse_depths(dm, lw, K2, np.linalg.inv(K2), T2, W2, 0.3, tsdf_res=12, scale=0.12, center=scene.SPHERE_C, wmax=2.0)
     assert np.array_equal(T1, T2) and np.array_equal(W1, W2) and (W2 > 0).any()
     assert C.threads() >= 1
+
+
+# ------------------------------------------------------------------------------------------------ A3 / A4: TSDF -> TSDF fusion
+def _sphere(shape, centre, radius, tdist):
+    g = np.stack(np.meshgrid(*[np.arange(s, dtype=np.float64) for s in shape], indexing="ij"), axis=-1)
+    return np.clip(np.linalg.norm(g - centre, axis=-1) - radius, -1.5 * tdist, 1.5 * tdist)
+
+
+def _dq(rng, rot, trans, scale=1.0):
+    ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
+    ang = rng.normal() * rot
+    q = np.append(np.cos(ang / 2), np.sin(ang / 2) * ax)
+    t = rng.normal(size=3) * trans
+    return np.append(q, 0.5 * O.quaternion_multiply(np.array([0.0, t[0], t[1], t[2]]), q)) * scale
+
+
+def test_c_rigid_matches_reference_golden_g3(golden):
+    """All four live volumes of g3 (R = 20, non-unit `_lw`, wmax = 5): the reference's own outputs, bit for bit, and the numpy
+    oracle's after every call."""
+    g = golden("g3_rigid")
+    T, W = g["T0"].copy(), g["W0"].copy()
+    Tn, Wn = T.copy(), W.copy()
+    for r in range(4):
+        n, m = C.update_tsdf_rigid(T, W, g["lives"][r], g["lw"], float(g["tdist"]), wmax=float(g["wmax"]), return_mask=True, n_threads=3)
+        _, _, mn = O.update_tsdf_rigid(Tn, Wn, g["lives"][r], g["lw"], float(g["tdist"]), wmax=float(g["wmax"]), return_mask=True)
+        assert np.array_equal(m, mn) and n == int(mn.sum()) and mn.any() and (~mn).any()
+        assert np.array_equal(T, Tn) and np.array_equal(W, Wn), r
+        if r == 0:
+            assert np.array_equal(W, g["W_after1"]) and np.array_equal(T, g["T_after1"])
+    assert np.array_equal(W, g["W_after4"]) and np.array_equal(T, g["T_after4"])
+
+
+RIGID_CASES = [  # (grid, live extent, live dtype, lw kind, slabs)
+    ((11, 9, 13), (11, 9, 13), np.float64, "rigid", None),
+    ((12, 10, 16), (12, 10, 16), np.float32, "scaled", ((0, 5), (5, 5), (5, 12))),
+    ((10, 12, 14), (14, 9, 18), np.float64, "scaled", ((0, 3), (3, 10))),
+    ((16, 8, 20), (9, 8, 12), np.float32, "rigid", None),
+    ((12, 12, 12), (12, 12, 12), np.float64, "identity", ((0, 7), (7, 12))),
+    ((9, 11, 16), (9, 11, 16), np.float32, "quarter", None),
+]
+
+
+@pytest.mark.parametrize("res,live_res,live_dtype,lw_kind,slabs", RIGID_CASES)
+def test_c_rigid_matches_numpy_oracle(res, live_res, live_dtype, lw_kind, slabs):
+    """A3 against oracle_np.update_tsdf_rigid, bit for bit: ragged grids, a live volume larger and smaller than the grid, float32
+    live read in place, non-unit `_lw` (scale 0.97), the identity (samples on voxel centres; live values at exactly -tdist must not
+    update), a quarter turn about z with an integer translation (near-lattice ties); slabs swept separately, once through whole
+    volumes (x_range) and once through arrays that hold the slab's planes only (x_base)."""
+    rng = np.random.default_rng(sum(res) * 5 + sum(live_res))
+    tdist = 1.5
+    live = _sphere(live_res, np.array(res) / 2.0 - 0.3, min(res) / 3.0, tdist) + 0.01 * rng.normal(size=live_res)
+    if lw_kind == "identity":
+        live[:, :, ::3] = -tdist
+    live = live.astype(live_dtype)
+    lw = {"rigid": _dq(rng, 0.1, 0.6), "scaled": _dq(rng, 0.2, 0.8, 0.97), "identity": np.array([1.0, 0, 0, 0, 0, 0, 0, 0]),
+          "quarter": np.concatenate([[np.sqrt(0.5), 0, 0, np.sqrt(0.5)], 0.5 * O.quaternion_multiply(np.array([0.0, 8.0, -1.0, 2.0]),
+                                                                                                    [np.sqrt(0.5), 0, 0, np.sqrt(0.5)])])}[lw_kind]
+    T0 = _sphere(res, np.array(res) / 2.0, min(res) / 3.2, tdist)
+    W0 = (rng.random(res) < 0.6) * rng.integers(1, 6, size=res).astype(np.float64)
+    Tn, Wn = T0.copy(), W0.copy()
+    _, _, mn = O.update_tsdf_rigid(Tn, Wn, live, lw, tdist, wmax=4.0, return_mask=True)
+    assert mn.any() and (~mn).any()
+    T, W = T0.copy(), W0.copy()
+    n, m = C.update_tsdf_rigid(T, W, live, lw, tdist, wmax=4.0, return_mask=True, n_threads=4)
+    assert n == int(mn.sum()) and np.array_equal(m, mn)
+    assert np.array_equal(T, Tn) and np.array_equal(W, Wn)
+    if lw_kind == "identity":
+        assert not mn[:, :, ::3].any()
+    for a, b in slabs or ():
+        Ts, Ws = T0.copy(), W0.copy()
+        C.update_tsdf_rigid(Ts, Ws, live, lw, tdist, wmax=4.0, x_range=(a, b))
+        assert np.array_equal(Ts[a:b], Tn[a:b]) and np.array_equal(Ws[a:b], Wn[a:b])
+        assert np.array_equal(np.delete(Ts, np.s_[a:b], 0), np.delete(T0, np.s_[a:b], 0))
+        Ts, Ws = T0[a:b].copy(), W0[a:b].copy()
+        C.update_tsdf_rigid(Ts, Ws, live, lw, tdist, wmax=4.0, x_base=a)
+        assert np.array_equal(Ts, Tn[a:b]) and np.array_equal(Ws, Wn[a:b])
+
+
+def test_c_dqb_matches_reference_golden_g4(golden):
+    """All three live volumes of g4 (R = 14, N = 24, k = 4, non-unit `_lw`, wmax = 9): the reference's outputs and the numpy
+    oracle's after every call -- masks identical, values within 1e-12."""
+    g = golden("g4_dqb")
+    k = int(g["knn"])
+    args = (g["node_pos"], g["node_dq"], g["node_w"], k, g["lw"], float(g["tdist"]))
+    T, W = g["T0"].copy(), g["W0"].copy()
+    Tn, Wn = T.copy(), W.copy()
+    for r in range(3):
+        W_before = W.copy()
+        n, m = C.update_tsdf_dqb(T, W, g["lives"][r], *args, wmax=float(g["wmax"]), return_mask=True, n_threads=3)
+        _, _, mn = O.update_tsdf_dqb(Tn, Wn, g["lives"][r], *args, wmax=float(g["wmax"]), return_mask=True)
+        assert np.array_equal(m, mn) and n == int(mn.sum()) and mn.any() and (~mn).any()
+        assert np.abs(T - Tn).max() <= 1e-12 and np.abs(W - Wn).max() <= 1e-12
+        if r == 0:
+            assert np.array_equal(W != W_before, g["W_after1"] != g["W0"])
+            assert np.abs(W - g["W_after1"]).max() <= 1e-12 and np.abs(T - g["T_after1"]).max() <= 1e-12
+    assert np.abs(W - g["W_after3"]).max() <= 1e-12 and np.abs(T - g["T_after3"]).max() <= 1e-12
+
+
+DQB_CASES = [  # (grid, live extent, live dtype, N, knn, field, slabs)
+    ((10, 9, 13), (10, 9, 13), np.float64, 30, 4, "random", ((0, 3), (3, 10))),
+    ((8, 8, 16), (8, 8, 16), np.float32, 5, 1, "random", None),
+    ((12, 10, 11), (15, 8, 14), np.float64, 40, 3, "random", None),
+    ((9, 12, 10), (7, 12, 13), np.float32, 60, 8, "random", ((0, 4), (4, 4), (4, 9))),
+    ((8, 8, 16), (8, 8, 16), np.float64, 6, 4, "zero", None),
+    ((12, 28, 33), (12, 28, 33), np.float32, 420, 8, "cluster", None),
+    ((10, 10, 10), (10, 10, 10), np.float64, 20, 4, "identity", None),
+]
+
+
+@pytest.mark.parametrize("res,live_res,live_dtype,N,k,field,slabs", DQB_CASES)
+def test_c_dqb_matches_numpy_oracle(res, live_res, live_dtype, N, k, field, slabs):
+    """A4 against oracle_np.update_tsdf_dqb: identical masks, values within 1e-12.  knn 1, 3, 4 and 8; ragged grids; a live
+    volume larger and smaller than the grid; float32 live read in place; non-unit `_lw`; all-zero node DQs (the zero blend ->
+    identity); 320 nodes clustered round one brick (more than the device's 256 candidates per brick); the identity field (every
+    sample on a lattice point); W0 with zeros (first touch: wt = wi); slabs, whole volumes and slab-only arrays."""
+    rng = np.random.default_rng(N * 13 + k + sum(live_res))
+    tdist = 2.0
+    node_pos = rng.uniform(0, np.array(res) - 1, size=(N, 3))
+    if field == "cluster":
+        node_pos[:320] = np.array(res) / 2.0 + rng.normal(size=(320, 3)) * 1.5
+    node_w = rng.uniform(2.0, 5.0, size=N)
+    if field == "zero":
+        node_dq = np.zeros((N, 8))
+    elif field == "identity":
+        node_dq = np.tile([1.0, 0, 0, 0, 0, 0, 0, 0], (N, 1))
+        node_pos = np.round(node_pos)                           # (integer node positions: knn ties between equidistant nodes)
+    else:
+        node_dq = np.array([_dq(rng, 0.08, 0.4, 1 + 0.02 * rng.normal()) for _ in range(N)])
+    lw = np.array([1.0, 0, 0, 0, 0, 0, 0, 0]) if field == "identity" else _dq(rng, 0.05, 0.3, 0.99)
+    T0 = _sphere(res, np.array(res) / 2.0, min(res) / 3.0, tdist)
+    W0 = (rng.random(res) < 0.6) * rng.uniform(0.5, 3.0, size=res)
+    live = (_sphere(live_res, np.array(res) / 2.0 + 0.4, min(res) / 3.1, tdist) + 0.01 * rng.normal(size=live_res)).astype(live_dtype)
+    args = (node_pos, node_dq, node_w, k, lw, tdist)
+    Tn, Wn = T0.copy(), W0.copy()
+    _, _, mn = O.update_tsdf_dqb(Tn, Wn, live, *args, wmax=7.0, return_mask=True)
+    assert mn.any() and (~mn).any() and (mn & (W0 == 0)).any()
+    T, W = T0.copy(), W0.copy()
+    n, m = C.update_tsdf_dqb(T, W, live, *args, wmax=7.0, return_mask=True, n_threads=4)
+    assert n == int(mn.sum()) and np.array_equal(m, mn)
+    assert np.abs(T - Tn).max() <= 1e-12 and np.abs(W - Wn).max() <= 1e-12
+    for a, b in slabs or ():
+        Ts, Ws = T0.copy(), W0.copy()
+        C.update_tsdf_dqb(Ts, Ws, live, *args, wmax=7.0, x_range=(a, b))
+        assert np.array_equal(Ts[a:b], T[a:b]) and np.array_equal(Ws[a:b], W[a:b])
+        assert np.array_equal(np.delete(Ws, np.s_[a:b], 0), np.delete(W0, np.s_[a:b], 0))
+        Ts, Ws = T0[a:b].copy(), W0[a:b].copy()
+        C.update_tsdf_dqb(Ts, Ws, live, *args, wmax=7.0, x_base=a)
+        assert np.array_equal(Ts, T[a:b]) and np.array_equal(Ws, W[a:b])
+
+
+@pytest.mark.parametrize("kind", ["rigid", "dqb"])
+def test_c_voxel_list_form_matches_the_volume_form(kind):
+    """Form (b) -- a list of flat voxel indices, per-voxel T / w in, T / w / mask out -- gives exactly what form (a) gives at
+    those voxels, in any order and with repeats."""
+    rng = np.random.default_rng(41)
+    res, live_res, tdist, N, k = (14, 11, 18), (16, 10, 18), 2.0, 50, 4
+    node_pos = rng.uniform(0, np.array(res) - 1, size=(N, 3))
+    node_dq = np.array([_dq(rng, 0.08, 0.4) for _ in range(N)])
+    node_w = rng.uniform(2.0, 5.0, size=N)
+    lw = _dq(rng, 0.05, 0.3, 0.98)
+    T0 = _sphere(res, np.array(res) / 2.0, 4.0, tdist)
+    W0 = (rng.random(res) < 0.6) * rng.uniform(0.5, 3.0, size=res)
+    live = _sphere(live_res, np.array(res) / 2.0 + 0.4, 3.9, tdist).astype(np.float32)
+    T, W = T0.copy(), W0.copy()
+    if kind == "rigid":
+        _, m = C.update_tsdf_rigid(T, W, live, lw, tdist, wmax=6.0, return_mask=True)
+    else:
+        _, m = C.update_tsdf_dqb(T, W, live, node_pos, node_dq, node_w, k, lw, tdist, wmax=6.0, return_mask=True)
+    idx = np.concatenate([rng.permutation(T0.size)[:700], [0, T0.size - 1, 5, 5]])
+    Ti, Wi = T0.reshape(-1)[idx], W0.reshape(-1)[idx]
+    if kind == "rigid":
+        To, Wo, mo = C.update_tsdf_rigid_at(idx, res, Ti, Wi, live, lw, tdist, wmax=6.0, n_threads=3)
+    else:
+        To, Wo, mo = C.update_tsdf_dqb_at(idx, res, Ti, Wi, live, node_pos, node_dq, node_w, k, lw, tdist, wmax=6.0, n_threads=3)
+    assert np.array_equal(To, T.reshape(-1)[idx]) and np.array_equal(Wo, W.reshape(-1)[idx])
+    assert np.array_equal(mo, m.reshape(-1)[idx]) and mo.any() and (~mo).any()
+    with pytest.raises(ValueError):
+        C.update_tsdf_rigid_at([T0.size], res, [0.0], [0.0], live, lw, tdist)
