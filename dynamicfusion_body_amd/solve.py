@@ -654,6 +654,8 @@ class WarpSolver:
         reg_here = (not self.distributed) or _dist.world()[0] == 0
         nn = 0 if (self.node_nbr is None or rw == 0.0 or not reg_here) else self.node_nbr.data_ptr()
         if _lib.opt_on("py_gn_atomic"):          # the atomics-based build (no plan needed), kept for A/B comparison
+            if huber > 0.0:
+                raise ValueError("the atomic build (py_gn_atomic) has no Huber weights")
             _lib.check(self.lib.dfh_gn_build(self.spos.data_ptr(), self.snrm.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(),
                                              self.corr.data_ptr(), self.valid.data_ptr(), self.S, self.knn,
                                              self.node_dq.data_ptr(), self.node_pos.data_ptr(), self.node_w.data_ptr(), nn, self.N,

@@ -438,7 +438,8 @@ int dfh_gn_iteration_views(const double *sample_pos, const double *sample_nrm, c
                      double step, int n_iters, const int *blk_upper, int n_upper, void *stream);
 /* A frame's whole solve behind one call: n_global rigid-mode steps (a build + dfh_gn_global_step(global_lm) each; global_scratch as
  * there, global_xi_out may be NULL), then the n_iters node iterations of dfh_gn_iteration_views -- the same launches in the same
- * order as the separate calls, hence the same bits.  pipeline.SlabFrame.step's solve on one GPU. */
+ * order as the separate calls, hence the same bits.  Reached through pipeline.FrameSolver.gn_iteration(n_global > 0) on one GPU;
+ * SlabFrame.step does not use it (its rigid-mode steps are dfh_gn_global_sampled_views, its node iterations dfh_gn_iteration_views). */
 int dfh_gn_frame_solve_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
                      double *corr_out, unsigned char *valid_out, int n_samples, int knn, double *node_dq,
                      const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
