@@ -13,13 +13,44 @@ LIB_PATH = os.environ.get("DFH_LIB_PATH") or os.path.join(_PKG, "libdfusion_hip.
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dfusion_hip.h")
 
 F32, F64 = 0, 1
-ABI_VERSION = 6
+ABI_VERSION = 7
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
 _vp = ctypes.c_void_p
 _int = ctypes.c_int
 _dbl = ctypes.c_double
+
+
+class Problem(ctypes.Structure):
+    """dfh_gn_problem (include/dfusion_hip.h): what the solver owns."""
+    _fields_ = [("sample_pos", _vp), ("sample_nrm", _vp), ("nbr", _vp), ("weights", _vp), ("corr", _vp), ("valid", _vp),
+                ("n_samples", _int), ("knn", _int),
+                ("node_dq", _vp), ("node_pos", _vp), ("node_w", _vp), ("node_nbr", _vp), ("n_nodes", _int),
+                ("lw_dq", _dbl * 8), ("rw", _dbl), ("huber_delta", _dbl),
+                ("row_ptr", _vp), ("col", _vp), ("n_blocks", _int), ("vals", _vp), ("rhs", _vp), ("cost_count", _vp),
+                ("blk_upper", _vp), ("n_upper", _int),
+                ("run_id", _vp), ("n_rows", _int), ("partial", _vp), ("blk_ptr", _vp), ("blk_ent", _vp), ("node_ptr", _vp),
+                ("node_ent", _vp),
+                ("partial_reg", _vp), ("rblk_ptr", _vp), ("rblk_ent", _vp), ("rnode_ptr", _vp), ("rnode_ent", _vp)]
+
+
+class Frame(ctypes.Structure):
+    """dfh_gn_frame: the live frame the data term is associated against (always a packed views table)."""
+    _fields_ = [("views", _vp), ("n_views", _int), ("depth_dtype", _int), ("H", _int), ("W", _int),
+                ("K", _dbl * 9), ("Kinv", _dbl * 9), ("scale", _dbl), ("center", _dbl * 3), ("half", _dbl), ("max_dist", _dbl)]
+
+
+class SolveParams(ctypes.Structure):
+    """dfh_gn_solve_params: one dfh_gn_solve call's schedule."""
+    _fields_ = [("pcg_iters", _int), ("lm_abs", _dbl), ("lm_rel", _dbl), ("x_out", _vp), ("pcg_workspace", _vp),
+                ("pcg_workspace_bytes", ctypes.c_size_t), ("step", _dbl), ("n_iters", _int), ("n_global", _int),
+                ("global_lm", _dbl), ("global_xi_out", _vp), ("global_scratch", _vp), ("global_scratch_bytes", ctypes.c_size_t)]
+
+
+_problem_p = ctypes.POINTER(Problem)
+_frame_p = ctypes.POINTER(Frame)
+STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -59,40 +90,13 @@ _SIGNATURES = {
     "dfh_dqb_skip_layout": (_int, [_c_int_p, _int, _int, _c_int_p, _int, _int, ctypes.POINTER(ctypes.c_size_t)]),
     "dfh_dqb_build_candidates": (_int, [_c_int_p, _int, _int, _vp, _int, _int, _vp, ctypes.c_size_t, _vp]),
     "dfh_sample_knn_bricks": (_int, [_vp, _int, _vp, _vp, _int, _int, _c_int_p, _int, _int, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
-    "dfh_gn_associate": (_int, [_vp, _vp, _vp, _int, _int, _vp, _c_double_p, _vp, _int, _int, _int, _c_double_p,
-                                _c_double_p, _c_double_p, _dbl, _c_double_p, _dbl, _dbl, _vp, _vp, _vp]),
-    "dfh_gn_build": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _c_double_p, _dbl,
-                            _vp, _vp, _int, _vp, _vp, _vp, _vp]),
     "dfh_permute_samples": (_int, [_vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dfh_gn_partial_doubles": (ctypes.c_size_t, [_int]),
-    "dfh_gn_build_planned": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _c_double_p, _dbl,
-                                    _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _dbl, _vp]),
-    "dfh_gn_build_planned_assoc": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _c_double_p, _dbl,
-                                          _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                          _dbl, _vp, _int, _int, _c_double_p, _c_double_p, _c_double_p, _dbl, _c_double_p, _dbl, _dbl, _vp]),
-    "dfh_gn_iteration": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _c_double_p, _dbl,
-                                _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                _dbl, _vp, _int, _int, _c_double_p, _c_double_p, _c_double_p, _dbl, _c_double_p, _dbl, _dbl,
-                                _int, _dbl, _dbl, _vp, _vp, ctypes.c_size_t, _dbl, _vp]),
-    "dfh_gn_views_bytes": (ctypes.c_size_t, [_int]),
-    "dfh_gn_pack_views": (_int, [_vp, _int, ctypes.POINTER(ctypes.c_void_p), _c_double_p, _vp]),
-    "dfh_gn_views_bytes_cells": (ctypes.c_size_t, [_int, _int, _int]),
-    "dfh_gn_pack_views_cells": (_int, [_vp, _int, ctypes.POINTER(ctypes.c_void_p), _int, _int, _c_double_p, _vp]),
-    "dfh_gn_associate_views": (_int, [_vp, _vp, _vp, _int, _int, _vp, _c_double_p, _vp, _int, _int, _int, _int, _c_double_p,
-                                      _c_double_p, _dbl, _c_double_p, _dbl, _dbl, _vp, _vp, _vp]),
-    "dfh_gn_build_planned_assoc_views": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _c_double_p, _dbl,
-                                                _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                                _dbl, _vp, _int, _int, _int, _c_double_p, _c_double_p, _dbl, _c_double_p, _dbl, _dbl, _vp, _int, _vp]),
-    "dfh_gn_iteration_views": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _c_double_p, _dbl,
-                                      _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      _dbl, _vp, _int, _int, _int, _c_double_p, _c_double_p, _dbl, _c_double_p, _dbl, _dbl,
-                                      _int, _dbl, _dbl, _vp, _vp, ctypes.c_size_t, _dbl, _int, _vp, _int, _vp]),
-    "dfh_gn_frame_solve_views": (_int, [_vp, _vp, _vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _vp, _int, _c_double_p, _dbl,
-                                      _vp, _vp, _int, _vp, _vp, _vp, _vp, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
-                                      _dbl, _vp, _int, _int, _int, _c_double_p, _c_double_p, _dbl, _c_double_p, _dbl, _dbl,
-                                      _int, _dbl, _dbl, _vp, _vp, ctypes.c_size_t, _dbl, _int, _vp, _int,
-                                      _int, _dbl, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dfh_gn_views_bytes": (ctypes.c_size_t, [_int, _int, _int, _int]),
+    "dfh_gn_pack_views": (_int, [_vp, _int, ctypes.POINTER(ctypes.c_void_p), _int, _int, _int, _c_double_p, _vp]),
+    "dfh_gn_associate": (_int, [_problem_p, _frame_p, _vp]),
+    "dfh_gn_build": (_int, [_problem_p, _frame_p, _vp]),
+    "dfh_gn_solve": (_int, [_problem_p, _frame_p, ctypes.POINTER(SolveParams), _vp]),
     "dfh_gn_pack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "dfh_gn_unpack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "dfh_gn_sort_workspace_bytes": (ctypes.c_size_t, [_int]),
@@ -112,8 +116,7 @@ _SIGNATURES = {
     "dfh_apply_twist": (_int, [_vp, _vp, _int, _dbl, _vp]),
     "dfh_relax_twists": (_int, [_vp, _int, _dbl, _vp]),
     "dfh_gn_global_sampled_bytes": (ctypes.c_size_t, [_int, _int]),
-    "dfh_gn_global_sampled_views": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _int, _c_double_p, _dbl, _vp, _int, _int, _int, _int, _c_double_p,
-                                           _c_double_p, _dbl, _c_double_p, _dbl, _dbl, _int, _dbl, _int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dfh_gn_global_sampled": (_int, [_problem_p, _frame_p, _int, _dbl, _int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dfh_gn_global_apply": (_int, [_vp, _dbl, _int, _vp, _vp, _vp]),
     "dfh_gn_global_step_bytes": (ctypes.c_size_t, []),
     "dfh_gn_global_step": (_int, [_vp, _int, _vp, _int, _dbl, _vp, _vp, _vp, ctypes.c_size_t, _vp]),

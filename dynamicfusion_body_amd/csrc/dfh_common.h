@@ -32,7 +32,7 @@ struct Vec3 { double v[3]; };
 struct DQ { double q[8]; };
 
 constexpr int kWave = 64;             // CDNA wavefront
-// Samples per tile of the planned normal-equation build (dfh_gn_plan_* / dfh_gn_build_planned*): one workgroup of kGnTile
+// Samples per tile of the planned normal-equation build (dfh_gn_plan_* / dfh_gn_build, dfh_gn_solve): one workgroup of kGnTile
 // threads per tile, a scratch row never spans two tiles.  128 (round 3; 256 before): a tile's life is a chain of dependent
 // phases (association 4.6 us, Jacobian rows 2.9, run bookkeeping 1.2, Gram 3.7-10 by the longest run), the launch lasts two
 // tile lives whatever the occupancy, so tiles are made shorter and more numerous (25.6 KB of LDS each: five per CU).

@@ -1,5 +1,5 @@
 // Per-frame bookkeeping of the warp-field solve on the device: samples sorted by node tuple, and the static plan of
-// dfh_gn_build_planned (rows = runs of equal tuples inside kGnTile-sample tiles; per 6x6 block and per node the list of
+// the planned dfh_gn_build (rows = runs of equal tuples inside kGnTile-sample tiles; per 6x6 block and per node the list of
 // (row, slot) entries that contribute to it).  The host used to assemble all this from ~35 torch launches per frame
 // (pack, sort, cumsum, searchsorted, ...): host-bound at ~0.6 ms.  Here it is a handful of launches behind three C
 // entry points; the two key sorts are rocPRIM's device radix sort (stable, so every list comes out in ascending entry

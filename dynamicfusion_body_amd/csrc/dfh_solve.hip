@@ -525,8 +525,6 @@ __global__ __launch_bounds__(256) void permute_samples_kernel(const long *__rest
 // ------------------------------------------------------------------------------- association
 struct AssocParams {
     Mat3 K, Kinv;
-    Mat34 lw_cam;
-    Mat3 Rinv;            // inverse of lw_cam's 3x3 part
     DQ lw;
     double scale, inv_scale, cx, cy, cz, half, max_dist;
     int H, W, k;
@@ -558,18 +556,17 @@ struct AssocView {
     double lw_cam[12];
     double Rinv[9];
     const void *depth;
-    const float *cells;      // per 16 x 16-pixel cell {smallest, largest valid z = -depth} (dfh_gn_pack_views_cells); null: none
+    const float *cells;      // per 16 x 16-pixel cell {smallest, largest valid z = -depth} (float32 maps); null: none
     double cull_ok;          // 1: this view's extrinsic is a rigid motion (the depth-interval test below is exact for it)
 };                           // 192 bytes
 static_assert(sizeof(AssocView) == 192, "AssocView is a 192-byte record");
 constexpr int kCellPx = 16;
 
 // Projective association of one warped sample xp (index space) against ONE view: project with the reference's primitives,
-// take the nearest depth pixel, back-project.  Returns validity (before the distance gate); c = correspondence in index
-// space, d2 = its squared distance from xp.
-// The two halves of it: up to the pixel (no memory access), and from the pixel's depth on.  associate_views runs the first
-// half for several views, asks for their depth values together and only then goes on: one memory round trip per group of
-// views instead of one per view.
+// take the nearest depth pixel, back-project -- in two halves: up to the pixel (no memory access), and from the pixel's depth
+// on (validity before the distance gate; c = correspondence in index space, d2 = its squared distance from xp).
+// associate_views runs the first half for several views, asks for their depth values together and only then goes on: one
+// memory round trip per group of views instead of one per view.
 __device__ __forceinline__ bool associate_project(const AssocParams &p, const double *lw, const D3 &xp, double &u, double &v) {
     // index -> world -> camera -> pixel (fusion_dm.py:191-195)
     const double wx = p.scale * (xp.x - p.half) + p.cx, wy = p.scale * (xp.y - p.half) + p.cy, wz = p.scale * (xp.z - p.half) + p.cz;
@@ -606,30 +603,6 @@ __device__ __forceinline__ bool associate_backproject(const AssocParams &p, cons
     const double dx = c0 - xp.x, dy = c1 - xp.y, dz = c2 - xp.z;
     d2 = dx * dx + dy * dy + dz * dz;
     return z > 0.0;
-}
-
-template <typename DepthT>
-__device__ __forceinline__ bool associate_view(const AssocParams &p, const double *lw, const double *Rinv, const DepthT *__restrict__ depth,
-                                               const D3 &xp, double &c0, double &c1, double &c2, double &d2) {
-    double u, v;
-    bool ok = associate_project(p, lw, xp, u, v);
-    c0 = 0.0; c1 = 0.0; c2 = 0.0; d2 = 0.0;
-    if (ok) {
-        const int ui = (int)rint(u), vi = (int)rint(v);
-        const double z = -1.0 * (double)depth[(size_t)vi * p.W + ui];                  // :196
-        ok = associate_backproject(p, lw, Rinv, z, u, v, xp, c0, c1, c2, d2);
-    }
-    return ok;
-}
-
-// One view (the parameters inside p): validity includes the distance gate; c = 0 when invalid.
-template <typename DepthT>
-__device__ __forceinline__ bool associate_point(const AssocParams &p, const DepthT *__restrict__ depth, const D3 &xp, double (&c)[3]) {
-    double c0, c1, c2, d2;
-    bool ok = associate_view<DepthT>(p, p.lw_cam.m, p.Rinv.m, depth, xp, c0, c1, c2, d2);
-    if (ok && p.max_dist > 0.0) ok = d2 <= p.max_dist * p.max_dist;
-    c[0] = ok ? c0 : 0.0; c[1] = ok ? c1 : 0.0; c[2] = ok ? c2 : 0.0;
-    return ok;
 }
 
 // Several views (BASELINE config 5: the live frame is eight depth maps): every view is tried in turn, the sample keeps the
@@ -685,7 +658,7 @@ __device__ __forceinline__ bool associate_views(const AssocParams &p, const Asso
 // x' has camera depth l2(x'), and |c - x'| (index units) = |c_cam - l| / scale >= |z - l2| / scale.  With B in front of the
 // camera its image lies inside the bounding rectangle of its eight projected corners and l2 over B inside the corners' range
 // [l2min, l2max] (affine).  The view is dropped when the rectangle misses [0, W-1) x [0, H-1), or the pixels it can round to
-// hold no valid depth, or their valid depths [zmin, zmax] (a table of 16 x 16-pixel cells, dfh_gn_pack_views_cells) stay
+// hold no valid depth, or their valid depths [zmin, zmax] (a table of 16 x 16-pixel cells, dfh_gn_pack_views) stay
 // further than max_dist from [l2min, l2max].  Thread t of the tile takes corner t & 7 of view t >> 3 (n_views <= 16).
 // All kTile threads call this; box = {xmin, xmax, ymin, ymax, zmin, zmax} of the tile's warped samples (an empty tile: min > max).
 __device__ __forceinline__ unsigned tile_view_mask(const AssocParams &p, const AssocView *__restrict__ views, int n_views, const double (&box)[6],
@@ -756,7 +729,7 @@ __device__ __forceinline__ unsigned tile_view_mask(const AssocParams &p, const A
 template <typename DepthT>
 __global__ __launch_bounds__(256) void associate_kernel(const double *__restrict__ spos, const int *__restrict__ nbr,
                                                          const double *__restrict__ wts, int S,
-                                                         const double *__restrict__ node_dq, const DepthT *__restrict__ depth,
+                                                         const double *__restrict__ node_dq,
                                                          const AssocParams p, double *__restrict__ corr,
                                                          unsigned char *__restrict__ valid, const AssocView *__restrict__ views, int n_views) {
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -774,7 +747,7 @@ __global__ __launch_bounds__(256) void associate_kernel(const double *__restrict
     const D3 x1 = dqb_warp_exact(b, round_f32(px), round_f32(py), round_f32(pz));
     const D3 xp = dqb_warp_exact(p.lw.q, round_f32(x1.x), round_f32(x1.y), round_f32(x1.z));
     double c[3];
-    const bool ok = views ? associate_views<DepthT>(p, views, n_views, xp, c) : associate_point<DepthT>(p, depth, xp, c);
+    const bool ok = associate_views<DepthT>(p, views, n_views, xp, c);
     corr[3 * (size_t)i] = c[0];
     corr[3 * (size_t)i + 1] = c[1];
     corr[3 * (size_t)i + 2] = c[2];
@@ -891,7 +864,7 @@ struct RegTail {
     double *partial_reg;
     double rw;
     int N, k, n_tiles;
-    // dfh_gn_iteration: doubles the launch's LAST workgroups set to zero (the solve's workspace: its clearing rides along here
+    // dfh_gn_solve: doubles the launch's LAST workgroups set to zero (the solve's workspace: its clearing rides along here
     // instead of being a launch of its own between gather and solve); first_zero_wg = index of the first such workgroup
     double *zero_ptr;
     unsigned long long zero_count;
@@ -904,13 +877,12 @@ __device__ void gn_reg_pairs(int block, const int *__restrict__ node_nbr, int N,
                              double *__restrict__ rhs, double *__restrict__ cost_count, double *__restrict__ partial_reg);
 
 // ASSOC: the projective association (associate_kernel's arithmetic, same bits) runs inside this kernel -- every sample of the
-// tile is warped once, associated against `depth`, its correspondence and validity are written to corr / valid (for the
+// tile is warped once, associated against the frame's views, its correspondence and validity are written to corr / valid (for the
 // callers that read them) and the valid ones go straight on to their Jacobian rows: one launch and one blend + warp per
 // sample less per GN iteration.
 struct AssocArgs {
     AssocParams ap;
-    const float *depth;
-    const AssocView *views;     // non-null: n_views views from a dfh_gn_pack_views table, of the kernel's depth type (depth / ap.lw_cam unused)
+    const AssocView *views;     // n_views views from a dfh_gn_pack_views table, of the kernel's depth type
     int n_views;
     int cull;                   // 1: drop, per tile, the views none of its samples can be valid in (tile_view_mask)
 };
@@ -1005,7 +977,7 @@ __global__ __launch_bounds__(kTile) void gn_build_data_kernel(const double *__re
         view_mask = tile_view_mask(aa.ap, aa.views, aa.n_views, box, &sMask);
     }
     if (ASSOC && tid < tile_n)
-        a_ok = aa.views ? associate_views<float>(aa.ap, aa.views, aa.n_views, a_xp, a_c, view_mask) : associate_point<float>(aa.ap, aa.depth, a_xp, a_c);
+        a_ok = associate_views<float>(aa.ap, aa.views, aa.n_views, a_xp, a_c, view_mask);
     // corr / valid are outputs only: stored after the last global load of the kernel (stored here, every later s_waitcnt for a
     // load also waited for these stores' acknowledgements)
     auto store_assoc = [&]() {
@@ -2612,8 +2584,7 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(3, 8))) v
             const D3 x1 = dqb_warp_exact(bh, pfx, pfy, pfz);
             const D3 xp = dqb_warp_exact(p.lw.q, round_f32(x1.x), round_f32(x1.y), round_f32(x1.z));
             double c[3];
-            const bool ok = aa.views ? associate_views<DepthT>(aa.ap, aa.views, aa.n_views, xp, c)
-                                     : associate_point<DepthT>(aa.ap, reinterpret_cast<const DepthT *>(aa.depth), xp, c);
+            const bool ok = associate_views<DepthT>(aa.ap, aa.views, aa.n_views, xp, c);
             if (ok) {
                 double Jrow[6 * K];
                 double r = data_row_from(node_dq, idx, w, K, p.lw.q, bh, nb, pfx, pfy, pfz, xp, snrm[3 * (size_t)s], snrm[3 * (size_t)s + 1],
@@ -2749,8 +2720,57 @@ __global__ __launch_bounds__(256) void apply_twist_kernel(double *__restrict__ n
 }  // namespace dfh
 
 // =================================================================================== C ABI
-static int fill_assoc_params(dfh::AssocParams &p, const double lw_dq[8], int H, int W, const double K[9], const double Kinv[9],
-                             const double lw_cam[12], double scale, const double center[3], double half, double max_dist, int knn);
+// What every GN entry point checks of its problem: the samples and nodes; with `system` also the block system and the plans.
+static int check_problem(const char *what, const dfh_gn_problem *p, bool system) {
+    using namespace dfh;
+    DFH_REQUIRE(p, "%s: null problem", what);
+    DFH_REQUIRE(p->n_samples >= 0 && p->n_nodes >= 1, "%s: bad sizes", what);
+    DFH_REQUIRE(p->knn >= 1 && p->knn <= kKMaxS, "%s: knn=%d outside [1,%d]", what, p->knn, kKMaxS);
+    DFH_REQUIRE(p->huber_delta >= 0.0, "%s: negative huber_delta", what);
+    DFH_REQUIRE(p->node_dq, "%s: null node_dq", what);
+    if (p->n_samples > 0)
+        DFH_REQUIRE(p->sample_pos && p->sample_nrm && p->nbr && p->weights && p->corr && p->valid, "%s: null sample pointer", what);
+    if (!system) return DFH_OK;
+    DFH_REQUIRE(p->n_blocks >= 1, "%s: bad sizes", what);
+    DFH_REQUIRE(p->node_pos && p->node_w && p->row_ptr && p->col && p->vals && p->rhs && p->cost_count, "%s: null pointer", what);
+    DFH_REQUIRE(p->n_upper >= 0 && p->n_upper <= p->n_blocks && (p->n_upper == 0 || p->blk_upper), "%s: bad upper-block list", what);
+    if (p->blk_ptr) {
+        // (a rank whose slab holds no surface has no samples, no rows and EMPTY entry lists: null pointers are fine then)
+        DFH_REQUIRE(p->n_rows >= 0 && p->node_ptr && (p->n_rows == 0 || (p->blk_ent && p->node_ent)), "%s: null plan array", what);
+        DFH_REQUIRE(p->n_samples == 0 || (p->run_id && p->partial && p->n_rows > 0), "%s: samples without rows", what);
+        if (p->partial_reg)
+            DFH_REQUIRE(p->rblk_ptr && p->rblk_ent && p->rnode_ptr && p->rnode_ent, "%s: null regulariser plan array", what);
+    }
+    return DFH_OK;
+}
+
+// ... and of its frame; `fused`: the association runs inside the data-row kernel, which reads float32 maps only.
+static int check_frame(const char *what, const dfh_gn_frame *f, bool fused) {
+    using namespace dfh;
+    DFH_REQUIRE(f, "%s: null frame", what);
+    DFH_REQUIRE(f->views && f->n_views >= 1 && f->n_views <= DFH_GN_MAX_VIEWS, "%s: needs 1..%d packed views", what, DFH_GN_MAX_VIEWS);
+    DFH_REQUIRE(f->depth_dtype == DFH_F32 || f->depth_dtype == DFH_F64, "%s: bad depth_dtype", what);
+    DFH_REQUIRE(!fused || f->depth_dtype == DFH_F32, "%s: the fused association needs float32 depth maps", what);
+    DFH_REQUIRE(f->H >= 2 && f->W >= 2 && f->scale != 0.0, "%s: bad depth map / scale", what);
+    return DFH_OK;
+}
+
+// The association's kernel arguments.  cull: drop, per tile, the views none of its samples can be valid in (tile_view_mask):
+// it costs a tile one barrier and one memory round trip (+5 % on the 3-view frame, where the views all face the object and
+// nothing is dropped), so it is taken from four views up (the 8-view orbit: -9 % of the solve stage).
+static dfh::AssocArgs assoc_args(const dfh_gn_problem &p, const dfh_gn_frame &f, bool cull) {
+    using namespace dfh;
+    AssocArgs aa;
+    for (int i = 0; i < 9; ++i) { aa.ap.K.m[i] = f.K[i]; aa.ap.Kinv.m[i] = f.Kinv[i]; }
+    for (int i = 0; i < 8; ++i) aa.ap.lw.q[i] = p.lw_dq[i];
+    aa.ap.scale = f.scale; aa.ap.inv_scale = 1.0 / f.scale;
+    aa.ap.cx = f.center[0]; aa.ap.cy = f.center[1]; aa.ap.cz = f.center[2]; aa.ap.half = f.half; aa.ap.max_dist = f.max_dist;
+    aa.ap.H = f.H; aa.ap.W = f.W; aa.ap.k = p.knn;
+    aa.views = static_cast<const AssocView *>(f.views);
+    aa.n_views = f.n_views;
+    aa.cull = cull && f.n_views >= 4 && !on(opt().gn_no_view_cull) ? 1 : 0;
+    return aa;
+}
 
 extern "C" {
 
@@ -2915,58 +2935,25 @@ int dfh_permute_samples(const long *order, int n_samples, int knn, const double 
     return DFH_OK;
 }
 
-// views: a dfh_gn_pack_views table (then depth / lw_cam are unused), or nullptr for the one view (depth, lw_cam)
-static int gn_associate_impl(const char *what, const double *sample_pos, const int *nbr, const double *weights, int n_samples, int knn,
-                             const double *node_dq, const double lw_dq[8], const void *depth, int depth_dtype, const void *views, int n_views,
-                             int H, int W, const double K[9], const double Kinv[9], const double lw_cam[12], double scale,
-                             const double center[3], double half, double max_dist, double *corr_out, unsigned char *valid_out, void *stream) {
+int dfh_gn_associate(const dfh_gn_problem *problem, const dfh_gn_frame *frame, void *stream) {
     using namespace dfh;
-    DFH_REQUIRE(n_samples >= 0 && knn >= 1 && knn <= kKMaxS, "%s: bad sizes", what);
-    DFH_REQUIRE(depth_dtype == DFH_F32 || depth_dtype == DFH_F64, "%s: bad depth_dtype", what);
-    DFH_REQUIRE(H >= 2 && W >= 2 && scale != 0.0, "%s: bad depth map / scale", what);
-    if (n_samples == 0) return DFH_OK;
-    DFH_REQUIRE(sample_pos && nbr && weights && node_dq && lw_dq && (depth || views) && K && Kinv && lw_cam && center && corr_out && valid_out,
-                "%s: null pointer", what);
-    AssocParams p;
-    {
-        const int rc = fill_assoc_params(p, lw_dq, H, W, K, Kinv, lw_cam, scale, center, half, max_dist, knn);
-        if (rc != DFH_OK) return rc;
-    }
-    dim3 grid((n_samples + 255) / 256), block(256);
-    const AssocView *vw = static_cast<const AssocView *>(views);
-    if (depth_dtype == DFH_F32) {
-        hipLaunchKernelGGL(associate_kernel<float>, grid, block, 0, (hipStream_t)stream, sample_pos, nbr, weights, n_samples,
-                           node_dq, (const float *)depth, p, corr_out, valid_out, vw, n_views);
+    int rc = check_problem("dfh_gn_associate", problem, false);
+    if (rc == DFH_OK) rc = check_frame("dfh_gn_associate", frame, false);
+    if (rc != DFH_OK) return rc;
+    const dfh_gn_problem &q = *problem;
+    if (q.n_samples == 0) return DFH_OK;
+    const AssocArgs aa = assoc_args(q, *frame, false);
+    dim3 grid((q.n_samples + 255) / 256), block(256);
+    if (frame->depth_dtype == DFH_F32) {
+        hipLaunchKernelGGL(associate_kernel<float>, grid, block, 0, (hipStream_t)stream, q.sample_pos, q.nbr, q.weights, q.n_samples,
+                           q.node_dq, aa.ap, q.corr, q.valid, aa.views, aa.n_views);
     } else {
-        hipLaunchKernelGGL(associate_kernel<double>, grid, block, 0, (hipStream_t)stream, sample_pos, nbr, weights, n_samples,
-                           node_dq, (const double *)depth, p, corr_out, valid_out, vw, n_views);
+        hipLaunchKernelGGL(associate_kernel<double>, grid, block, 0, (hipStream_t)stream, q.sample_pos, q.nbr, q.weights, q.n_samples,
+                           q.node_dq, aa.ap, q.corr, q.valid, aa.views, aa.n_views);
     }
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;
 }
-
-int dfh_gn_associate(const double *sample_pos, const int *nbr, const double *weights, int n_samples, int knn,
-                     const double *node_dq, const double lw_dq[8], const void *depth, int depth_dtype, int H, int W,
-                     const double K[9], const double Kinv[9], const double lw_cam[12], double scale,
-                     const double center[3], double half, double max_dist, double *corr_out,
-                     unsigned char *valid_out, void *stream) {
-    return gn_associate_impl("dfh_gn_associate", sample_pos, nbr, weights, n_samples, knn, node_dq, lw_dq, depth, depth_dtype, nullptr, 0, H, W,
-                             K, Kinv, lw_cam, scale, center, half, max_dist, corr_out, valid_out, stream);
-}
-
-static const double kIdentity34[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-
-int dfh_gn_associate_views(const double *sample_pos, const int *nbr, const double *weights, int n_samples, int knn,
-                           const double *node_dq, const double lw_dq[8], const void *views, int n_views, int depth_dtype, int H, int W,
-                           const double K[9], const double Kinv[9], double scale, const double center[3], double half,
-                           double max_dist, double *corr_out, unsigned char *valid_out, void *stream) {
-    using namespace dfh;
-    DFH_REQUIRE(views && n_views >= 1 && n_views <= DFH_GN_MAX_VIEWS, "dfh_gn_associate_views: needs 1..%d packed views", DFH_GN_MAX_VIEWS);
-    return gn_associate_impl("dfh_gn_associate_views", sample_pos, nbr, weights, n_samples, knn, node_dq, lw_dq, nullptr, depth_dtype, views,
-                             n_views, H, W, K, Kinv, kIdentity34, scale, center, half, max_dist, corr_out, valid_out, stream);
-}
-
-size_t dfh_gn_views_bytes(int n_views) { return n_views > 0 ? (size_t)n_views * sizeof(dfh::AssocView) : 0; }
 
 // The table travels as kernel arguments of a one-workgroup launch that writes it to device memory (a hipMemcpyAsync from
 // pageable host memory is staged by the runtime and stalls the stream for tens of microseconds)
@@ -3012,31 +2999,46 @@ static size_t view_cells_floats(int H, int W) {
     return 2 * (size_t)((W + dfh::kCellPx - 1) / dfh::kCellPx) * (size_t)((H + dfh::kCellPx - 1) / dfh::kCellPx);
 }
 
-size_t dfh_gn_views_bytes_cells(int n_views, int H, int W) {
+size_t dfh_gn_views_bytes(int n_views, int depth_dtype, int H, int W) {
     if (n_views <= 0 || H <= 0 || W <= 0) return 0;
+    if (depth_dtype == DFH_F64) return (size_t)n_views * sizeof(dfh::AssocView);
+    if (depth_dtype != DFH_F32) return 0;
     return views_cells_offset(n_views) + (size_t)n_views * view_cells_floats(H, W) * sizeof(float);
 }
 
-static int pack_views_impl(void *views_out, int n_views, const void *const *depth, const double *lw_cam, int cells, int H, int W, void *stream) {
+// the inverse of an extrinsic's 3x3 part (adjugate)
+static int invert_rotation(const double m[12], double Rinv[9]) {
+    const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], i = m[10];
+    const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
+    DFH_REQUIRE(det != 0.0, "dfh_gn_pack_views: singular extrinsic");
+    const double id = 1.0 / det;
+    Rinv[0] = (e * i - f * h) * id; Rinv[1] = (c * h - b * i) * id; Rinv[2] = (b * f - c * e) * id;
+    Rinv[3] = (f * g - d * i) * id; Rinv[4] = (a * i - c * g) * id; Rinv[5] = (c * d - a * f) * id;
+    Rinv[6] = (d * h - e * g) * id; Rinv[7] = (b * g - a * h) * id; Rinv[8] = (a * e - b * d) * id;
+    return DFH_OK;
+}
+
+int dfh_gn_pack_views(void *out, int n_views, const void *const *depth, int depth_dtype, int H, int W, const double *lw_cam,
+                      void *stream) {
     using namespace dfh;
-    DFH_REQUIRE(views_out && depth && lw_cam, "dfh_gn_pack_views: null pointer");
+    DFH_REQUIRE(out && depth && lw_cam, "dfh_gn_pack_views: null pointer");
     DFH_REQUIRE(n_views >= 1 && n_views <= DFH_GN_MAX_VIEWS, "dfh_gn_pack_views: %d views (1..%d)", n_views, DFH_GN_MAX_VIEWS);
+    DFH_REQUIRE(depth_dtype == DFH_F32 || depth_dtype == DFH_F64, "dfh_gn_pack_views: bad depth_dtype");
+    DFH_REQUIRE(H >= 2 && W >= 2, "dfh_gn_pack_views: bad depth map size");
     static_assert(DFH_GN_MAX_VIEWS <= kViewChunk, "one upload launch");
+    const bool cells = depth_dtype == DFH_F32;
     ViewChunk c;
     std::memset(&c, 0, sizeof c);
     for (int v = 0; v < n_views; ++v) {
         DFH_REQUIRE(depth[v], "dfh_gn_pack_views: depth map %d is null", v);
-        AssocParams tmp;                                  // (for the inverse of the extrinsic's 3x3 part)
-        const double zero3[3] = {0, 0, 0}, eye9[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, ident8[8] = {1, 0, 0, 0, 0, 0, 0, 0};
-        const int rc = fill_assoc_params(tmp, ident8, 2, 2, eye9, eye9, lw_cam + 12 * v, 1.0, zero3, 0.0, 0.0, 1);
+        const double *m = lw_cam + 12 * v;
+        const int rc = invert_rotation(m, c.v[v].Rinv);
         if (rc != DFH_OK) return rc;
-        for (int i = 0; i < 12; ++i) c.v[v].lw_cam[i] = lw_cam[12 * v + i];
-        for (int i = 0; i < 9; ++i) c.v[v].Rinv[i] = tmp.Rinv.m[i];
+        for (int i = 0; i < 12; ++i) c.v[v].lw_cam[i] = m[i];
         c.v[v].depth = depth[v];
         if (cells) {
-            c.v[v].cells = reinterpret_cast<const float *>(static_cast<char *>(views_out) + views_cells_offset(n_views)) + (size_t)v * view_cells_floats(H, W);
+            c.v[v].cells = reinterpret_cast<const float *>(static_cast<char *>(out) + views_cells_offset(n_views)) + (size_t)v * view_cells_floats(H, W);
             // the depth-interval test of tile_view_mask needs |R x| = |x|: R^T R = I to 1e-9 (what a camera pose is)
-            const double *m = lw_cam + 12 * v;
             double worst = 0.0;
             for (int a = 0; a < 3; ++a)
                 for (int b = 0; b < 3; ++b) {
@@ -3046,54 +3048,30 @@ static int pack_views_impl(void *views_out, int n_views, const void *const *dept
             c.v[v].cull_ok = worst <= 1e-9 ? 1.0 : 0.0;
         }
     }
-    hipLaunchKernelGGL(upload_views_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, static_cast<AssocView *>(views_out), c, n_views);
+    hipLaunchKernelGGL(upload_views_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, static_cast<AssocView *>(out), c, n_views);
     if (cells) {
         const unsigned ncell = (unsigned)(view_cells_floats(H, W) / 2);
         hipLaunchKernelGGL(view_cells_kernel, dim3(ncell, (unsigned)n_views), dim3(256), 0, (hipStream_t)stream,
-                           static_cast<const AssocView *>(views_out), H, W);
+                           static_cast<const AssocView *>(out), H, W);
     }
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;
 }
 
-int dfh_gn_pack_views(void *views_out, int n_views, const void *const *depth, const double *lw_cam, void *stream) {
-    return pack_views_impl(views_out, n_views, depth, lw_cam, 0, 0, 0, stream);
-}
-
-int dfh_gn_pack_views_cells(void *views_out, int n_views, const void *const *depth, int H, int W, const double *lw_cam, void *stream) {
-    using namespace dfh;
-    DFH_REQUIRE(H >= 2 && W >= 2, "dfh_gn_pack_views_cells: bad depth map size");
-    return pack_views_impl(views_out, n_views, depth, lw_cam, 1, H, W, stream);
-}
-
-static int gn_build_impl(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                         double *corr, unsigned char *valid, int n_samples, int knn, const double *node_dq,
-                         const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                         const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                         double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                         const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                         const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                         void *stream, const dfh::AssocArgs *assoc = nullptr, double *zero_ptr = nullptr, size_t zero_count = 0,
-                         bool *zeroed = nullptr, const int *blk_upper = nullptr, int n_upper = 0) {
+// assoc: the association fused into the data-row kernel (the caller checked that there is a plan); zero_ptr / zero_count:
+// doubles the launch's last workgroups clear (*zeroed says whether they did).  The problem is checked by the caller.
+static int gn_build_impl(const dfh_gn_problem &q, const dfh::AssocArgs *assoc, void *stream, double *zero_ptr = nullptr,
+                         size_t zero_count = 0, bool *zeroed = nullptr) {
     using namespace dfh;
     if (zeroed) *zeroed = false;
-    const bool planned = blk_ptr != nullptr;
-    DFH_REQUIRE(!assoc || planned, "dfh_gn_build: association inside the build needs a plan");
-    DFH_REQUIRE(huber_delta >= 0.0, "dfh_gn_build: negative huber_delta");
+    const int knn = q.knn, n_samples = q.n_samples, n_nodes = q.n_nodes, n_blocks = q.n_blocks, n_rows = q.n_rows;
+    double *vals = q.vals, *rhs = q.rhs, *cost_count = q.cost_count, *partial = q.partial, *partial_reg = q.partial_reg;
+    const bool planned = q.blk_ptr != nullptr;
     const bool planned_reg = planned && partial_reg != nullptr;
-    if (planned_reg) DFH_REQUIRE(rblk_ptr && rblk_ent && rnode_ptr && rnode_ent, "dfh_gn_build_planned: null regulariser plan array");
-    DFH_REQUIRE(n_samples >= 0 && n_nodes >= 1 && n_blocks >= 1, "dfh_gn_build: bad sizes");
-    DFH_REQUIRE(knn >= 1 && knn <= kKMaxS, "dfh_gn_build: knn=%d outside [1,%d]", knn, kKMaxS);
-    DFH_REQUIRE(node_dq && node_pos && node_w && lw_dq && row_ptr && col && vals && rhs && cost_count, "dfh_gn_build: null pointer");
-    if (planned) {
-        // (a rank whose slab holds no surface has no samples, no rows and EMPTY entry lists: null pointers are fine then)
-        DFH_REQUIRE(n_rows >= 0 && node_ptr && (n_rows == 0 || (blk_ent && node_ent)), "dfh_gn_build_planned: null plan array");
-        DFH_REQUIRE(n_samples == 0 || (run_id && partial && n_rows > 0), "dfh_gn_build_planned: samples without rows");
-    }
     hipStream_t s = (hipStream_t)stream;
     const int n_tiles = (n_samples + kTile - 1) / kTile;
     // planned build: the regulariser's pair rows ride along in the data-row launch (they only write partial_reg)
-    const bool reg_in_data_launch = planned_reg && node_nbr && rw != 0.0 && n_samples > 0 && !on(opt().gn_reg_own_launch);
+    const bool reg_in_data_launch = planned_reg && q.node_nbr && q.rw != 0.0 && n_samples > 0 && !on(opt().gn_reg_own_launch);
     double *tile_cost = planned && partial ? partial + (size_t)n_rows * gn_row_stride(knn) : nullptr;   // 2 doubles per tile, behind the rows; then one live flag per row
     if (planned) {
         // every block / rhs entry / cost is written by the gather, and every row of `partial` by the tile pass (rows
@@ -3107,15 +3085,14 @@ static int gn_build_impl(const double *sample_pos, const double *sample_nrm, con
         DFH_HIP_CHECK(hipMemsetAsync(cost_count, 0, sizeof(double) * 2, s));
     }
     if (n_samples > 0) {
-        DFH_REQUIRE(sample_pos && sample_nrm && nbr && weights && corr && valid, "dfh_gn_build: null sample pointer");
         BuildParams p;
-        for (int i = 0; i < 8; ++i) p.lw.q[i] = lw_dq[i];
-        p.S = n_samples; p.k = knn; p.N = n_nodes; p.huber = huber_delta;
+        for (int i = 0; i < 8; ++i) p.lw.q[i] = q.lw_dq[i];
+        p.S = n_samples; p.k = knn; p.N = n_nodes; p.huber = q.huber_delta;
         RegTail rt = {};
         rt.n_tiles = n_tiles;
         if (reg_in_data_launch) {
-            rt.node_nbr = node_nbr; rt.node_pos = node_pos; rt.node_w = node_w; rt.partial_reg = partial_reg;
-            rt.rw = rw; rt.N = n_nodes; rt.k = knn;
+            rt.node_nbr = q.node_nbr; rt.node_pos = q.node_pos; rt.node_w = q.node_w; rt.partial_reg = partial_reg;
+            rt.rw = q.rw; rt.N = n_nodes; rt.k = knn;
         }
         unsigned n_wg = (unsigned)(n_tiles + (reg_in_data_launch ? (n_nodes * knn + kTileWaves - 1) / kTileWaves : 0));
         if (planned && zero_ptr && zero_count > 0 && (zero_count + kZeroPerWg - 1) / kZeroPerWg < (1u << 20)) {
@@ -3128,14 +3105,14 @@ static int gn_build_impl(const double *sample_pos, const double *sample_nrm, con
 #define DFH_BUILD(KK)                                                                                               \
     case KK:                                                                                                        \
         if (assoc)                                                                                                  \
-            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, true>), grid, block, 0, s, sample_pos, sample_nrm, nbr, weights, corr, \
-                               valid, node_dq, p, row_ptr, col, vals, rhs, cost_count, run_id, partial, tile_cost, rt, aa); \
+            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, true>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
+                               q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, aa); \
         else if (planned)                                                                                           \
-            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, false>), grid, block, 0, s, sample_pos, sample_nrm, nbr, weights, corr, \
-                               valid, node_dq, p, row_ptr, col, vals, rhs, cost_count, run_id, partial, tile_cost, rt, aa); \
+            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, false>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
+                               q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, aa); \
         else                                                                                                        \
-            hipLaunchKernelGGL((gn_build_data_kernel<KK, false, false>), grid, block, 0, s, sample_pos, sample_nrm, nbr, weights, corr, \
-                               valid, node_dq, p, row_ptr, col, vals, rhs, cost_count, run_id, partial, tile_cost, rt, aa); \
+            hipLaunchKernelGGL((gn_build_data_kernel<KK, false, false>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
+                               q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, aa); \
         break
         switch (knn) {
             DFH_BUILD(1); DFH_BUILD(2); DFH_BUILD(3); DFH_BUILD(4); DFH_BUILD(5); DFH_BUILD(6); DFH_BUILD(7); DFH_BUILD(8);
@@ -3148,17 +3125,18 @@ static int gn_build_impl(const double *sample_pos, const double *sample_nrm, con
     RegLists rl = {};
     const bool reg_in_gather = reg_in_data_launch && !on(opt().gn_reg_own_gather);
     if (reg_in_gather) {
-        rl.partial = partial_reg; rl.blk_ptr = rblk_ptr; rl.blk_ent = rblk_ent; rl.node_ptr = rnode_ptr; rl.node_ent = rnode_ent;
+        rl.partial = partial_reg; rl.blk_ptr = q.rblk_ptr; rl.blk_ent = q.rblk_ent; rl.node_ptr = q.rnode_ptr; rl.node_ent = q.rnode_ent;
         rl.n_rows = n_nodes * knn;
     }
     if (planned) {
-        const int2 *upper = (blk_upper && n_upper > 0 && !on(opt().gn_gather_full)) ? reinterpret_cast<const int2 *>(blk_upper) : nullptr;
+        const int n_upper = q.n_upper;
+        const int2 *upper = (q.blk_upper && n_upper > 0 && !on(opt().gn_gather_full)) ? reinterpret_cast<const int2 *>(q.blk_upper) : nullptr;
         const int n_walk = upper ? n_upper : n_blocks;
         dim3 grid((unsigned)((n_walk + 3) / 4 + (n_nodes + 3) / 4 + 1)), block(256);
 #define DFH_GATHER(KK)                                                                                              \
     case KK:                                                                                                        \
-        hipLaunchKernelGGL(gn_gather_kernel<KK>, grid, block, 0, s, partial, tile_cost + 2 * (size_t)n_tiles, n_rows, blk_ptr, blk_ent, n_blocks, node_ptr,  \
-                           node_ent, n_nodes, vals, rhs, cost_count, tile_cost, n_tiles, 2, false, dbg_part, rl, upper, n_upper);   \
+        hipLaunchKernelGGL(gn_gather_kernel<KK>, grid, block, 0, s, partial, tile_cost + 2 * (size_t)n_tiles, n_rows, q.blk_ptr, q.blk_ent, n_blocks, \
+                           q.node_ptr, q.node_ent, n_nodes, vals, rhs, cost_count, tile_cost, n_tiles, 2, false, dbg_part, rl, upper, n_upper);  \
         break
         switch (knn) {
             DFH_GATHER(1); DFH_GATHER(2); DFH_GATHER(3); DFH_GATHER(4); DFH_GATHER(5); DFH_GATHER(6); DFH_GATHER(7); DFH_GATHER(8);
@@ -3166,138 +3144,36 @@ static int gn_build_impl(const double *sample_pos, const double *sample_nrm, con
 #undef DFH_GATHER
         DFH_HIP_CHECK(hipGetLastError());
     }
-    if (node_nbr && rw != 0.0) {
+    if (q.node_nbr && q.rw != 0.0) {
         const int n = n_nodes * knn;
         if (!reg_in_data_launch)
-            hipLaunchKernelGGL(gn_build_reg_kernel, dim3((n + 3) / 4), dim3(256), 0, s, node_nbr, n_nodes, knn, node_dq, node_pos,
-                               node_w, rw, row_ptr, col, vals, rhs, cost_count, planned_reg ? partial_reg : nullptr);
+            hipLaunchKernelGGL(gn_build_reg_kernel, dim3((n + 3) / 4), dim3(256), 0, s, q.node_nbr, n_nodes, knn, q.node_dq, q.node_pos,
+                               q.node_w, q.rw, q.row_ptr, q.col, vals, rhs, cost_count, planned_reg ? partial_reg : nullptr);
         if (planned_reg && !reg_in_gather) {
             dim3 grid((unsigned)((n_blocks + 3) / 4 + (n_nodes + 3) / 4 + 1)), block(256);
-            hipLaunchKernelGGL(gn_gather_kernel<2>, grid, block, 0, s, partial_reg, (const double *)nullptr, n, rblk_ptr, rblk_ent, n_blocks, rnode_ptr,
-                               rnode_ent, n_nodes, vals, rhs, cost_count, partial_reg + gn_row_gram(2) + 12, n, gn_row_stride(2), true, dbg_part,
-                               RegLists{});
+            hipLaunchKernelGGL(gn_gather_kernel<2>, grid, block, 0, s, partial_reg, (const double *)nullptr, n, q.rblk_ptr, q.rblk_ent, n_blocks,
+                               q.rnode_ptr, q.rnode_ent, n_nodes, vals, rhs, cost_count, partial_reg + gn_row_gram(2) + 12, n, gn_row_stride(2),
+                               true, dbg_part, RegLists{});
         }
         DFH_HIP_CHECK(hipGetLastError());
     }
     return DFH_OK;
 }
 
-int dfh_gn_build(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                 const double *corr, const unsigned char *valid, int n_samples, int knn, const double *node_dq,
-                 const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                 const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                 double *rhs, double *cost_count, void *stream) {
-    return gn_build_impl(sample_pos, sample_nrm, nbr, weights, const_cast<double *>(corr), const_cast<unsigned char *>(valid), n_samples,
-                         knn, node_dq, node_pos, node_w, node_nbr,
-                         n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs, cost_count, nullptr, 0, nullptr, nullptr, nullptr,
-                         nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0.0, stream);
+int dfh_gn_build(const dfh_gn_problem *problem, const dfh_gn_frame *frame, void *stream) {
+    using namespace dfh;
+    int rc = check_problem("dfh_gn_build", problem, true);
+    if (rc == DFH_OK && frame) rc = check_frame("dfh_gn_build", frame, true);
+    if (rc != DFH_OK) return rc;
+    if (!frame) return gn_build_impl(*problem, nullptr, stream);
+    DFH_REQUIRE(problem->blk_ptr, "dfh_gn_build: association inside the build needs a plan");
+    const AssocArgs aa = assoc_args(*problem, *frame, true);
+    return gn_build_impl(*problem, &aa, stream);
 }
 
 size_t dfh_gn_partial_doubles(int knn) {
     if (knn < 1 || knn > dfh::kKMaxS) return 0;
     return (size_t)dfh::gn_row_stride(knn);
-}
-
-int dfh_gn_build_planned(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                         const double *corr, const unsigned char *valid, int n_samples, int knn, const double *node_dq,
-                         const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                         const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                         double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                         const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                         const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                         void *stream) {
-    using namespace dfh;
-    DFH_REQUIRE(blk_ptr, "dfh_gn_build_planned: null blk_ptr");
-    return gn_build_impl(sample_pos, sample_nrm, nbr, weights, const_cast<double *>(corr), const_cast<unsigned char *>(valid), n_samples,
-                         knn, node_dq, node_pos, node_w, node_nbr,
-                         n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs, cost_count, run_id, n_rows, partial, blk_ptr,
-                         blk_ent, node_ptr, node_ent, partial_reg, rblk_ptr, rblk_ent, rnode_ptr, rnode_ent, huber_delta, stream);
-}
-
-static int fill_assoc_params(dfh::AssocParams &p, const double lw_dq[8], int H, int W, const double K[9], const double Kinv[9],
-                             const double lw_cam[12], double scale, const double center[3], double half, double max_dist, int knn) {
-    using namespace dfh;
-    for (int i = 0; i < 9; ++i) { p.K.m[i] = K[i]; p.Kinv.m[i] = Kinv[i]; }
-    for (int i = 0; i < 12; ++i) p.lw_cam.m[i] = lw_cam[i];
-    for (int i = 0; i < 8; ++i) p.lw.q[i] = lw_dq[i];
-    {   // inverse of the 3x3 part (adjugate)
-        const double *m = lw_cam;
-        const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g = m[8], h = m[9], i = m[10];
-        const double det = a * (e * i - f * h) - b * (d * i - f * g) + c * (d * h - e * g);
-        DFH_REQUIRE(det != 0.0, "dfh_gn_associate: singular extrinsic");
-        const double id = 1.0 / det;
-        p.Rinv.m[0] = (e * i - f * h) * id; p.Rinv.m[1] = (c * h - b * i) * id; p.Rinv.m[2] = (b * f - c * e) * id;
-        p.Rinv.m[3] = (f * g - d * i) * id; p.Rinv.m[4] = (a * i - c * g) * id; p.Rinv.m[5] = (c * d - a * f) * id;
-        p.Rinv.m[6] = (d * h - e * g) * id; p.Rinv.m[7] = (b * g - a * h) * id; p.Rinv.m[8] = (a * e - b * d) * id;
-    }
-    p.scale = scale; p.inv_scale = 1.0 / scale; p.cx = center[0]; p.cy = center[1]; p.cz = center[2]; p.half = half; p.max_dist = max_dist;
-    p.H = H; p.W = W; p.k = knn;
-    return DFH_OK;
-}
-
-static int gn_build_planned_assoc_impl(const char *what, const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                               double *corr_out, unsigned char *valid_out, int n_samples, int knn, const double *node_dq,
-                               const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                               const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                               double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                               const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                               const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                               const float *depth, const void *views, int n_views, int H, int W, const double K[9], const double Kinv[9],
-                               const double lw_cam[12], double scale, const double center[3], double half, double max_dist, void *stream,
-                               const int *blk_upper = nullptr, int n_upper = 0) {
-    using namespace dfh;
-    DFH_REQUIRE(blk_ptr, "%s: null blk_ptr", what);
-    DFH_REQUIRE((depth || views) && K && Kinv && lw_cam && center && lw_dq && corr_out && valid_out, "%s: null pointer", what);
-    DFH_REQUIRE(H >= 2 && W >= 2 && scale != 0.0, "%s: bad depth map / scale", what);
-    AssocArgs aa;
-    const int rc = fill_assoc_params(aa.ap, lw_dq, H, W, K, Kinv, lw_cam, scale, center, half, max_dist, knn);
-    if (rc != DFH_OK) return rc;
-    aa.depth = depth;
-    aa.views = static_cast<const AssocView *>(views);
-    aa.n_views = n_views;
-    // per-tile view culling costs a tile one barrier and one memory round trip (+5 % on the 3-view frame, where the views all
-    // face the object and nothing is dropped): taken from four views up (the 8-view orbit: -9 % of the solve stage)
-    aa.cull = views && n_views >= 4 && !on(opt().gn_no_view_cull) ? 1 : 0;
-    return gn_build_impl(sample_pos, sample_nrm, nbr, weights, corr_out, valid_out, n_samples, knn, node_dq, node_pos, node_w, node_nbr,
-                         n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs, cost_count, run_id, n_rows, partial, blk_ptr,
-                         blk_ent, node_ptr, node_ent, partial_reg, rblk_ptr, rblk_ent, rnode_ptr, rnode_ent, huber_delta, stream, &aa,
-                         nullptr, 0, nullptr, blk_upper, n_upper);
-}
-
-int dfh_gn_build_planned_assoc(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                               double *corr_out, unsigned char *valid_out, int n_samples, int knn, const double *node_dq,
-                               const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                               const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                               double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                               const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                               const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                               const float *depth, int H, int W, const double K[9], const double Kinv[9], const double lw_cam[12],
-                               double scale, const double center[3], double half, double max_dist, void *stream) {
-    return gn_build_planned_assoc_impl("dfh_gn_build_planned_assoc", sample_pos, sample_nrm, nbr, weights, corr_out, valid_out, n_samples, knn,
-                                       node_dq, node_pos, node_w, node_nbr, n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs, cost_count,
-                                       run_id, n_rows, partial, blk_ptr, blk_ent, node_ptr, node_ent, partial_reg, rblk_ptr, rblk_ent,
-                                       rnode_ptr, rnode_ent, huber_delta, depth, nullptr, 0, H, W, K, Kinv, lw_cam, scale, center, half,
-                                       max_dist, stream);
-}
-
-int dfh_gn_build_planned_assoc_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                               double *corr_out, unsigned char *valid_out, int n_samples, int knn, const double *node_dq,
-                               const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                               const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                               double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                               const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                               const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                               const void *views, int n_views, int H, int W, const double K[9], const double Kinv[9],
-                               double scale, const double center[3], double half, double max_dist, const int *blk_upper, int n_upper,
-                               void *stream) {
-    using namespace dfh;
-    DFH_REQUIRE(views && n_views >= 1 && n_views <= DFH_GN_MAX_VIEWS, "dfh_gn_build_planned_assoc_views: needs 1..%d packed views", DFH_GN_MAX_VIEWS);
-    DFH_REQUIRE(n_upper >= 0 && n_upper <= n_blocks && (n_upper == 0 || blk_upper), "dfh_gn_build_planned_assoc_views: bad upper-block list");
-    return gn_build_planned_assoc_impl("dfh_gn_build_planned_assoc_views", sample_pos, sample_nrm, nbr, weights, corr_out, valid_out, n_samples,
-                                       knn, node_dq, node_pos, node_w, node_nbr, n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs,
-                                       cost_count, run_id, n_rows, partial, blk_ptr, blk_ent, node_ptr, node_ent, partial_reg, rblk_ptr,
-                                       rblk_ent, rnode_ptr, rnode_ent, huber_delta, nullptr, views, n_views, H, W, K, Kinv, kIdentity34, scale,
-                                       center, half, max_dist, stream, blk_upper, n_upper);
 }
 
 size_t dfh_pcg_workspace_bytes(int n_nodes, int iters) {
@@ -3550,133 +3426,40 @@ int dfh_pcg_solve_update(const int *row_ptr, const int *col, double *vals, const
     return pcg_solve_impl(row_ptr, col, vals, rhs, n_nodes, iters, lm_abs, lm_rel, x_out, workspace, workspace_bytes, node_dq, step, stream);
 }
 
-static int gn_iteration_impl(const char *what, const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                     double *corr_out, unsigned char *valid_out, int n_samples, int knn, double *node_dq,
-                     const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                     const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                     double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                     const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                     const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                     const float *depth, const void *views, int n_views, int H, int W, const double K[9], const double Kinv[9],
-                     const double lw_cam[12], double scale, const double center[3], double half, double max_dist,
-                     int pcg_iters, double lm_abs, double lm_rel, double *x_out, void *pcg_workspace, size_t pcg_workspace_bytes,
-                     double step, void *stream, const int *blk_upper = nullptr, int n_upper = 0) {
+int dfh_gn_solve(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_solve_params *params, void *stream) {
     using namespace dfh;
-    DFH_REQUIRE(blk_ptr, "%s: null blk_ptr", what);
-    DFH_REQUIRE((depth || views) && K && Kinv && lw_cam && center && lw_dq && corr_out && valid_out && node_dq, "%s: null pointer", what);
-    DFH_REQUIRE(H >= 2 && W >= 2 && scale != 0.0, "%s: bad depth map / scale", what);
-    DFH_REQUIRE(n_nodes >= 1 && pcg_iters >= 1 && x_out && pcg_workspace, "%s: bad solve arguments", what);
-    DFH_REQUIRE(pcg_workspace_bytes >= dfh_pcg_workspace_bytes(n_nodes, pcg_iters), "%s: solve workspace too small", what);
-    AssocArgs aa;
-    int rc = fill_assoc_params(aa.ap, lw_dq, H, W, K, Kinv, lw_cam, scale, center, half, max_dist, knn);
+    int rc = check_problem("dfh_gn_solve", problem, true);
+    if (rc == DFH_OK) rc = check_frame("dfh_gn_solve", frame, true);
     if (rc != DFH_OK) return rc;
-    aa.depth = depth;
-    aa.views = static_cast<const AssocView *>(views);
-    aa.n_views = n_views;
-    // per-tile view culling costs a tile one barrier and one memory round trip (+5 % on the 3-view frame, where the views all
-    // face the object and nothing is dropped): taken from four views up (the 8-view orbit: -9 % of the solve stage)
-    aa.cull = views && n_views >= 4 && !on(opt().gn_no_view_cull) ? 1 : 0;
+    const dfh_gn_problem &q = *problem;
+    DFH_REQUIRE(q.blk_ptr, "dfh_gn_solve: null blk_ptr (the fused association needs a plan)");
+    DFH_REQUIRE(params, "dfh_gn_solve: null params");
+    const dfh_gn_solve_params &sp = *params;
+    DFH_REQUIRE(sp.n_iters >= 0 && sp.n_iters <= 1000, "dfh_gn_solve: %d iterations", sp.n_iters);
+    DFH_REQUIRE(sp.n_global >= 0 && sp.n_global <= 100, "dfh_gn_solve: %d rigid-mode steps", sp.n_global);
+    DFH_REQUIRE(sp.pcg_iters >= 1 && sp.x_out && sp.pcg_workspace, "dfh_gn_solve: bad solve arguments");
+    DFH_REQUIRE(sp.pcg_workspace_bytes >= dfh_pcg_workspace_bytes(q.n_nodes, sp.pcg_iters), "dfh_gn_solve: solve workspace too small");
+    const AssocArgs aa = assoc_args(q, *frame, true);
+    for (int g = 0; g < sp.n_global; ++g) {
+        rc = gn_build_impl(q, &aa, stream);
+        if (rc != DFH_OK) return rc;
+        rc = dfh_gn_global_step(q.vals, q.n_blocks, q.rhs, q.n_nodes, sp.global_lm, q.node_dq, sp.global_xi_out, sp.global_scratch,
+                                sp.global_scratch_bytes, stream);
+        if (rc != DFH_OK) return rc;
+    }
+    // the frame's iterations are queued back to back from here: nothing between them depends on the host
     double *zbegin = nullptr;
     size_t zcount = 0;
-    pcg_zero_range(pcg_workspace, n_nodes, pcg_iters, &zbegin, &zcount);
-    bool zeroed = false;
-    rc = gn_build_impl(sample_pos, sample_nrm, nbr, weights, corr_out, valid_out, n_samples, knn, node_dq, node_pos, node_w, node_nbr,
-                       n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs, cost_count, run_id, n_rows, partial, blk_ptr,
-                       blk_ent, node_ptr, node_ent, partial_reg, rblk_ptr, rblk_ent, rnode_ptr, rnode_ent, huber_delta, stream, &aa,
-                       on(opt().gn_iter_own_clear) ? nullptr : zbegin, zcount, &zeroed, blk_upper, n_upper);
-    if (rc != DFH_OK) return rc;
-    return pcg_solve_impl(row_ptr, col, vals, rhs, n_nodes, pcg_iters, lm_abs, lm_rel, x_out, pcg_workspace, pcg_workspace_bytes, node_dq,
-                          step, stream, zeroed);
-}
-
-int dfh_gn_iteration(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                     double *corr_out, unsigned char *valid_out, int n_samples, int knn, double *node_dq,
-                     const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                     const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                     double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                     const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                     const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                     const float *depth, int H, int W, const double K[9], const double Kinv[9], const double lw_cam[12],
-                     double scale, const double center[3], double half, double max_dist,
-                     int pcg_iters, double lm_abs, double lm_rel, double *x_out, void *pcg_workspace, size_t pcg_workspace_bytes,
-                     double step, void *stream) {
-    return gn_iteration_impl("dfh_gn_iteration", sample_pos, sample_nrm, nbr, weights, corr_out, valid_out, n_samples, knn, node_dq, node_pos,
-                             node_w, node_nbr, n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs, cost_count, run_id, n_rows, partial, blk_ptr,
-                             blk_ent, node_ptr, node_ent, partial_reg, rblk_ptr, rblk_ent, rnode_ptr, rnode_ent, huber_delta, depth, nullptr, 0,
-                             H, W, K, Kinv, lw_cam, scale, center, half, max_dist, pcg_iters, lm_abs, lm_rel, x_out, pcg_workspace,
-                             pcg_workspace_bytes, step, stream);
-}
-
-int dfh_gn_iteration_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                     double *corr_out, unsigned char *valid_out, int n_samples, int knn, double *node_dq,
-                     const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                     const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                     double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                     const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                     const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                     const void *views, int n_views, int H, int W, const double K[9], const double Kinv[9],
-                     double scale, const double center[3], double half, double max_dist,
-                     int pcg_iters, double lm_abs, double lm_rel, double *x_out, void *pcg_workspace, size_t pcg_workspace_bytes,
-                     double step, int n_iters, const int *blk_upper, int n_upper, void *stream) {
-    using namespace dfh;
-    DFH_REQUIRE(views && n_views >= 1 && n_views <= DFH_GN_MAX_VIEWS, "dfh_gn_iteration_views: needs 1..%d packed views", DFH_GN_MAX_VIEWS);
-    DFH_REQUIRE(n_upper >= 0 && n_upper <= n_blocks && (n_upper == 0 || blk_upper), "dfh_gn_iteration_views: bad upper-block list");
-    DFH_REQUIRE(n_iters >= 0 && n_iters <= 1000, "dfh_gn_iteration_views: %d iterations", n_iters);
-    // the frame's iterations are queued back to back from here: nothing between them depends on the host
-    for (int it = 0; it < n_iters; ++it) {
-        const int rc = gn_iteration_impl("dfh_gn_iteration_views", sample_pos, sample_nrm, nbr, weights, corr_out, valid_out, n_samples, knn, node_dq,
-                                         node_pos, node_w, node_nbr, n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs, cost_count, run_id, n_rows,
-                                         partial, blk_ptr, blk_ent, node_ptr, node_ent, partial_reg, rblk_ptr, rblk_ent, rnode_ptr, rnode_ent,
-                                         huber_delta, nullptr, views, n_views, H, W, K, Kinv, kIdentity34, scale, center, half, max_dist,
-                                         pcg_iters, lm_abs, lm_rel, x_out, pcg_workspace, pcg_workspace_bytes, step, stream, blk_upper, n_upper);
+    pcg_zero_range(sp.pcg_workspace, q.n_nodes, sp.pcg_iters, &zbegin, &zcount);
+    for (int it = 0; it < sp.n_iters; ++it) {
+        bool zeroed = false;
+        rc = gn_build_impl(q, &aa, stream, on(opt().gn_iter_own_clear) ? nullptr : zbegin, zcount, &zeroed);
+        if (rc != DFH_OK) return rc;
+        rc = pcg_solve_impl(q.row_ptr, q.col, q.vals, q.rhs, q.n_nodes, sp.pcg_iters, sp.lm_abs, sp.lm_rel, sp.x_out, sp.pcg_workspace,
+                            sp.pcg_workspace_bytes, q.node_dq, sp.step, stream, zeroed);
         if (rc != DFH_OK) return rc;
     }
     return DFH_OK;
-}
-
-// A frame's whole solve behind one call (round 4): n_global rigid-mode steps (build + dfh_gn_global_step each), then n_iters
-// node iterations (dfh_gn_iteration_views).  The same launches in the same order as the separate calls: the same bits; what it
-// saves is the host's way through the binding, twice per rigid-mode step.
-int dfh_gn_frame_solve_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                     double *corr_out, unsigned char *valid_out, int n_samples, int knn, double *node_dq,
-                     const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                     const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                     double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                     const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                     const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                     const void *views, int n_views, int H, int W, const double K[9], const double Kinv[9],
-                     double scale, const double center[3], double half, double max_dist,
-                     int pcg_iters, double lm_abs, double lm_rel, double *x_out, void *pcg_workspace, size_t pcg_workspace_bytes,
-                     double step, int n_iters, const int *blk_upper, int n_upper,
-                     int n_global, double global_lm, double *global_xi_out, void *global_scratch, size_t global_scratch_bytes, void *stream) {
-    using namespace dfh;
-    DFH_REQUIRE(views && n_views >= 1 && n_views <= DFH_GN_MAX_VIEWS, "dfh_gn_frame_solve_views: needs 1..%d packed views", DFH_GN_MAX_VIEWS);
-    DFH_REQUIRE(n_global >= 0 && n_global <= 100, "dfh_gn_frame_solve_views: %d rigid-mode steps", n_global);
-    if (n_global > 0) {
-        DFH_REQUIRE(blk_ptr && K && Kinv && center && lw_dq && corr_out && valid_out && node_dq, "dfh_gn_frame_solve_views: null pointer");
-        DFH_REQUIRE(H >= 2 && W >= 2 && scale != 0.0, "dfh_gn_frame_solve_views: bad depth map / scale");
-        AssocArgs aa;
-        int rc = fill_assoc_params(aa.ap, lw_dq, H, W, K, Kinv, kIdentity34, scale, center, half, max_dist, knn);
-        if (rc != DFH_OK) return rc;
-        aa.depth = nullptr;
-        aa.views = static_cast<const AssocView *>(views);
-        aa.n_views = n_views;
-        aa.cull = n_views >= 4 && !on(opt().gn_no_view_cull) ? 1 : 0;
-        for (int g = 0; g < n_global; ++g) {
-            rc = gn_build_impl(sample_pos, sample_nrm, nbr, weights, corr_out, valid_out, n_samples, knn, node_dq, node_pos, node_w, node_nbr,
-                               n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs, cost_count, run_id, n_rows, partial, blk_ptr,
-                               blk_ent, node_ptr, node_ent, partial_reg, rblk_ptr, rblk_ent, rnode_ptr, rnode_ent, huber_delta, stream, &aa,
-                               nullptr, 0, nullptr, blk_upper, n_upper);
-            if (rc != DFH_OK) return rc;
-            rc = dfh_gn_global_step(vals, n_blocks, rhs, n_nodes, global_lm, node_dq, global_xi_out, global_scratch, global_scratch_bytes, stream);
-            if (rc != DFH_OK) return rc;
-        }
-    }
-    return dfh_gn_iteration_views(sample_pos, sample_nrm, nbr, weights, corr_out, valid_out, n_samples, knn, node_dq, node_pos, node_w, node_nbr,
-                                  n_nodes, lw_dq, rw, row_ptr, col, n_blocks, vals, rhs, cost_count, run_id, n_rows, partial, blk_ptr, blk_ent,
-                                  node_ptr, node_ent, partial_reg, rblk_ptr, rblk_ent, rnode_ptr, rnode_ent, huber_delta, views, n_views, H, W,
-                                  K, Kinv, scale, center, half, max_dist, pcg_iters, lm_abs, lm_rel, x_out, pcg_workspace, pcg_workspace_bytes,
-                                  step, n_iters, blk_upper, n_upper, stream);
 }
 
 // J^T J is symmetric: block (b, a) is the transpose of block (a, b).  Between ranks only the blocks with col >= row travel
@@ -3762,48 +3545,40 @@ int dfh_gn_global_apply(const double *sums29, double lm_rel, int n_nodes, double
     return DFH_OK;
 }
 
-int dfh_gn_global_sampled_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights, int n_samples, int knn,
-                                double *node_dq, int n_nodes, const double lw_dq[8], double huber_delta, const void *views, int n_views,
-                                int depth_dtype, int H, int W, const double K[9], const double Kinv[9], double scale, const double center[3],
-                                double half, double max_dist, int stride, double lm_rel, int n_steps, double *xi_out, double *sums_out,
-                                void *scratch, size_t scratch_bytes, void *stream) {
+int dfh_gn_global_sampled(const dfh_gn_problem *problem, const dfh_gn_frame *frame, int stride, double lm_rel, int n_steps,
+                          double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream) {
     using namespace dfh;
-    DFH_REQUIRE(n_steps >= 0 && n_steps <= 100 && stride >= 1, "dfh_gn_global_sampled_views: %d steps, stride %d", n_steps, stride);
+    DFH_REQUIRE(n_steps >= 0 && n_steps <= 100 && stride >= 1, "dfh_gn_global_sampled: %d steps, stride %d", n_steps, stride);
     if (n_steps == 0) return DFH_OK;
-    DFH_REQUIRE(n_samples >= 0 && node_dq && lw_dq && views && K && Kinv && center && scratch, "dfh_gn_global_sampled_views: null pointer");
-    DFH_REQUIRE(n_samples == 0 || (sample_pos && sample_nrm && nbr && weights), "dfh_gn_global_sampled_views: null sample array");
-    DFH_REQUIRE(knn >= 1 && knn <= 8, "dfh_gn_global_sampled_views: knn = %d (1..8)", knn);
-    DFH_REQUIRE(depth_dtype == DFH_F32 || depth_dtype == DFH_F64, "dfh_gn_global_sampled_views: bad depth_dtype");
-    DFH_REQUIRE(n_views >= 1 && n_views <= DFH_GN_MAX_VIEWS && n_nodes >= 1 && lm_rel >= 0.0 && huber_delta >= 0.0, "dfh_gn_global_sampled_views: bad arguments");
-    DFH_REQUIRE(scratch_bytes >= dfh_gn_global_sampled_bytes(n_samples, stride), "dfh_gn_global_sampled_views: scratch too small");
-    DFH_REQUIRE(!sums_out || n_steps == 1, "dfh_gn_global_sampled_views: sums_out (the caller reduces over ranks and applies) takes one step per call");
-    AssocArgs aa;
-    const int rc = fill_assoc_params(aa.ap, lw_dq, H, W, K, Kinv, kIdentity34, scale, center, half, max_dist, knn);
+    int rc = check_problem("dfh_gn_global_sampled", problem, false);
+    if (rc == DFH_OK) rc = check_frame("dfh_gn_global_sampled", frame, false);
     if (rc != DFH_OK) return rc;
-    aa.depth = nullptr;
-    aa.views = static_cast<const AssocView *>(views);
-    aa.n_views = n_views;
-    aa.cull = 0;
+    const dfh_gn_problem &q = *problem;
+    const int n_samples = q.n_samples, knn = q.knn, n_nodes = q.n_nodes;
+    DFH_REQUIRE(scratch && lm_rel >= 0.0, "dfh_gn_global_sampled: bad arguments");
+    DFH_REQUIRE(scratch_bytes >= dfh_gn_global_sampled_bytes(n_samples, stride), "dfh_gn_global_sampled: scratch too small");
+    DFH_REQUIRE(!sums_out || n_steps == 1, "dfh_gn_global_sampled: sums_out (the caller reduces over ranks and applies) takes one step per call");
+    const AssocArgs aa = assoc_args(q, *frame, false);
     BuildParams bp;
-    for (int i = 0; i < 8; ++i) bp.lw.q[i] = lw_dq[i];
-    bp.S = n_samples; bp.k = knn; bp.N = n_nodes; bp.huber = huber_delta;
+    for (int i = 0; i < 8; ++i) bp.lw.q[i] = q.lw_dq[i];
+    bp.S = n_samples; bp.k = knn; bp.N = n_nodes; bp.huber = q.huber_delta;
     const long n_tiles = (n_samples + kTile - 1) / kTile;
     const long n_sub = (n_tiles + stride - 1) / stride;
     const int n_wg = (int)std::min<long>(n_sub, kGlobalGrid);
     double *tile_part = static_cast<double *>(scratch);
     double *sums = sums_out ? sums_out : tile_part + (size_t)kGlobalVals * kGlobalGrid;
     hipStream_t st = (hipStream_t)stream;
-    const bool f64 = depth_dtype == DFH_F64;
+    const bool f64 = frame->depth_dtype == DFH_F64;
     for (int g = 0; g < n_steps; ++g) {
         if (n_wg > 0) {
 #define DFH_GLOBAL_ROWS(KK)                                                                                                        \
     case KK:                                                                                                                       \
         if (f64)                                                                                                                   \
-            hipLaunchKernelGGL((gn_global_rows_kernel<KK, double>), dim3((unsigned)n_wg), dim3(kTile), 0, st, sample_pos, sample_nrm, \
-                               nbr, weights, (const double *)node_dq, bp, stride, n_sub, tile_part, aa);                            \
+            hipLaunchKernelGGL((gn_global_rows_kernel<KK, double>), dim3((unsigned)n_wg), dim3(kTile), 0, st, q.sample_pos, q.sample_nrm, \
+                               q.nbr, q.weights, (const double *)q.node_dq, bp, stride, n_sub, tile_part, aa);                            \
         else                                                                                                                       \
-            hipLaunchKernelGGL((gn_global_rows_kernel<KK, float>), dim3((unsigned)n_wg), dim3(kTile), 0, st, sample_pos, sample_nrm, \
-                               nbr, weights, (const double *)node_dq, bp, stride, n_sub, tile_part, aa);                            \
+            hipLaunchKernelGGL((gn_global_rows_kernel<KK, float>), dim3((unsigned)n_wg), dim3(kTile), 0, st, q.sample_pos, q.sample_nrm, \
+                               q.nbr, q.weights, (const double *)q.node_dq, bp, stride, n_sub, tile_part, aa);                            \
         break
             switch (knn) {
                 DFH_GLOBAL_ROWS(1); DFH_GLOBAL_ROWS(2); DFH_GLOBAL_ROWS(3); DFH_GLOBAL_ROWS(4);
@@ -3811,8 +3586,8 @@ int dfh_gn_global_sampled_views(const double *sample_pos, const double *sample_n
             }
 #undef DFH_GLOBAL_ROWS
         }
-        if (sums_out) hipLaunchKernelGGL(gn_global_finish_kernel<false>, dim3(1), dim3(1024), 0, st, (const double *)tile_part, n_wg, sums, lm_rel, n_nodes, node_dq, xi_out);
-        else hipLaunchKernelGGL(gn_global_finish_kernel<true>, dim3(1), dim3(1024), 0, st, (const double *)tile_part, n_wg, sums, lm_rel, n_nodes, node_dq, xi_out);
+        if (sums_out) hipLaunchKernelGGL(gn_global_finish_kernel<false>, dim3(1), dim3(1024), 0, st, (const double *)tile_part, n_wg, sums, lm_rel, n_nodes, q.node_dq, xi_out);
+        else hipLaunchKernelGGL(gn_global_finish_kernel<true>, dim3(1), dim3(1024), 0, st, (const double *)tile_part, n_wg, sums, lm_rel, n_nodes, q.node_dq, xi_out);
     }
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;

@@ -74,7 +74,7 @@ def SE3TDQ(M):
 # ---- the reference's small helpers beside its DQ algebra (core/util.py) ------------------------------------------
 def huber_loss(x, c):
     """Huber's rho of core/util.py:50-54: x^2 / 2 up to |x| = c, c (|x| - c / 2) beyond; scalars or arrays.  (The solver
-    applies it as IRLS weights on the data rows: dfh_gn_build_planned's huber_delta.)"""
+    applies it as IRLS weights on the data rows: dfh_gn_problem's huber_delta.)"""
     a = np.abs(x)
     return np.where(a <= c, 0.5 * np.square(x), c * (a - 0.5 * c)) if np.ndim(x) else (0.5 * x * x if a <= c else c * (a - 0.5 * c))
 

@@ -301,7 +301,7 @@ class SlabFrame:
         R = self.R
         # `depth` / `lw_cam` may be lists: the live volume is then fused from all of them (as the reference's
         # compute_live_tsdf does, core/fusion_dm.py:166-170) and the warp solve associates every sample against all of them
-        # (the view in which it lies closest to the observed surface: dfh_gn_associate_views; data_views=1 keeps round 2's
+        # (the view in which it lies closest to the observed surface: dfh_gn_associate; data_views=1 keeps round 2's
         # first-view-only data term)
         depth_list = list(depth) if isinstance(depth, (list, tuple)) else [depth]
         lw_list = list(lw_cam) if isinstance(depth, (list, tuple)) else [lw_cam]

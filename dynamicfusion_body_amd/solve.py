@@ -237,6 +237,7 @@ class WarpSolver:
                                                   # (tools/rccl_capture_check.py: the RCCL path rehearsed on a one-GPU box)
         self.node_nbr = None
         self.S = 0
+        self._prob, self._frm, self._sp = _lib.Problem(), _lib.Frame(), _lib.SolveParams()     # the C ABI's structs, refilled per call
         if _dist.ranks_share_a_gpu():                  # (whether or not THIS solver runs collectives: ADVICE round 2)
             # several processes time-share this GPU (a rehearsal of the multi-GPU job on one card): co-residency of the
             # persistent PCG's workgroups is not guaranteed across processes -> two launches per iteration, no grid barrier
@@ -417,7 +418,7 @@ class WarpSolver:
         self.vals = self.system[:self.B * 36]
         self.rhs = self.system[self.B * 36:self.B * 36 + 6 * N]
         self.cost_count = self.system[self.B * 36 + 6 * N:]
-        # the pattern's symmetry for the gather (dfh_gn_iteration_views: blk_upper): per block with col >= row its index and its
+        # the pattern's symmetry for the gather (dfh_gn_problem.blk_upper): per block with col >= row its index and its
         # mirror block's (-1 on the diagonal); only those blocks' lists are walked, every sum is stored twice
         upper_m = self.col >= rows
         mkey_s = self.col.to(torch.int64) * N + rows.to(torch.int64)
@@ -446,7 +447,7 @@ class WarpSolver:
         self._pattern = True
 
     def _build_plan(self, keys, reg=True, overlap=()):
-        """Static part of the data term (dfh_gn_build_planned): rows = runs of equal node tuples inside a
+        """Static part of the data term (the planned dfh_gn_build): rows = runs of equal node tuples inside a
         256-sample tile, and for every block / node the rows (and tuple slots) that contribute to it.
         reg=False keeps the regularisation lists (they depend on the pattern and the graph only).
         The data plan is built on the device (dfh_gn_plan_count / dfh_gn_plan_build: run scan, block look-up, two radix
@@ -574,22 +575,46 @@ class WarpSolver:
             v = v.to(device="cuda", dtype=torch.uint8)
             self.valid = v[self._order_index()].contiguous() if self.order is not None else v.contiguous()
 
-    # -- several live views -----------------------------------------------------------------
+    # -- the C ABI's problem and frame ---------------------------------------------------------
+    _PROBLEM_TENSORS = (("sample_pos", "spos"), ("sample_nrm", "snrm"), ("nbr", "snbr"), ("weights", "swts"), ("corr", "corr"),
+                        ("valid", "valid"), ("node_dq", "node_dq"), ("node_pos", "node_pos"), ("node_w", "node_w"),
+                        ("row_ptr", "row_ptr"), ("col", "col"), ("vals", "vals"), ("rhs", "rhs"), ("cost_count", "cost_count"),
+                        ("blk_upper", "blk_upper"), ("run_id", "run_id"), ("partial", "partial"), ("blk_ptr", "blk_ptr"),
+                        ("blk_ent", "blk_ent"), ("node_ptr", "node_ptr"), ("node_ent", "node_ent"), ("partial_reg", "partial_reg"),
+                        ("rblk_ptr", "rblk_ptr"), ("rblk_ent", "rblk_ent"), ("rnode_ptr", "rnode_ptr"), ("rnode_ent", "rnode_ent"))
+
+    def _problem(self, lw_dq, rw=0.0, huber=0.0, reg=True, plan=True, upper=True):
+        """The solver's dfh_gn_problem, filled from its tensors on every call (set_correspondences, set_graph and a pattern
+        rebuild replace them; what does not exist yet -- the pattern before the first build -- is NULL).  reg: the regulariser
+        rows (node_nbr, when rw != 0); plan=False: the atomic build; upper=False: the gather walks every block."""
+        p = self._prob
+        for field, attr in self._PROBLEM_TENSORS:
+            t = getattr(self, attr, None)
+            setattr(p, field, 0 if t is None else t.data_ptr())
+        p.n_samples, p.knn, p.n_nodes = self.S, self.knn, self.N
+        p.node_nbr = self.node_nbr.data_ptr() if (reg and self.node_nbr is not None and rw != 0.0) else 0
+        p.lw_dq, p.rw, p.huber_delta = _lib.darr(lw_dq, 8), float(rw), float(huber)
+        p.n_blocks, p.n_rows = getattr(self, "B", 0), getattr(self, "n_rows", 0)
+        p.n_upper = self.n_upper if upper and p.blk_upper else 0
+        if not upper:
+            p.blk_upper = 0
+        if not plan:
+            p.blk_ptr = 0
+        return p
+
     @staticmethod
-    def _one_or_many(depth, lw_cam):
-        """(depth, lw_cam) of a single view, or (list of depths, list of extrinsics) with more than one entry."""
+    def _views(depth, lw_cam):
+        """(depth, lw_cam) of one view, or (list of depths, list of extrinsics) -> (list of depths, list of extrinsics)."""
         if isinstance(depth, (list, tuple)):
             depths, lws = list(depth), list(lw_cam)
             if len(depths) != len(lws) or not depths:
                 raise ValueError('length of camera matrix array must equal that of depth maps')
-            if len(depths) == 1:
-                return depths[0], lws[0], False
-            return depths, lws, True
-        return depth, lw_cam, False
+            return depths, lws
+        return [depth], [lw_cam]
 
     def _views_table(self, depths, lw_cams):
         """Device table of a frame's views (dfh_gn_pack_views: extrinsics, their inverses, depth pointers; float32 maps: also the
-        16 x 16-pixel cells' depth ranges, dfh_gn_pack_views_cells), rebuilt only when the depth tensors, their contents or the
+        16 x 16-pixel cells' depth ranges), rebuilt only when the depth tensors, their contents or the
         extrinsics change (a frame's iterations share it).  Contents: the key holds every tensor's version counter, which torch
         bumps on each in-place write (copy_, fill_, indexing assignment, out= ops); writes that bypass torch -- a kernel or a
         copy through the raw data_ptr -- are not seen, and such a caller must pass new tensors.  Returns (table, n_views, H, W)."""
@@ -605,44 +630,30 @@ class WarpSolver:
         if getattr(self, "_views_key", None) != key:
             ptrs = (ctypes.c_void_p * n)(*[int(d.data_ptr()) for d in depths])
             Hh, Ww = (int(v) for v in depths[0].shape)
-            if depths[0].dtype == torch.float32:
-                # with the per-view depth-cell tables: the fused build drops, per tile, the views that cannot hold a correspondence
-                nbytes = self.lib.dfh_gn_views_bytes_cells(n, Hh, Ww)
-                buf = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-                _lib.check(self.lib.dfh_gn_pack_views_cells(buf.data_ptr(), n, ptrs, Hh, Ww, lw.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                            current_stream_ptr()), "dfh_gn_pack_views_cells")
-            else:
-                nbytes = self.lib.dfh_gn_views_bytes(n)
-                buf = torch.empty(nbytes, dtype=torch.uint8, device="cuda")
-                _lib.check(self.lib.dfh_gn_pack_views(buf.data_ptr(), n, ptrs, lw.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                      current_stream_ptr()), "dfh_gn_pack_views")
+            dt = dtype_code(depths[0])
+            buf = torch.empty(self.lib.dfh_gn_views_bytes(n, dt, Hh, Ww), dtype=torch.uint8, device="cuda")
+            _lib.check(self.lib.dfh_gn_pack_views(buf.data_ptr(), n, ptrs, dt, Hh, Ww, lw.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                  current_stream_ptr()), "dfh_gn_pack_views")
             self._views_key, self._views_buf, self._views_keep = key, buf, list(depths)
         H, W = depths[0].shape
         return self._views_buf, n, int(H), int(W)
 
+    def _frame(self, depth, lw_cam, K, Kinv, scale, center, half, max_dist):
+        """The live frame (one view or lists of views) as a dfh_gn_frame, through the cached views' table."""
+        depths, lws = self._views(depth, lw_cam)
+        tab, n, H, W = self._views_table(depths, lws)
+        f = self._frm
+        f.views, f.n_views, f.depth_dtype, f.H, f.W = tab.data_ptr(), n, dtype_code(depths[0]), H, W
+        f.K, f.Kinv, f.center = _lib.darr(K, 9), _lib.darr(Kinv, 9), _lib.darr(center, 3)
+        f.scale, f.half, f.max_dist = float(scale), float(half), float(max_dist)
+        return f
+
     def associate_depth(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist=0.0):
         """Projective association of the warped samples against a live depth map (CUDA tensor) -- or against several
         (lists of depth maps and extrinsics): each sample keeps the correspondence of the view in which it lies closest to
-        the observed surface (dfh_gn_associate_views)."""
-        depth, lw_cam, many = self._one_or_many(depth, lw_cam)
-        if many:
-            tab, n, H, W = self._views_table(depth, lw_cam)
-            _lib.check(self.lib.dfh_gn_associate_views(self.spos.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(), self.S, self.knn,
-                                                       self.node_dq.data_ptr(), _lib.darr(lw_dq, 8), tab.data_ptr(), n, dtype_code(depth[0]),
-                                                       H, W, _lib.darr(K, 9), _lib.darr(Kinv, 9), float(scale),
-                                                       _lib.darr(np.asarray(center, dtype=np.float64), 3), float(half), float(max_dist),
-                                                       self.corr.data_ptr(), self.valid.data_ptr(), current_stream_ptr()),
-                       "dfh_gn_associate_views")
-            return
-        if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dim() == 2 and depth.is_contiguous()):
-            raise ValueError("depth must be a contiguous 2-D CUDA tensor")
-        H, W = depth.shape
-        _lib.check(self.lib.dfh_gn_associate(self.spos.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(), self.S, self.knn,
-                                             self.node_dq.data_ptr(), _lib.darr(lw_dq, 8), depth.data_ptr(), dtype_code(depth),
-                                             int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), _lib.darr(lw_cam, 12),
-                                             float(scale), _lib.darr(np.asarray(center, dtype=np.float64), 3), float(half),
-                                             float(max_dist), self.corr.data_ptr(), self.valid.data_ptr(),
-                                             current_stream_ptr()), "dfh_gn_associate")
+        the observed surface (dfh_gn_associate)."""
+        frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        _lib.check(self.lib.dfh_gn_associate(self._problem(lw_dq), frame, current_stream_ptr()), "dfh_gn_associate")
 
     # -- iteration ---------------------------------------------------------------------------
     def build(self, lw_dq, rw, huber=0.0):
@@ -652,137 +663,63 @@ class WarpSolver:
         # data rows are sharded with the samples; the regularisation rows (one per node pair) are
         # not, so exactly one rank adds them before the all-reduce
         reg_here = (not self.distributed) or _dist.world()[0] == 0
-        nn = 0 if (self.node_nbr is None or rw == 0.0 or not reg_here) else self.node_nbr.data_ptr()
-        if _lib.opt_on("py_gn_atomic"):          # the atomics-based build (no plan needed), kept for A/B comparison
-            if huber > 0.0:
-                raise ValueError("the atomic build (py_gn_atomic) has no Huber weights")
-            _lib.check(self.lib.dfh_gn_build(self.spos.data_ptr(), self.snrm.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(),
-                                             self.corr.data_ptr(), self.valid.data_ptr(), self.S, self.knn,
-                                             self.node_dq.data_ptr(), self.node_pos.data_ptr(), self.node_w.data_ptr(), nn, self.N,
-                                             _lib.darr(lw_dq, 8), float(rw), self.row_ptr.data_ptr(), self.col.data_ptr(), self.B,
-                                             self.vals.data_ptr(), self.rhs.data_ptr(), self.cost_count.data_ptr(),
-                                             current_stream_ptr()), "dfh_gn_build")
-        else:
-            _lib.check(self.lib.dfh_gn_build_planned(
-                self.spos.data_ptr(), self.snrm.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(), self.corr.data_ptr(),
-                self.valid.data_ptr(), self.S, self.knn, self.node_dq.data_ptr(), self.node_pos.data_ptr(), self.node_w.data_ptr(),
-                nn, self.N, _lib.darr(lw_dq, 8), float(rw), self.row_ptr.data_ptr(), self.col.data_ptr(), self.B,
-                self.vals.data_ptr(), self.rhs.data_ptr(), self.cost_count.data_ptr(), self.run_id.data_ptr(), self.n_rows,
-                self.partial.data_ptr(), self.blk_ptr.data_ptr(), self.blk_ent.data_ptr(), self.node_ptr.data_ptr(),
-                self.node_ent.data_ptr(), *((self.partial_reg.data_ptr(), self.rblk_ptr.data_ptr(), self.rblk_ent.data_ptr(),
-                                             self.rnode_ptr.data_ptr(), self.rnode_ent.data_ptr())
-                                            if self.partial_reg is not None else (0, 0, 0, 0, 0)),
-                float(huber), current_stream_ptr()), "dfh_gn_build_planned")
+        atomic = _lib.opt_on("py_gn_atomic")      # the atomics-based build (no plan needed), kept for A/B comparison
+        if atomic and huber > 0.0:
+            raise ValueError("the atomic build (py_gn_atomic) has no Huber weights")
+        _lib.check(self.lib.dfh_gn_build(self._problem(lw_dq, rw, huber, reg=reg_here, plan=not atomic, upper=False), None,
+                                         current_stream_ptr()), "dfh_gn_build")
         self._allreduce_system()                  # no-op on one GPU; samples are sharded by slab
 
     def build_associated(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist=0.0, huber=0.0):
-        """associate_depth + build in one launch sequence (dfh_gn_build_planned_assoc): same corr / valid, same system, bit
+        """associate_depth + build in one launch sequence (dfh_gn_build with a frame): same corr / valid, same system, bit
         for bit; float32 depth maps and the planned build only (otherwise the two calls are made)."""
         if self._pattern is None:
             self._build_pattern()
-        depth, lw_cam, many = self._one_or_many(depth, lw_cam)
-        d0 = depth[0] if many else depth
-        fused = (isinstance(d0, torch.Tensor) and d0.is_cuda and d0.dim() == 2 and d0.is_contiguous() and
-                 d0.dtype == torch.float32 and self.S > 0 and not _lib.opt_on("py_gn_atomic") and not _lib.opt_on("py_gn_no_fused_assoc"))
-        if not fused:
+        frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        if (frame.depth_dtype != _lib.F32 or self.S == 0 or _lib.opt_on("py_gn_atomic") or _lib.opt_on("py_gn_no_fused_assoc")):
             self.associate_depth(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist)
             return self.build(lw_dq, rw, huber)
         reg_here = (not self.distributed) or _dist.world()[0] == 0
-        nn = 0 if (self.node_nbr is None or rw == 0.0 or not reg_here) else self.node_nbr.data_ptr()
-        if many:
-            tab, nv, H, W = self._views_table(depth, lw_cam)
-            _lib.check(self.lib.dfh_gn_build_planned_assoc_views(
-                self.spos.data_ptr(), self.snrm.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(), self.corr.data_ptr(),
-                self.valid.data_ptr(), self.S, self.knn, self.node_dq.data_ptr(), self.node_pos.data_ptr(), self.node_w.data_ptr(),
-                nn, self.N, _lib.darr(lw_dq, 8), float(rw), self.row_ptr.data_ptr(), self.col.data_ptr(), self.B,
-                self.vals.data_ptr(), self.rhs.data_ptr(), self.cost_count.data_ptr(), self.run_id.data_ptr(), self.n_rows,
-                self.partial.data_ptr(), self.blk_ptr.data_ptr(), self.blk_ent.data_ptr(), self.node_ptr.data_ptr(),
-                self.node_ent.data_ptr(), *((self.partial_reg.data_ptr(), self.rblk_ptr.data_ptr(), self.rblk_ent.data_ptr(),
-                                             self.rnode_ptr.data_ptr(), self.rnode_ent.data_ptr())
-                                            if self.partial_reg is not None else (0, 0, 0, 0, 0)),
-                float(huber), tab.data_ptr(), nv, H, W, _lib.darr(K, 9), _lib.darr(Kinv, 9), float(scale),
-                _lib.darr(np.asarray(center, dtype=np.float64), 3), float(half), float(max_dist),
-                self.blk_upper.data_ptr() if self.blk_upper is not None else 0, self.n_upper, current_stream_ptr()),
-                "dfh_gn_build_planned_assoc_views")
-            self._allreduce_system()
-            return
-        H, W = depth.shape
-        _lib.check(self.lib.dfh_gn_build_planned_assoc(
-            self.spos.data_ptr(), self.snrm.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(), self.corr.data_ptr(),
-            self.valid.data_ptr(), self.S, self.knn, self.node_dq.data_ptr(), self.node_pos.data_ptr(), self.node_w.data_ptr(),
-            nn, self.N, _lib.darr(lw_dq, 8), float(rw), self.row_ptr.data_ptr(), self.col.data_ptr(), self.B,
-            self.vals.data_ptr(), self.rhs.data_ptr(), self.cost_count.data_ptr(), self.run_id.data_ptr(), self.n_rows,
-            self.partial.data_ptr(), self.blk_ptr.data_ptr(), self.blk_ent.data_ptr(), self.node_ptr.data_ptr(),
-            self.node_ent.data_ptr(), *((self.partial_reg.data_ptr(), self.rblk_ptr.data_ptr(), self.rblk_ent.data_ptr(),
-                                         self.rnode_ptr.data_ptr(), self.rnode_ent.data_ptr())
-                                        if self.partial_reg is not None else (0, 0, 0, 0, 0)),
-            float(huber), depth.data_ptr(), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), _lib.darr(lw_cam, 12), float(scale),
-            _lib.darr(np.asarray(center, dtype=np.float64), 3), float(half), float(max_dist), current_stream_ptr()),
-            "dfh_gn_build_planned_assoc")
+        _lib.check(self.lib.dfh_gn_build(self._problem(lw_dq, rw, huber, reg=reg_here), frame, current_stream_ptr()), "dfh_gn_build")
         self._allreduce_system()
 
     def iterate_associated(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist=0.0, huber=0.0, lm_abs=0.0, lm_rel=0.0,
                            n_iters=1, n_global=0, global_lm=0.1):
-        """n_iters GN iterations: build_associated + solve_update each.  On one GPU (no all-reduce between the halves) they
-        are ONE call, dfh_gn_iteration_views (the views' table holds one or several depth maps): the iterations are queued
-        back to back without returning to Python, and in each the clearing of the solve's workspace rides in the data-row
-        launch -- the same bits as separate calls.  option py_gn_iter_per_call: one dfh_gn_iteration call per iteration (single
-        view), as before round 3."""
+        """n_global rigid-mode steps (build_associated + global_step each), then n_iters GN iterations (build_associated +
+        solve_update each).  On one GPU (no all-reduce between the halves) they are ONE call, dfh_gn_solve: the iterations are
+        queued back to back without returning to Python, and in each the clearing of the solve's workspace rides in the data-row
+        launch -- the same bits as separate calls.  option py_gn_iter_per_call: one dfh_gn_solve call per iteration."""
         if self._pattern is None:
             self._build_pattern()
-        depth, lw_cam, many = self._one_or_many(depth, lw_cam)
-        d0 = depth[0] if many else depth
-        one_call = (isinstance(d0, torch.Tensor) and d0.is_cuda and d0.dim() == 2 and d0.is_contiguous() and
-                    d0.dtype == torch.float32 and self.S > 0 and not _lib.opt_on("py_gn_atomic") and
+        frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        one_call = (frame.depth_dtype == _lib.F32 and self.S > 0 and not _lib.opt_on("py_gn_atomic") and
                     not _lib.opt_on("py_gn_no_fused_assoc") and not _lib.opt_on("py_gn_no_fused_iter") and
                     not (self.distributed and (_dist.world()[1] > 1 or self.force_collective)))
-        if not one_call:
+        per_call = one_call and _lib.opt_on("py_gn_iter_per_call")
+        if not one_call or per_call:
             for _ in range(int(n_global)):                # the rigid mode first (global_step): one twist for all nodes
                 self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber)
                 self.global_step(global_lm)
-            for _ in range(int(n_iters)):
-                self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber)
-                self.solve_update(lm_abs, lm_rel)
-            return
-        nn = 0 if (self.node_nbr is None or rw == 0.0) else self.node_nbr.data_ptr()
-        common = (self.spos.data_ptr(), self.snrm.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(), self.corr.data_ptr(),
-                  self.valid.data_ptr(), self.S, self.knn, self.node_dq.data_ptr(), self.node_pos.data_ptr(), self.node_w.data_ptr(),
-                  nn, self.N, _lib.darr(lw_dq, 8), float(rw), self.row_ptr.data_ptr(), self.col.data_ptr(), self.B,
-                  self.vals.data_ptr(), self.rhs.data_ptr(), self.cost_count.data_ptr(), self.run_id.data_ptr(), self.n_rows,
-                  self.partial.data_ptr(), self.blk_ptr.data_ptr(), self.blk_ent.data_ptr(), self.node_ptr.data_ptr(),
-                  self.node_ent.data_ptr(), *((self.partial_reg.data_ptr(), self.rblk_ptr.data_ptr(), self.rblk_ent.data_ptr(),
-                                               self.rnode_ptr.data_ptr(), self.rnode_ent.data_ptr())
-                                              if self.partial_reg is not None else (0, 0, 0, 0, 0)),
-                  float(huber))
-        tail = (self.pcg_iters, float(lm_abs), float(lm_rel), self.dx.data_ptr(), self.pcg_ws.data_ptr(), self.pcg_ws.numel() * 8, 1.0)
-        if not many and _lib.opt_on("py_gn_iter_per_call"):
-            for _ in range(int(n_global)):
-                self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber)
-                self.global_step(global_lm)
-            H, W = depth.shape
-            for _ in range(int(n_iters)):
-                _lib.check(self.lib.dfh_gn_iteration(
-                    *common, depth.data_ptr(), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), _lib.darr(lw_cam, 12), float(scale),
-                    _lib.darr(np.asarray(center, dtype=np.float64), 3), float(half), float(max_dist), *tail, current_stream_ptr()),
-                    "dfh_gn_iteration")
-            return
-        tab, nv, H, W = self._views_table(depth if many else [depth], lw_cam if many else [lw_cam])
-        if int(n_global) > 0:
+            if not one_call:
+                for _ in range(int(n_iters)):
+                    self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber)
+                    self.solve_update(lm_abs, lm_rel)
+                return
+            frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        sp = self._sp
+        sp.pcg_iters, sp.lm_abs, sp.lm_rel, sp.step = self.pcg_iters, float(lm_abs), float(lm_rel), 1.0
+        sp.x_out, sp.pcg_workspace, sp.pcg_workspace_bytes = self.dx.data_ptr(), self.pcg_ws.data_ptr(), self.pcg_ws.numel() * 8
+        sp.n_iters, sp.n_global, sp.global_lm = (1, 0, 0.0) if per_call else (int(n_iters), int(n_global), float(global_lm))
+        sp.global_xi_out = sp.global_scratch = sp.global_scratch_bytes = 0
+        if sp.n_global > 0:
             if getattr(self, "_global_ws", None) is None:
                 self._global_ws = torch.zeros((self.lib.dfh_gn_global_step_bytes() + 7) // 8, dtype=torch.float64, device="cuda")
                 self.global_xi = torch.zeros(8, dtype=torch.float64, device="cuda")
-            _lib.check(self.lib.dfh_gn_frame_solve_views(
-                *common, tab.data_ptr(), nv, H, W, _lib.darr(K, 9), _lib.darr(Kinv, 9), float(scale),
-                _lib.darr(np.asarray(center, dtype=np.float64), 3), float(half), float(max_dist), *tail, int(n_iters),
-                self.blk_upper.data_ptr() if self.blk_upper is not None else 0, self.n_upper, int(n_global), float(global_lm),
-                self.global_xi.data_ptr(), self._global_ws.data_ptr(), self._global_ws.numel() * 8, current_stream_ptr()),
-                "dfh_gn_frame_solve_views")
-            return
-        _lib.check(self.lib.dfh_gn_iteration_views(
-            *common, tab.data_ptr(), nv, H, W, _lib.darr(K, 9), _lib.darr(Kinv, 9), float(scale),
-            _lib.darr(np.asarray(center, dtype=np.float64), 3), float(half), float(max_dist), *tail, int(n_iters),
-            self.blk_upper.data_ptr() if self.blk_upper is not None else 0, self.n_upper, current_stream_ptr()),
-            "dfh_gn_iteration_views")
+            sp.global_xi_out, sp.global_scratch = self.global_xi.data_ptr(), self._global_ws.data_ptr()
+            sp.global_scratch_bytes = self._global_ws.numel() * 8
+        prob = self._problem(lw_dq, rw, huber)
+        for _ in range(int(n_iters) if per_call else 1):
+            _lib.check(self.lib.dfh_gn_solve(prob, frame, sp, current_stream_ptr()), "dfh_gn_solve")
 
     def _allreduce_system(self):
         """Sum of the normal equations over ranks, in place: the upper block triangle + J^T r + {cost, count} in one collective
@@ -814,31 +751,28 @@ class WarpSolver:
                    "dfh_pcg_solve")
 
     def global_sampled(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist=0.0, huber=0.0, lm_rel=0.1, n_steps=1, stride=1):
-        """n_steps rigid-mode steps straight from the samples (dfh_gn_global_sampled_views): ONE twist shared by all nodes, fitted
+        """n_steps rigid-mode steps straight from the samples (dfh_gn_global_sampled): ONE twist shared by all nodes, fitted
         to the data rows of every `stride`-th tile (no built system, no regulariser), applied to every node.  depth / lw_cam:
         one view or lists.  Samples sharded over ranks: the 29 sums are all-reduced, every rank applies the same twist.
         Asynchronous; self.global_xi holds the last step's twist | objective | valid count."""
-        depth, lw_cam, many = self._one_or_many(depth, lw_cam)
-        tab, nv, H, W = self._views_table(depth if many else [depth], lw_cam if many else [lw_cam])
+        frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
         if getattr(self, "global_xi", None) is None or self.global_xi.numel() < 8:
             self.global_xi = torch.zeros(8, dtype=torch.float64, device="cuda")
         nbytes = self.lib.dfh_gn_global_sampled_bytes(self.S, int(stride))
         if getattr(self, "_gs_ws", None) is None or self._gs_ws.numel() * 8 < nbytes:
             self._gs_ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device="cuda")
         sharded = self.distributed and (_dist.world()[1] > 1 or self.force_collective)
-        args = (self.spos.data_ptr(), self.snrm.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(), self.S, self.knn, self.node_dq.data_ptr(),
-                self.N, _lib.darr(lw_dq, 8), float(huber), tab.data_ptr(), nv, dtype_code(depth[0] if many else depth), H, W,
-                _lib.darr(K, 9), _lib.darr(Kinv, 9), float(scale),
-                _lib.darr(np.asarray(center, dtype=np.float64), 3), float(half), float(max_dist), int(stride), float(lm_rel))
+        prob = self._problem(lw_dq, huber=huber)
+        ws = (self._gs_ws.data_ptr(), self._gs_ws.numel() * 8, current_stream_ptr())
         if not sharded:
-            _lib.check(self.lib.dfh_gn_global_sampled_views(*args, int(n_steps), self.global_xi.data_ptr(), 0, self._gs_ws.data_ptr(),
-                                                            self._gs_ws.numel() * 8, current_stream_ptr()), "dfh_gn_global_sampled_views")
+            _lib.check(self.lib.dfh_gn_global_sampled(prob, frame, int(stride), float(lm_rel), int(n_steps), self.global_xi.data_ptr(), 0, *ws),
+                       "dfh_gn_global_sampled")
             return
         if getattr(self, "_gs_sums", None) is None:
             self._gs_sums = torch.zeros(32, dtype=torch.float64, device="cuda")
         for _ in range(int(n_steps)):
-            _lib.check(self.lib.dfh_gn_global_sampled_views(*args, 1, 0, self._gs_sums.data_ptr(), self._gs_ws.data_ptr(),
-                                                            self._gs_ws.numel() * 8, current_stream_ptr()), "dfh_gn_global_sampled_views")
+            _lib.check(self.lib.dfh_gn_global_sampled(prob, frame, int(stride), float(lm_rel), 1, 0, self._gs_sums.data_ptr(), *ws),
+                       "dfh_gn_global_sampled")
             _dist.allreduce_system(self._gs_sums, force=self.force_collective)
             _lib.check(self.lib.dfh_gn_global_apply(self._gs_sums.data_ptr(), float(lm_rel), self.N, self.node_dq.data_ptr(),
                                                     self.global_xi.data_ptr(), current_stream_ptr()), "dfh_gn_global_apply")

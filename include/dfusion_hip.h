@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DFH_ABI_VERSION 6
+#define DFH_ABI_VERSION 7
 
 #define DFH_F32 0
 #define DFH_F64 1
@@ -257,101 +257,117 @@ int dfh_graph_unsupported(const double *verts, int n_verts, const int *nbr, int 
 int dfh_dq_blend_points(const double *points, int n_points, const int *nbr, int knn, const double *node_dq, const double *node_pos,
                         const double *node_w, int n_nodes, double *dq_out, void *stream);
 
-/* Projective data association (not in the reference, which matches marching-cubes vertices through a
- * KD-tree, core/fusion.py:255-276): warp each sample with the current field (Fusion.warp), map index ->
- * world (pos = scale*(i - half) + center, fusion_dm.py:191) -> camera (lw_cam, :193) -> pixel (:194-195),
- * take the nearest depth pixel z = -depth[rint(v)][rint(u)] (:196), back-project K^-1 (z [u,v,1])
- * (:198-200) and map back to index space.  valid_out[s] = 0 when outside the image, no depth, or farther
- * than max_dist voxels from the warped sample (max_dist <= 0: no gate). */
 /* out[i] = in[order[i]] for the four per-sample arrays at once (samples are sorted by node tuple before the build:
  * few runs per tile of dfh_gn_tile_samples() samples).  order: n_samples int64 indices, a permutation. */
 int dfh_permute_samples(const long *order, int n_samples, int knn, const double *pos, const double *nrm, const int *nbr,
                         const double *weights, double *pos_out, double *nrm_out, int *nbr_out, double *weights_out, void *stream);
 
-int dfh_gn_associate(const double *sample_pos, const int *nbr, const double *weights, int n_samples, int knn,
-                     const double *node_dq, const double lw_dq[8], const void *depth, int depth_dtype, int H, int W,
-                     const double K[9], const double Kinv[9], const double lw_cam[12], double scale,
-                     const double center[3], double half, double max_dist, double *corr_out,
-                     unsigned char *valid_out, void *stream);
+/* The Gauss-Newton problem the solver owns: samples, nodes, term settings, the block system and the plans of its build.
+ * Gauss-Newton normal equations of 0.5*|computef|^2 in 6-DoF left twists (dq_a <- exp(xi_a) (x) dq_a): vals <- J^T J,
+ * rhs <- J^T r, cost_count[0] <- 0.5 |r|^2 (the Huber objective with huber_delta > 0), cost_count[1] <- valid samples. */
+typedef struct dfh_gn_problem {
+    /* samples, sorted by node tuple for the planned build: positions and normals (n_samples x 3), their knn nearest nodes
+     * (n_samples x knn int32) and static blend weights (dfh_sample_knn); corr (n_samples x 3, index space) / valid (uint8):
+     * inputs of a build without a frame, outputs of an association.  1 <= knn <= 8. */
+    const double *sample_pos, *sample_nrm;
+    const int *nbr;
+    const double *weights;
+    double *corr;
+    unsigned char *valid;
+    int n_samples, knn;
+    /* nodes: node_dq (n_nodes x 8, updated by dfh_gn_solve), positions (x 3), weights (the 4th tuple entry, 2*radius);
+     * node_nbr (n_nodes x knn int32; NULL: no regulariser rows) = _neighbor_look_up[_nodes[i][0]][j]. */
+    double *node_dq;
+    const double *node_pos, *node_w;
+    const int *node_nbr;
+    int n_nodes;
+    /* lw_dq: the rigid part `_lw`; rw: the regulariser weight (0: no regulariser rows); huber_delta > 0:
+     * every data row and its residual are scaled by sqrt(min(1, huber_delta / |r|)), the IRLS form of the Huber loss of the
+     * reference's solver (least_squares(loss='huber'), core/fusion.py:389); 0 = plain least squares. */
+    double lw_dq[8];
+    double rw, huber_delta;
+    /* the block system: vals (n_blocks x 36) in block-sparse rows row_ptr (n_nodes + 1) / col (sorted), rhs (6 n_nodes),
+     * cost_count (2).  The pattern must contain every node pair of every sample tuple and every (i, j) of node_nbr (both
+     * orders) plus the diagonal; missing blocks are silently dropped.  blk_upper (n_upper pairs of ints; NULL / 0: none): for
+     * every block with column >= row {its index, its mirror block's (column, row), -1 on the diagonal}; with it the gather walks
+     * only those blocks and stores every sum twice, the second time transposed: the same bits, half the walks. */
+    const int *row_ptr, *col;
+    int n_blocks;
+    double *vals, *rhs, *cost_count;
+    const int *blk_upper;
+    int n_upper;
+    /* the data plan (dfh_gn_plan_build; static while the samples are): a "row" = a maximal run of equal tuples inside one
+     * tile of dfh_gn_tile_samples() samples.  run_id[s] = row of sample s (n_rows rows); partial: scratch of
+     * n_rows x dfh_gn_partial_doubles(knn) + 2 x ceil(n_samples / dfh_gn_tile_samples()) + n_rows doubles; blk_ptr (n_blocks + 1)
+     * / blk_ent: per block the entries row * knn^2 + sa * knn + sb; node_ptr (n_nodes + 1) / node_ent: per node the entries
+     * row * knn + slot.  The tile pass stores each row's Gram matrix, J^T r, cost and count, a gather adds them per block: no
+     * floating-point atomics, the same bits every run.  blk_ptr == NULL: the data rows go to the blocks through atomics. */
+    const int *run_id;
+    int n_rows;
+    double *partial;
+    const int *blk_ptr, *blk_ent, *node_ptr, *node_ent;
+    /* the regulariser's plan: partial_reg (n_nodes * knn rows of dfh_gn_partial_doubles(2) doubles) and its lists, a pair
+     * (i, node_nbr[i*knn+slot]) being a 2-node row (entries row * 4 + sa * 2 + sb, row * 2 + slot).  partial_reg == NULL (or
+     * an atomic build) keeps the regulariser on atomics. */
+    double *partial_reg;
+    const int *rblk_ptr, *rblk_ent, *rnode_ptr, *rnode_ent;
+} dfh_gn_problem;
 
-/* Association against SEVERAL live views (BASELINE config 5: the live frame is eight depth maps).  Every view is tried in
- * turn with the arithmetic of dfh_gn_associate; a sample keeps the correspondence of the view in which it lies closest to
- * the observed surface (smallest |c - x'| among the views where it is valid; max_dist gates every view; ties go to the lower
- * view index), so it still contributes ONE data row and the block pattern / plan do not depend on the number of views.  One
- * view gives dfh_gn_associate's result bit for bit.  No reference counterpart (its correspondences are mesh-to-mesh,
- * core/fusion.py:255-276; its view loop is the TSDF fusion's, core/fusion_dm.py:166-170); oracle: gn_np.associate_depth_views.
- *   dfh_gn_pack_views writes the views' table (extrinsics, their inverses, depth pointers) into `views_out`, a device buffer
- *   of dfh_gn_views_bytes(n_views) bytes: once per frame; depth[v]: device pointers to H x W maps of one dtype; lw_cam: 12
- *   doubles per view (host).  The *_views calls take that table instead of (depth, lw_cam). */
+/* The live frame the data term is associated against (projective association, not in the reference, which matches
+ * marching-cubes vertices through a KD-tree, core/fusion.py:255-276): each sample is warped with the current field
+ * (Fusion.warp), mapped index -> world (pos = scale*(i - half) + center, fusion_dm.py:191) -> camera (the view's lw_cam,
+ * :193) -> pixel (:194-195); the nearest depth pixel z = -depth[rint(v)][rint(u)] (:196) is back-projected, K^-1 (z [u,v,1])
+ * (:198-200), and mapped back to index space.  A view gives no correspondence outside the image, without depth, or farther
+ * than max_dist voxels from the warped sample (max_dist <= 0: no gate).  With several views a sample keeps the view in which
+ * it lies closest to the observed surface (ties go to the lower view index): still ONE data row per sample.  Oracle:
+ * gn_np.associate_depth_views. */
+typedef struct dfh_gn_frame {
+    const void *views;       /* a dfh_gn_pack_views table (device) of n_views (1..DFH_GN_MAX_VIEWS) maps of depth_dtype */
+    int n_views, depth_dtype;
+    int H, W;                /* the maps' size, >= 2 each */
+    double K[9], Kinv[9];    /* intrinsics and their inverse, 3x3 row-major */
+    double scale;            /* index -> world: scale * (i - half) + center; scale != 0 */
+    double center[3];
+    double half;
+    double max_dist;         /* the distance gate in voxels (<= 0: none) */
+} dfh_gn_frame;
+
+/* One call's solve schedule (dfh_gn_solve). */
+typedef struct dfh_gn_solve_params {
+    int pcg_iters;                        /* the PCG of dfh_pcg_solve_update (>= 1) on the system of each iteration's build */
+    double lm_abs, lm_rel;
+    double *x_out;                        /* 6 n_nodes: the last iteration's step */
+    void *pcg_workspace;                  /* dfh_pcg_workspace_bytes(n_nodes, pcg_iters) bytes */
+    size_t pcg_workspace_bytes;
+    double step;                          /* node_dq <- exp(step * x) node_dq */
+    int n_iters;                          /* node iterations, 0..1000 */
+    int n_global;                         /* rigid-mode steps in front of them, 0..100 (dfh_gn_global_step(global_lm)) */
+    double global_lm;
+    double *global_xi_out;                /* may be NULL */
+    void *global_scratch;                 /* dfh_gn_global_step_bytes(), zeroed once by the caller */
+    size_t global_scratch_bytes;
+} dfh_gn_solve_params;
+
+/* The views' table of a frame, written into `out`, a device buffer of dfh_gn_views_bytes(n_views, depth_dtype, H, W) bytes,
+ * once per frame: extrinsics, their inverses, depth pointers.  depth[v]: host array of device pointers to H x W maps of
+ * depth_dtype; lw_cam: 12 doubles per view (host).  For DFH_F32 maps the table also holds, per view, the 16 x 16-pixel cells'
+ * {smallest, largest valid z = -depth}: with them the fused builds drop, per 128-sample tile, the views none of its samples can
+ * be valid in (the tile's warped box projects outside the image, or onto pixels whose valid depths all lie further than
+ * max_dist from the box's depth range; exact for rigid extrinsics and a pinhole K) -- the same corr / valid, the same bits
+ * (option gn_no_view_cull = 1 keeps every view).  DFH_F64 maps get no cells. */
 #define DFH_GN_MAX_VIEWS 16
-size_t dfh_gn_views_bytes(int n_views);
-int dfh_gn_pack_views(void *views_out, int n_views, const void *const *depth, const double *lw_cam, void *stream);
-/* The same table with, behind it, per view a table of 16 x 16-pixel cells {smallest, largest valid z = -depth} of FLOAT32 depth
- * maps (views_out: dfh_gn_views_bytes_cells(n_views, H, W) bytes).  With it the fused builds (dfh_gn_build_planned_assoc_views,
- * dfh_gn_iteration_views) drop, per 128-sample tile, the views none of its samples can be valid in -- the tile's warped samples'
- * box projects outside the image, or onto pixels whose valid depths all lie further than max_dist from the box's depth range
- * (exact for rigid extrinsics and a pinhole K: |c - x'| >= |z - l2| / scale) -- before projecting a single sample into them:
- * same corr / valid, same bits (option gn_no_view_cull = 1 keeps every view).  Round 4; no reference counterpart. */
-size_t dfh_gn_views_bytes_cells(int n_views, int H, int W);
-int dfh_gn_pack_views_cells(void *views_out, int n_views, const void *const *depth, int H, int W, const double *lw_cam, void *stream);
-int dfh_gn_associate_views(const double *sample_pos, const int *nbr, const double *weights, int n_samples, int knn,
-                           const double *node_dq, const double lw_dq[8], const void *views, int n_views, int depth_dtype, int H, int W,
-                           const double K[9], const double Kinv[9], double scale, const double center[3], double half,
-                           double max_dist, double *corr_out, unsigned char *valid_out, void *stream);
+size_t dfh_gn_views_bytes(int n_views, int depth_dtype, int H, int W);
+int dfh_gn_pack_views(void *out, int n_views, const void *const *depth, int depth_dtype, int H, int W, const double *lw_cam,
+                      void *stream);
 
-/* Gauss-Newton normal equations of 0.5*|computef|^2 in 6-DoF left twists (dq_a <- exp(xi_a) (x) dq_a):
- * vals (n_blocks x 36, block-sparse rows row_ptr/col with sorted columns) <- J^T J, rhs (6 n_nodes) <-
- * J^T r, cost_count[0] <- 0.5 |r|^2, cost_count[1] <- number of valid samples.  Data rows use the static
- * weights of dfh_sample_knn; node_nbr == NULL or rw == 0 skips the regularisation rows.  The block
- * pattern must contain every node pair of every sample tuple and every (i, j) of node_nbr (both
- * orders) plus the diagonal; missing blocks are silently dropped. */
-int dfh_gn_build(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                 const double *corr, const unsigned char *valid, int n_samples, int knn, const double *node_dq,
-                 const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                 const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                 double *rhs, double *cost_count, void *stream);
+/* corr / valid of the problem's samples against the frame (no system is touched). */
+int dfh_gn_associate(const dfh_gn_problem *problem, const dfh_gn_frame *frame, void *stream);
 
-/* The same normal equations without floating-point atomics in the data term (same bits every run), for
- * callers that prepare a plan once per frame (samples and their node tuples are static while the warp field
- * moves).  Samples sorted by node tuple; a "row" = a maximal run of equal tuples inside one tile of dfh_gn_tile_samples() (128) samples:
- *   run_id[s]           row of sample s (n_rows rows);  partial: scratch of n_rows x dfh_gn_partial_doubles(knn)
- *                       + 2 x ceil(n_samples / dfh_gn_tile_samples()) + n_rows doubles (the rows | {cost, count} per tile | one live flag per row)
- *   blk_ptr (n_blocks+1), blk_ent   for block b the entries row * knn^2 + sa * knn + sb (slots sa, sb of the
- *                                   row's tuple hold the block's row node and column node), any fixed order
- *   node_ptr (n_nodes+1), node_ent  for node a the entries row * knn + slot
- * The tile pass stores each row's {Gram matrix as whole 6x6 sub-blocks for the slot pairs sa <= sb, 36 contiguous doubles each |
- * J^T r | cost | count} (rows padded to whole 64-byte lines; rows without a valid sample in this iteration are flagged dead in the
- * dense flag array and skipped); a gather pass adds them per block, reading one contiguous sub-block per list entry.
- * partial_reg (n_nodes * knn rows of dfh_gn_partial_doubles(2) doubles) + rblk_ptr / rblk_ent / rnode_ptr / rnode_ent: the same for the
- * regulariser, a pair (i, node_nbr[i*knn+slot]) being a 2-node row (entries row * 4 + sa * 2 + sb, row * 2 + slot);
- * partial_reg == NULL keeps the regulariser on atomics.
- * huber_delta > 0: every data row and its residual are scaled by sqrt(min(1, huber_delta / |r|)), the IRLS form of the
- * Huber loss the reference's solver uses (least_squares(loss='huber'), core/fusion.py:389); cost_count[0] is then the
- * Huber objective sum rho(r), rho = r^2 / 2 up to huber_delta and huber_delta (|r| - huber_delta / 2) beyond, plus the
- * regulariser's 0.5 |rho|^2.  0 = plain least squares. */
+/* The normal equations of the problem.  frame == NULL: corr / valid are inputs.  frame != NULL: the association is fused into
+ * the data-row kernel -- every sample is warped once, associated as by dfh_gn_associate (corr / valid receive the same values,
+ * bit for bit) and the valid ones go straight on to their Jacobian rows; it needs the data plan and DFH_F32 maps. */
+int dfh_gn_build(const dfh_gn_problem *problem, const dfh_gn_frame *frame, void *stream);
 size_t dfh_gn_partial_doubles(int knn);
-int dfh_gn_build_planned(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                         const double *corr, const unsigned char *valid, int n_samples, int knn, const double *node_dq,
-                         const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                         const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                         double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                         const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                         const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                         void *stream);
-
-/* dfh_gn_associate and dfh_gn_build_planned in ONE launch sequence: the data-row kernel warps every sample once, associates it
- * against `depth` (float32, H x W) exactly as dfh_gn_associate does -- corr_out / valid_out receive the same values, bit for
- * bit -- and sends the valid ones straight on to their Jacobian rows; the normal equations are those of dfh_gn_build_planned on
- * that corr / valid.  One launch and one blend + warp per sample less per GN iteration. */
-int dfh_gn_build_planned_assoc(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                               double *corr_out, unsigned char *valid_out, int n_samples, int knn, const double *node_dq,
-                               const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                               const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                               double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                               const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                               const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                               const float *depth, int H, int W, const double K[9], const double Kinv[9], const double lw_cam[12],
-                               double scale, const double center[3], double half, double max_dist, void *stream);
 
 /* Samples per tile of the planned build (a scratch row = a run of equal node tuples inside one tile; callers size tile_off,
  * the per-tile {cost, count} pairs behind the scratch rows and the torch restatement of the plan with it). */
@@ -366,7 +382,7 @@ int dfh_gn_tile_samples(void);
  *   (*n_rows_out, like *uncovered_out below and dfh_surface_count's *total_out, is written by ONE plain store of the sequence's
  *   last writer: it may be device memory or pinned host memory, which the host can then watch instead of queueing a copy.)
  * dfh_gn_plan_build:   run_id (n_samples), row_first (n_rows: first sample of every row) and the CSR lists of
- *   dfh_gn_build_planned -- blk_ptr (n_blocks + 1) / blk_ent (n_rows * knn^2), node_ptr (n_nodes + 1) / node_ent (n_rows * knn),
+ *   dfh_gn_problem -- blk_ptr (n_blocks + 1) / blk_ent (n_rows * knn^2), node_ptr (n_nodes + 1) / node_ent (n_rows * knn),
  *   every list in ascending entry order; *uncovered_out (device int) <- 1 if some node pair of some row is not a block
  *   of the pattern (row_ptr / col), its entries are left out.  n_rows is the value dfh_gn_plan_count produced. */
 size_t dfh_gn_sort_workspace_bytes(int n_samples);
@@ -391,67 +407,13 @@ int dfh_pcg_solve_update(const int *row_ptr, const int *col, double *vals, const
                          double lm_abs, double lm_rel, double *x_out, void *workspace, size_t workspace_bytes, double *node_dq,
                          double step, void *stream);
 
-/* One whole Gauss-Newton iteration of a single-GPU solve: dfh_gn_build_planned_assoc followed by dfh_pcg_solve_update on the
- * system it produced (vals / rhs -> x_out, node_dq <- exp(step * x) node_dq) -- the same bits as the two calls.  Knowing both
- * halves, the library lets the clearing of the solve's workspace ride in the data-row launch (its last workgroups) instead of
- * being a 5 us fill between gather and solve.  Multi-GPU solves keep the two calls (the all-reduce of vals / rhs / cost_count
- * goes between them).  Reference: the body of least_squares' iteration for Fusion.computef, core/fusion.py:356-389. */
-int dfh_gn_iteration(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                     double *corr_out, unsigned char *valid_out, int n_samples, int knn, double *node_dq,
-                     const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                     const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                     double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                     const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                     const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                     const float *depth, int H, int W, const double K[9], const double Kinv[9], const double lw_cam[12],
-                     double scale, const double center[3], double half, double max_dist,
-                     int pcg_iters, double lm_abs, double lm_rel, double *x_out, void *pcg_workspace, size_t pcg_workspace_bytes,
-                     double step, void *stream);
-
-/* dfh_gn_build_planned_assoc / dfh_gn_iteration with the association of dfh_gn_associate_views (float32 depth maps): the same
- * arguments with (views, n_views) in place of (depth, lw_cam).  dfh_gn_iteration_views queues `n_iters` whole iterations back to
- * back (a frame's ten iterations in one call: nothing between them depends on the host; the same bits as n_iters calls).
- * blk_upper (n_upper pairs of ints; NULL / 0: none): the symmetry of the block pattern -- for every block with column >= row
- * {its index, the index of its mirror block (column, row), -1 on the diagonal}.  With it the gather walks only those blocks'
- * lists and stores every sum twice, the second time transposed: J^T J is symmetric and block (b, a)'s list is block (a, b)'s with
- * the slots swapped, so the result is the same bit for bit with half the block walks and half the reads. */
-int dfh_gn_build_planned_assoc_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                               double *corr_out, unsigned char *valid_out, int n_samples, int knn, const double *node_dq,
-                               const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                               const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                               double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                               const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                               const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                               const void *views, int n_views, int H, int W, const double K[9], const double Kinv[9],
-                               double scale, const double center[3], double half, double max_dist, const int *blk_upper, int n_upper,
-                               void *stream);
-int dfh_gn_iteration_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                     double *corr_out, unsigned char *valid_out, int n_samples, int knn, double *node_dq,
-                     const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                     const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                     double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                     const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                     const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                     const void *views, int n_views, int H, int W, const double K[9], const double Kinv[9],
-                     double scale, const double center[3], double half, double max_dist,
-                     int pcg_iters, double lm_abs, double lm_rel, double *x_out, void *pcg_workspace, size_t pcg_workspace_bytes,
-                     double step, int n_iters, const int *blk_upper, int n_upper, void *stream);
-/* A frame's whole solve behind one call: n_global rigid-mode steps (a build + dfh_gn_global_step(global_lm) each; global_scratch as
- * there, global_xi_out may be NULL), then the n_iters node iterations of dfh_gn_iteration_views -- the same launches in the same
- * order as the separate calls, hence the same bits.  Reached through pipeline.FrameSolver.gn_iteration(n_global > 0) on one GPU;
- * SlabFrame.step does not use it (its rigid-mode steps are dfh_gn_global_sampled_views, its node iterations dfh_gn_iteration_views). */
-int dfh_gn_frame_solve_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights,
-                     double *corr_out, unsigned char *valid_out, int n_samples, int knn, double *node_dq,
-                     const double *node_pos, const double *node_w, const int *node_nbr, int n_nodes,
-                     const double lw_dq[8], double rw, const int *row_ptr, const int *col, int n_blocks, double *vals,
-                     double *rhs, double *cost_count, const int *run_id, int n_rows, double *partial, const int *blk_ptr,
-                     const int *blk_ent, const int *node_ptr, const int *node_ent, double *partial_reg,
-                     const int *rblk_ptr, const int *rblk_ent, const int *rnode_ptr, const int *rnode_ent, double huber_delta,
-                     const void *views, int n_views, int H, int W, const double K[9], const double Kinv[9],
-                     double scale, const double center[3], double half, double max_dist,
-                     int pcg_iters, double lm_abs, double lm_rel, double *x_out, void *pcg_workspace, size_t pcg_workspace_bytes,
-                     double step, int n_iters, const int *blk_upper, int n_upper,
-                     int n_global, double global_lm, double *global_xi_out, void *global_scratch, size_t global_scratch_bytes, void *stream);
+/* A single-GPU solve behind one call: params->n_global rigid-mode steps (a fused build + dfh_gn_global_step each), then
+ * params->n_iters node iterations, each a fused build followed by dfh_pcg_solve_update on the system it produced -- the same
+ * bits as the separate calls.  Knowing both halves, the library lets the clearing of the solve's workspace ride in the data-row
+ * launch; the iterations are queued back to back (nothing between them depends on the host).  frame: DFH_F32 maps; the problem
+ * needs its data plan.  Multi-GPU solves keep the separate calls (the all-reduce goes between build and solve).  Reference: the
+ * body of least_squares' iteration for Fusion.computef, core/fusion.py:356-389. */
+int dfh_gn_solve(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_solve_params *params, void *stream);
 
 /* Multi-GPU solve: what travels in the per-iteration all-reduce.  `system` = {J^T J blocks (n_blocks x 36) | J^T r (6 n_nodes) |
  * cost, count} as the builds write it; J^T J is symmetric, so only the blocks with col >= row are packed (then J^T r and
@@ -468,7 +430,7 @@ int dfh_gn_unpack_upper(double *system, const int *row_of, const int *col, const
  * one workgroup per CU.  That cannot be known when several PROCESSES time-share one GPU: such callers declare it with
  * dfh_pcg_set_mode(2) and every solve then takes the two-launches-per-iteration path (0 = auto, the default).
  * A barrier of the persistent kernel that does not complete within its spin bound (seconds) makes every workgroup
- * leave: x_out = NaN, node_dq untouched (the twist update of dfh_pcg_solve_update / dfh_gn_iteration* is all or nothing: the
+ * leave: x_out = NaN, node_dq untouched (the twist update of dfh_pcg_solve_update / dfh_gn_solve is all or nothing: the
  * workgroup that finishes last applies every row's step, and only if no barrier timed out and every x is finite -- after a
  * timed-out solve node_dq is what it was before that solve), and a per-device counter is bumped.  dfh_pcg_status() synchronises `stream`,
  * reads and clears that counter: DFH_OK, or DFH_E_TIMEOUT when a solve since the last call timed out
@@ -495,7 +457,7 @@ int dfh_apply_twist(double *node_dq, const double *xi, int n_nodes, double step,
  * starts at the view count), so what the field carried is largely in the volume afterwards -- without this decay nothing ever
  * pulls a node back and the field random-walks.  No reference counterpart. */
 int dfh_relax_twists(double *node_dq, int n_nodes, double factor, void *stream);
-/* The rigid mode of a built system (dfh_gn_build*: vals, rhs), solved on its own: all nodes share ONE twist xi --
+/* The rigid mode of a built system (dfh_gn_build: vals, rhs), solved on its own: all nodes share ONE twist xi --
  * (sum of all 6x6 blocks + lm_rel diag) xi = -(sum of all J^T r) -- which is applied to every node,
  * node_dq[a] <- exp(xi) (x) node_dq[a], and written to xi_out (6 doubles, may be NULL).  Block-Jacobi PCG truncated at ten
  * iterations hardly moves this mode (the regulariser does not penalise it, the preconditioner does not see it); the frame loop
@@ -509,16 +471,12 @@ int dfh_relax_twists(double *node_dq, int n_nodes, double factor, void *stream);
  * common left twist only rotates its residuals).  n_steps steps, each three short launches (rows, the 29 sums -- 21 upper entries
  * of A_g, 6 of g_g, objective, valid count -- and solve + apply); xi_out (8 doubles, may be NULL): the last step's twist | its
  * objective | its valid-sample count.  scratch: dfh_gn_global_sampled_bytes(n_samples, stride) bytes.  Sums in a fixed order: the
- * same bits every run.  knn 1..8; depth_dtype (DFH_F32 / DFH_F64): the element type of the views' depth maps, as in
- * dfh_gn_associate_views (the table holds pointers only).  sums_out != NULL (n_steps = 1): only the 29 sums of THIS rank's samples are produced (32 doubles)
- * -- the caller all-reduces them over ranks and calls dfh_gn_global_apply: every rank then applies the same twist.
+ * same bits every run.  Of the problem it reads the samples, node_dq, n_nodes, lw_dq and huber_delta; the frame's maps may be
+ * DFH_F32 or DFH_F64.  sums_out != NULL (n_steps = 1): only the 29 sums of THIS rank's samples are produced (32 doubles) -- the caller all-reduces them over ranks and calls dfh_gn_global_apply: every rank then applies the same twist.
  * Restated in oracle/gn_np.global_step_sampled. */
 size_t dfh_gn_global_sampled_bytes(int n_samples, int stride);
-int dfh_gn_global_sampled_views(const double *sample_pos, const double *sample_nrm, const int *nbr, const double *weights, int n_samples, int knn,
-                                double *node_dq, int n_nodes, const double lw_dq[8], double huber_delta, const void *views, int n_views,
-                                int depth_dtype, int H, int W, const double K[9], const double Kinv[9], double scale, const double center[3],
-                                double half, double max_dist, int stride, double lm_rel, int n_steps, double *xi_out, double *sums_out,
-                                void *scratch, size_t scratch_bytes, void *stream);
+int dfh_gn_global_sampled(const dfh_gn_problem *problem, const dfh_gn_frame *frame, int stride, double lm_rel, int n_steps,
+                          double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream);
 int dfh_gn_global_apply(const double *sums29, double lm_rel, int n_nodes, double *node_dq, double *xi_out, void *stream);
 size_t dfh_gn_global_step_bytes(void);
 int dfh_gn_global_step(const double *vals, int n_blocks, const double *rhs, int n_nodes, double lm_rel, double *node_dq, double *xi_out,

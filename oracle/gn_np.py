@@ -267,7 +267,7 @@ def associate_depth(points_idx, K, Kinv, lw_cam, dm, scale, center, half):
 
 
 def associate_depth_views(points_idx, K, Kinv, lw_cams, dms, scale, center, half, max_dist=0.0):
-    """Association against several live views (the device's dfh_gn_associate_views; no reference counterpart): every view is
+    """Association against several live views (the device's dfh_gn_associate; no reference counterpart): every view is
     tried with associate_depth, a point keeps the correspondence of the view in which it lies closest to the observed surface
     -- smallest |c - x'| among the views where it is valid and (max_dist > 0) within the gate; ties go to the lower view
     index.  Returns (corr_idx (S,3), valid (S,), chosen view (S,), -1 where invalid)."""
@@ -394,7 +394,7 @@ def global_step(dqs, blocks, Jtr, lm_rel):
 
 
 def global_step_sampled(dqs, pos, nrm, nbr, node_pos, node_w, lw, associate, huber, lm_rel, stride=1, tile=128):
-    """The rigid-mode step straight from the samples (dfh_gn_global_sampled_views): the data rows of every `stride`-th `tile`-sample
+    """The rigid-mode step straight from the samples (dfh_gn_global_sampled): the data rows of every `stride`-th `tile`-sample
     tile, a sample's Jacobian for the shared twist = the sum of its k node blocks, Huber weights as in the builds, no regulariser;
     (A_g + lm_rel diag A_g) xi = -g_g, xi applied to every node.  Returns (new dqs, xi, valid count)."""
     warped = O.warp(pos, dqs[nbr], node_pos[nbr], node_w[nbr], m_lw=lw)
@@ -412,7 +412,7 @@ def global_step_sampled(dqs, pos, nrm, nbr, node_pos, node_w, lw, associate, hub
 
 
 def huber_scale(r, delta):
-    """(sqrt of the IRLS weight per row, Huber objective sum rho(r)) -- dfh_gn_build_planned's huber_delta."""
+    """(sqrt of the IRLS weight per row, Huber objective sum rho(r)) -- dfh_gn_problem's huber_delta."""
     a = np.abs(r)
     sc = np.sqrt(np.minimum(1.0, delta / np.maximum(a, 1e-300)))
     obj = float(np.where(a <= delta, 0.5 * r * r, delta * (a - 0.5 * delta)).sum())

@@ -70,3 +70,28 @@ def test_options_round_trip():
     with pytest.raises(ValueError):
         _lib.set_option("no_such_switch", 1)
     assert _lib.get_option("no_such_switch") < -(2 ** 62)
+
+
+def test_gn_struct_layouts_match_the_ctypes_mirrors(tmp_path):
+    """dfh_gn_problem / dfh_gn_frame / dfh_gn_solve_params as the C compiler lays them out (sizeof, every field's offsetof)
+    equal their ctypes mirrors in _lib.py: a field added or moved on one side only fails here, not in a GPU test."""
+    import shutil
+    import subprocess
+    cc = shutil.which("cc")
+    assert cc, "no C compiler"
+    lines = []
+    for name, mirror in _lib.STRUCTS.items():
+        lines.append('printf("%s sizeof %%zu\\n", sizeof(%s));' % (name, name))
+        lines += ['printf("%s %s %%zu\\n", offsetof(%s, %s));' % (name, f, name, f) for f, _ in mirror._fields_]
+    src = tmp_path / "layout.c"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "dfusion_hip.h"\nint main(void) {\n%s\nreturn 0;\n}\n' % "\n".join(lines))
+    exe = tmp_path / "layout"
+    subprocess.run([cc, "-I", os.path.dirname(_lib.HEADER_PATH), "-o", str(exe), str(src)], check=True)
+    got = {}
+    for line in subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.splitlines():
+        name, field, value = line.split()
+        got[(name, field)] = int(value)
+    for name, mirror in _lib.STRUCTS.items():
+        assert got[(name, "sizeof")] == ctypes.sizeof(mirror), name
+        for f, _ in mirror._fields_:
+            assert got[(name, f)] == getattr(mirror, f).offset, (name, f)

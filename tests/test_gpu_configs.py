@@ -251,9 +251,9 @@ def test_config5_thirty_frame_sequence():
 
 
 def test_multi_view_association_and_gn_loop_vs_oracle():
-    """Data term over several live views (dfh_gn_associate_views / dfh_gn_iteration_views) at R = 64, three views 50 degrees
+    """Data term over several live views (dfh_gn_associate / dfh_gn_solve) at R = 64, three views 50 degrees
     apart: the chosen correspondences (closest valid view, ties to the lower index) equal oracle/gn_np.associate_depth_views',
-    one view through the same entry points equals dfh_gn_associate bit for bit, and six GN iterations with the benched
+    one view as a list equals one view bit for bit, and six GN iterations with the benched
     settings follow the CPU loop (same truncated PCG) to 1e-4 relative in cost at every iteration -- with MORE valid samples
     than any single view gives."""
     R, N, iters = 64, 96, 6
@@ -455,7 +455,7 @@ def test_solve_recovers_a_known_translation():
 
 
 def test_rigid_mode_step_variants_and_oracle():
-    """dfh_gn_global_sampled_views (the frame loop's rigid-mode step: one twist for all nodes from the data rows) against its numpy
+    """dfh_gn_global_sampled (the frame loop's rigid-mode step: one twist for all nodes from the data rows) against its numpy
     restatement (oracle/gn_np.global_step_sampled: all tiles, and every 3rd tile), and against the step from the BUILT normal
     equations (dfh_gn_global_step) with the regulariser switched off -- the same system summed another way."""
     R, N = 96, 128
@@ -520,7 +520,7 @@ def _rigid_scene():
 @pytest.mark.parametrize("knn", [1, 3, 4, 8])
 @pytest.mark.parametrize("depth_dtype", [np.float32, np.float64])
 def test_rigid_mode_step_every_depth_dtype_and_knn(depth_dtype, knn):
-    """The rigid-mode step (dfh_gn_global_sampled_views) on every input the node iterations accept: float32 and float64 depth maps
+    """The rigid-mode step (dfh_gn_global_sampled) on every input the node iterations accept: float32 and float64 depth maps
     (the float64 values are NOT float32-representable: a step that read them as float32, or cast them, fails), knn 1 .. 8, one and
     three views, stride 1 and 3 -- against oracle/gn_np.global_step_sampled: twist to 1e-9 relative, valid count exact, node DQs
     to 1e-9.  All-zero depth maps (no valid row): no step, no error."""

@@ -10,8 +10,8 @@ entries all depend on K.  Elsewhere the assembled system meets the oracle at K =
      gather bit for bit the full one, and both against the oracle's association and system;
   3. K = 8 at N = 215 (tuple keys packed on the device, just under 2^62) and N = 216 (torch.unique, no keys), and a second
      sample set on the kept pattern;
-  4. the one-call GN loop (dfh_gn_iteration_views) at knn 3 and 8 against gn_loop_truncated;
-  5. dfh_gn_frame_solve_views (n_global rigid-mode steps + the node iterations) against the separate calls and the oracle.
+  4. the one-call GN loop (dfh_gn_solve) at knn 3 and 8 against gn_loop_truncated;
+  5. dfh_gn_solve with n_global > 0 (n_global rigid-mode steps + the node iterations) against the separate calls and the oracle.
 
 Bounds of the system, per entry: |A - A_o| <= 1e-10 A_abs + 1e-13 max(A_abs), where A_abs is the same assembly of |J| and |r|
 (a single max-relative bound would hide a missing low-weight contribution); entries with A_abs = 0 are exactly 0; J^T r to
@@ -126,7 +126,7 @@ def make_solver(K, npos, nw, dq, pts, nrm):
 @pytest.mark.parametrize("shape", ["S1", "S127", "S129", "S3000", "cluster"])
 @pytest.mark.parametrize("K", KNNS)
 def test_build_every_knn_and_path_vs_oracle(K, shape):
-    """Planned build, atomic build (dfh_gn_build), regulariser in its own gather and in its own launch, Huber 0 and a delta that
+    """Planned build, atomic build (dfh_gn_build without a plan), regulariser in its own gather and in its own launch, Huber 0 and a delta that
     down-weights 40 % of the rows: all against the oracle; the planned build twice: the same bits."""
     rng = np.random.default_rng(100 * K + ["S1", "S127", "S129", "S3000", "cluster"].index(shape))
     npos, nw, dq, pts = problem(K, shape, rng)
@@ -176,7 +176,7 @@ def test_build_every_knn_and_path_vs_oracle(K, shape):
             worst[switch] = max(worst.get(switch, 0.0), check_system(sv, ref, tag + (switch,)))
             assert torch.equal(s1, sv.system) or not same_order, tag + (switch,)
         if huber == 0.0:
-            _lib.set_option("py_gn_atomic", 1)                  # dfh_gn_build (for K > 4 its table-less branch)
+            _lib.set_option("py_gn_atomic", 1)                  # the atomic dfh_gn_build (for K > 4 its table-less branch)
             sv.build(LW, rw, huber)
             worst["atomic"] = check_system(sv, ref, tag + ("atomic",))
             with pytest.raises(ValueError):
@@ -229,7 +229,7 @@ def scene_solver(knn):
 # ---------------------------------------------------------------- 2. the fused-association builds at every K
 @pytest.mark.parametrize("K", KNNS)
 def test_fused_association_builds_every_knn(K):
-    """dfh_gn_build_planned_assoc (one view) and dfh_gn_build_planned_assoc_views (three views) after moving the field: corr, valid
+    """dfh_gn_build with a frame (one view, three views) after moving the field: corr, valid
     and the system bit for bit those of the separate association + planned build, the upper-triangle gather bit for bit the
     full one, corr / valid those of associate_depth_views on the oracle's warped samples, the system the oracle's."""
     s = sphere_scene()
@@ -376,19 +376,19 @@ def gpu_loop(fs, iters, **kw):
 
 @pytest.mark.parametrize("knn", [3, 8])
 def test_one_call_gn_loop_vs_oracle(knn):
-    """dfh_gn_iteration_views with n_iters > 1 on three views, the benched settings, against gn_loop_truncated."""
+    """dfh_gn_solve with n_iters > 1 on three views, the benched settings, against gn_loop_truncated."""
     fs = scene_solver(knn)
     iters = 4
     costs, counts, dq = gpu_loop(fs, iters)
-    check_loop(("dfh_gn_iteration_views", knn), costs, counts, dq, *loop_oracle(fs, iters))
+    check_loop(("dfh_gn_solve", knn), costs, counts, dq, *loop_oracle(fs, iters))
     assert costs[-1] / counts[-1] < costs[0] / counts[0]
 
 
-# ---------------------------------------------------------------- 5. dfh_gn_frame_solve_views
+# ---------------------------------------------------------------- 5. dfh_gn_solve with rigid-mode steps
 @pytest.mark.parametrize("knn", [3, 4])
 def test_frame_solve_views_vs_separate_calls_and_oracle(knn):
     """gn_iteration(..., n_global=2): two rigid-mode steps from the built normal equations, then the node iterations, in one
-    library call (dfh_gn_frame_solve_views) -- bit for bit build_associated + global_step twice and then gn_iteration(n_iters),
+    library call (dfh_gn_solve, n_global > 0) -- bit for bit build_associated + global_step twice and then gn_iteration(n_iters),
     and the oracle's loop with global_iters = 2, global_sampled = False at the bars of the loop test."""
     s = sphere_scene()
     fs = scene_solver(knn)
@@ -405,5 +405,5 @@ def test_frame_solve_views_vs_separate_calls_and_oracle(knn):
                           (sv.node_dq, sv.system, sv.corr, sv.valid, sv.global_xi)):
         assert torch.equal(a, b), (knn, name)
     assert float(one[4][:6].abs().max()) > 0.0                                   # (the rigid-mode steps did move the field)
-    check_loop(("dfh_gn_frame_solve_views", knn), costs, counts, dq,
+    check_loop(("dfh_gn_solve n_global", knn), costs, counts, dq,
                *loop_oracle(fs, iters, global_iters=2, global_sampled=False, global_lm=0.1))

@@ -230,7 +230,7 @@ def test_frame_loop_variants_give_the_same_bits(monkeypatch):
     pinned memory behind an event; the plan's lists are built by counting + per-list sorts.  The sequential loop
     (DFH_NO_SIDE_STREAM), the radix-sort plan (DFH_PLAN_RADIX), the stage-timed loop (a synchronisation after every stage) and the
     loop that reads its counts through device scalars instead of host-visible words (HostScalar off) and the loop whose GN
-    iterations are two calls (build, solve) instead of dfh_gn_iteration (DFH_GN_NO_FUSED_ITER), and the loop whose gather walks the
+    iterations are two calls (build, solve) instead of dfh_gn_solve (DFH_GN_NO_FUSED_ITER), and the loop whose gather walks the
     lists of ALL blocks instead of those with column >= row (option gn_gather_full) must give the same warp
     field and the same canonical volume, bit for bit: a race between the streams, or a count read too early, would show here."""
     from dynamicfusion_body_amd.pipeline import SlabFrame
@@ -272,7 +272,7 @@ def test_frame_loop_variants_give_the_same_bits(monkeypatch):
         for a, b in zip(got[1:], ref[1:]):
             assert torch.equal(a, b), (env, timed)
     # the data term on the first view only (round 2's): the frame's iterations in one call through a one-view table against one
-    # dfh_gn_iteration call per iteration (DFH_GN_ITER_PER_CALL) -- the same bits; and the three-view data term is a different solve
+    # dfh_gn_solve call per iteration (DFH_GN_ITER_PER_CALL) -- the same bits; and the three-view data term is a different solve
     ref1 = run((), False, data_views=1)
     got1 = run(("DFH_GN_ITER_PER_CALL",), False, data_views=1)
     assert got1[0] == ref1[0]
@@ -282,8 +282,8 @@ def test_frame_loop_variants_give_the_same_bits(monkeypatch):
 
 
 def test_association_inside_the_build_is_bit_identical(monkeypatch):
-    """dfh_gn_build_planned_assoc (association folded into the data-row kernel) against dfh_gn_associate followed by
-    dfh_gn_build_planned: same correspondences, same validity, same normal equations and cost, bit for bit -- at identity and
+    """dfh_gn_build with a frame (association folded into the data-row kernel) against dfh_gn_associate followed by
+    dfh_gn_build without one: same correspondences, same validity, same normal equations and cost, bit for bit -- at identity and
     after moving the field, with and without Huber weights and a gate, and the whole 5-iteration loop."""
     R, N, k = 64, 48, 4
     K, (H, W), scale, center, tdist, T, Wt = build_canonical(R, "C1")
@@ -372,7 +372,7 @@ class _CountingLib:
 
     def __getattr__(self, name):
         fn = getattr(self._lib, name)
-        if name not in ("dfh_gn_pack_views", "dfh_gn_pack_views_cells"):
+        if name != "dfh_gn_pack_views":
             return fn
 
         def counted(*args):

@@ -364,8 +364,8 @@ def test_planned_gather_walks_lists_of_every_length():
 
 
 def test_planned_build_is_deterministic_and_matches_the_atomic_build(golden, monkeypatch):
-    """dfh_gn_build_planned (per-run partial rows + gather, regulariser included) has no floating-point
-    atomics: two builds give the same bits; dfh_gn_build (atomics) gives the same system to rounding."""
+    """The planned dfh_gn_build (per-run partial rows + gather, regulariser included) has no floating-point
+    atomics: two builds give the same bits; dfh_gn_build without a plan (atomics) gives the same system to rounding."""
     g, verts, norms, corr, nbr, vidx, npos, ndq, nw, lw, rw = load(golden)
     rng = np.random.default_rng(3)
     valid = (rng.random(len(verts)) < 0.7).astype(np.uint8)

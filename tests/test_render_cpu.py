@@ -16,16 +16,16 @@ def lib_path():
     return build.build_library()
 
 
-def test_render_symbols_declared_exported_bound_at_abi6(lib_path):
-    """The rasterizer's entry points (added with ABI 5) are declared, exported and bound in the library of ABI 6 (6 gave
-    dfh_gn_global_sampled_views its depth_dtype argument)."""
+def test_render_symbols_declared_exported_bound_at_abi7(lib_path):
+    """The rasterizer's entry points (added with ABI 5) are declared, exported and bound in the library of ABI 7 (7 passed the
+    GN problem and live frame as structs)."""
     declared = _lib.declared_symbols()
     lib = ctypes.CDLL(lib_path)
     for name in RENDER_SYMBOLS:
         assert name in declared, name
         assert hasattr(lib, name), name
         assert name in _lib._SIGNATURES, name
-    assert _lib.ABI_VERSION == 6 and _lib.load().dfh_version() == 6
+    assert _lib.ABI_VERSION == 7 and _lib.load().dfh_version() == 7
 
 
 def test_render_workspace_size_query(lib_path):
