@@ -623,12 +623,24 @@ struct ColumnLane {
 // PREFETCH: T / w of the wave's NEXT brick are requested right after the depth gathers of the current one (they are in
 // flight through its decisions, its stores and the next projection); otherwise a brick's T / w are requested when the walk
 // reaches it, ahead of its projection.
+// GATHER_FIRST (cache-resident slabs; PREFETCH unused): T / w of a pack are loaded only once the view is known to update it, so the
+// packs no view touches -- mostly behind the surface, where only the depth value tells -- cost no bytes (the byte class of the
+// row sweep, DFH_K1_PATH_ROWS).  That puts one more dependent round trip (gathers -> T / w) into a brick's life; the walk is
+// software-pipelined so that the wave never waits on it alone: brick i's T / w loads go out as soon as its decisions are made,
+// brick i+1 is projected and its gathers issued while they are in flight, and brick i is averaged and stored between the
+// issue of brick i+1's gathers and their use (view_pack's after_gathers hook).  Brick i+1's ms / upd are held across that wait.
+// The pinhole gather-first walk is held to 72 VGPRs, 7 waves per SIMD (left alone it takes 76: 6 waves, 3-4 % slower at 256^3;
+// a cap of 8 waves spills and is 30 % slower: profiles/r5_k1_experiments.txt).  The non-pinhole instances need ~110 VGPRs and
+// would spill under that cap: they keep the compiler's choice.
+#ifndef DFH_K1_GF_WAVES
+#define DFH_K1_GF_WAVES 7
+#endif
 #ifdef DFH_K1_WAVES                    // experiment builds: force the register budget of DFH_K1_WAVES waves per SIMD
 #define DFH_K1_OCC __attribute__((amdgpu_waves_per_eu(DFH_K1_WAVES, DFH_K1_WAVES)))
 #else
-#define DFH_K1_OCC
+#define DFH_K1_OCC __attribute__((amdgpu_waves_per_eu(GATHER_FIRST && PINHOLE ? DFH_K1_GF_WAVES : 1)))
 #endif
-template <typename DepthT, bool PINHOLE, int BY, bool PREFETCH, bool NT>
+template <typename DepthT, bool PINHOLE, int BY, bool PREFETCH, bool NT, bool GATHER_FIRST>
 __global__ __launch_bounds__(256) DFH_K1_OCC void integrate_depth_column_kernel(float *__restrict__ tsdf, float *__restrict__ tsdf_w,
                                                                       const DepthT *__restrict__ depth, const IntegrateParams p,
                                                                       const BrickGeom g, const unsigned short *__restrict__ mask) {
@@ -642,6 +654,40 @@ __global__ __launch_bounds__(256) DFH_K1_OCC void integrate_depth_column_kernel(
     int z0 = c.z_of(i);
     bool in_grid = c.in_xy && z0 < p.Z;
     P t, w;
+    if (GATHER_FIRST) {
+        float ms[4];
+        bool upd[4];
+        bool any = view_pack<DepthT, 4, PINHOLE, false>(p, p_rare, depth, p.x0 + c.xl, c.y, z0, ms, upd) && in_grid;
+        // (t / w live inside one iteration and the last brick is finished after the loop: with t / w carried round the loop,
+        // or the last brick finished inside it, the copies at its back edge waited for every outstanding access, stores included)
+        while (alive) {
+            P tb, wb;
+            if (any) { tb = ld_pack<NT>(tsdf + c.row + z0); wb = ld_pack<NT>(tsdf_w + c.row + z0); }
+            const int zn = c.z_of(__builtin_ctzll(alive));
+            alive &= alive - 1;
+            float msn[4];
+            bool updn[4];
+            const bool anyn = view_pack<DepthT, 4, PINHOLE, false>(p, p_rare, depth, p.x0 + c.xl, c.y, zn, msn, updn, [&](bool) {
+                if (any) {                               // brick i: average and store the updated packs
+                    apply_pack<4>(tb, wb, ms, upd, p.wmax_f);
+                    st_pack<NT>(tsdf + c.row + z0, tb);
+                    st_pack<NT>(tsdf_w + c.row + z0, wb);
+                }
+            }) && c.in_xy && zn < p.Z;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { ms[j] = msn[j]; upd[j] = updn[j]; }
+            any = anyn;
+            z0 = zn;
+        }
+        if (any) {
+            t = ld_pack<NT>(tsdf + c.row + z0);
+            w = ld_pack<NT>(tsdf_w + c.row + z0);
+            apply_pack<4>(t, w, ms, upd, p.wmax_f);
+            st_pack<NT>(tsdf + c.row + z0, t);
+            st_pack<NT>(tsdf_w + c.row + z0, w);
+        }
+        return;
+    }
     if (PREFETCH && in_grid) { t = ld_pack<NT>(tsdf + c.row + z0); w = ld_pack<NT>(tsdf_w + c.row + z0); }
     for (;;) {
         if (!PREFETCH && in_grid) { t = ld_pack<NT>(tsdf + c.row + z0); w = ld_pack<NT>(tsdf_w + c.row + z0); }
@@ -1052,17 +1098,29 @@ namespace dfh {
 // Options k1_no_bricks, k1_bricks_min (in 256-voxel bricks), k1_cull = 0 / 1, k1_bricks_nocull override.  (Classification
 // inside the sweep's waves -- eight lanes per brick -- was built and measured slower than the pass at both sizes: its pyramid
 // look-up is a memory round trip at the start of every wave, profiles/r3_k1_experiments.txt.)
-static int single_view_path(int vol_dtype, const int res[3], int x0, int x1, bool fast_ok, bool vec4, bool have_ws) {
-    if (vol_dtype != DFH_F32 || !fast_ok) return DFH_K1_PATH_EXACT;
+//   gather-first column walk (integrate_depth_column_kernel<..., GATHER_FIRST = true>): every slab that would take the unculled
+//     walk -- T, w loaded for the updated packs only, the row sweep's bytes (256^3: 159 against 214 MB per launch), so it reports
+//     DFH_K1_PATH_ROWS.  Option k1_gather_first = 0 keeps the walk that loads every pack, 1 also takes it behind the culling passes.
+struct K1Plan {
+    int path;          // DFH_K1_PATH_*: the byte class the sweep moves (dfh_integrate_depth_path)
+    bool bricks;       // a column walk (with or without the culling passes); otherwise the path names the kernel
+    bool cull;
+    bool gather_first;
+};
+
+static K1Plan single_view_plan(int vol_dtype, const int res[3], int x0, int x1, bool fast_ok, bool vec4, bool have_ws) {
+    if (vol_dtype != DFH_F32 || !fast_ok) return {DFH_K1_PATH_EXACT, false, false, false};
     const long slab_voxels = (long)(x1 - x0) * res[1] * res[2];
     const long bricks_min = opt().k1_bricks_min >= 0 ? opt().k1_bricks_min : kEarlyRowsMaxVoxels / 256 + 1;
     const long slab_bricks = (long)((res[1] + 3) / 4) * ((res[2] + 15) / 16) * ((x1 - x0 + kBrX - 1) / kBrX);
     if (vec4 && !on(opt().k1_no_bricks) && slab_bricks >= bricks_min) {
         const bool want_cull = !on(opt().k1_bricks_nocull) && (opt().k1_cull >= 0 ? opt().k1_cull != 0 : (size_t)slab_voxels * 8 > ((size_t)256 << 20));
-        if (!want_cull) return DFH_K1_PATH_COLUMNS;
-        if (have_ws) return DFH_K1_PATH_COLUMNS_CULLED;
+        if (!want_cull || have_ws) {
+            const bool gf = opt().k1_gather_first >= 0 ? opt().k1_gather_first != 0 : !want_cull;
+            return {gf ? DFH_K1_PATH_ROWS : want_cull ? DFH_K1_PATH_COLUMNS_CULLED : DFH_K1_PATH_COLUMNS, true, want_cull, gf};
+        }
     }
-    return DFH_K1_PATH_ROWS;
+    return {DFH_K1_PATH_ROWS, false, false, false};
 }
 
 }  // namespace dfh
@@ -1080,7 +1138,7 @@ extern "C" int dfh_integrate_depth_path(int vol_dtype, const int res[3], int x0,
     DFH_REQUIRE(res && res[0] > 0 && res[1] > 0 && res[2] > 0 && 0 <= x0 && x0 <= x1 && x1 <= res[0], "dfh_integrate_depth_path: bad grid or slab");
     const bool fast_ok = H <= kFastMaxDim && W <= kFastMaxDim;
     const bool vec4 = res[2] % 4 == 0 && !on(opt().k1_force_scalar);
-    return single_view_path(vol_dtype, res, x0, x1, fast_ok, vec4, have_workspace != 0);
+    return single_view_plan(vol_dtype, res, x0, x1, fast_ok, vec4, have_workspace != 0).path;
 }
 
 extern "C" int dfh_integrate_depth(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3],
@@ -1109,9 +1167,9 @@ extern "C" int dfh_integrate_depth(void *tsdf, void *tsdf_w, int vol_dtype, cons
     const bool fast_ok = H <= kFastMaxDim && W <= kFastMaxDim && scale > 0.0 && tdist > 0.0;
 
     const bool have_ws = workspace && workspace_bytes >= dfh_integrate_workspace_bytes(1, H, W, res, x0, x1);
-    const int path = single_view_path(vol_dtype, res, x0, x1, fast_ok, vec4, have_ws);
-    if (path == DFH_K1_PATH_COLUMNS || path == DFH_K1_PATH_COLUMNS_CULLED) {
-        const bool cull = path == DFH_K1_PATH_COLUMNS_CULLED;
+    const K1Plan plan = single_view_plan(vol_dtype, res, x0, x1, fast_ok, vec4, have_ws);
+    if (plan.bricks) {
+        const bool cull = plan.cull, gf = plan.gather_first;
         dim3 grid;
         int n_bricks = 0;
         const BrickGeom g = brick_geom(kBrY, p.Y, p.Z, p.nx, grid, n_bricks);
@@ -1132,8 +1190,8 @@ extern "C" int dfh_integrate_depth(void *tsdf, void *tsdf_w, int vol_dtype, cons
         // everything (373 against 384 us at 512^3), cache-resident slabs lose 5-10 % (80 against 70 VGPRs); k1_prefetch forces
         const bool prefetch = opt().k1_prefetch >= 0 ? opt().k1_prefetch != 0 : cull;
         const bool nt = use_nt((size_t)p.nx * p.Y * p.Z);
-#define DFH_COL(DT, PH, BY, PF, NT) hipLaunchKernelGGL((integrate_depth_column_kernel<DT, PH, BY, PF, NT>), grid, dim3(256), 0, s, (float *)tsdf, (float *)tsdf_w, (const DT *)depth, p, g, mask)
-#define DFH_COL_PF(DT, PH, BY, NT) do { if (prefetch) DFH_COL(DT, PH, BY, true, NT); else DFH_COL(DT, PH, BY, false, NT); } while (0)
+#define DFH_COL(DT, PH, BY, PF, NT, GF) hipLaunchKernelGGL((integrate_depth_column_kernel<DT, PH, BY, PF, NT, GF>), grid, dim3(256), 0, s, (float *)tsdf, (float *)tsdf_w, (const DT *)depth, p, g, mask)
+#define DFH_COL_PF(DT, PH, BY, NT) do { if (gf) DFH_COL(DT, PH, BY, false, NT, true); else if (prefetch) DFH_COL(DT, PH, BY, true, NT, false); else DFH_COL(DT, PH, BY, false, NT, false); } while (0)
 #define DFH_COL_SHAPE(DT, PH) do { if (nt) DFH_COL_PF(DT, PH, kBrY, true); else DFH_COL_PF(DT, PH, kBrY, false); } while (0)
         if (depth_dtype == DFH_F32) { if (pinhole) DFH_COL_SHAPE(float, true); else DFH_COL_SHAPE(float, false); }
         else { if (pinhole) DFH_COL_SHAPE(double, true); else DFH_COL_SHAPE(double, false); }

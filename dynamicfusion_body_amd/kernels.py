@@ -53,7 +53,10 @@ BRICK = (4, 2, 32)                                                            # 
 
 
 def integrate_path(T, depth, res=None, x_range=None, workspace=True):
-    """Name of the sweep integrate_depth takes for this slab and depth map (dfh_integrate_depth_path; no launch)."""
+    """The byte class of the sweep integrate_depth takes for this slab and depth map (dfh_integrate_depth_path; no launch):
+    "rows" = T and w loaded and stored for the updated packs only (the row sweep, and the gather-first column walk that 256^3
+    slabs take), "columns" = T and w of every pack loaded, "columns_culled" = of every pack of the bricks the culling passes
+    keep, "exact" = the fp64 chain."""
     lib = _lib.load()
     if res is None:
         res = tuple(T.shape)

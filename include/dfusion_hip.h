@@ -85,13 +85,13 @@ int dfh_integrate_depth(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3
                         void *workspace, size_t workspace_bytes, void *stream);
 
 /* Which sweep dfh_integrate_depth takes for float32 volumes of this slab and depth-map size (no launch): one of
- * DFH_K1_PATH_*.  All of them produce the same volumes bit for bit; they differ in the bytes they move (measurement code
- * counts those of the path taken).  have_workspace: a workspace of dfh_integrate_workspace_bytes(1, ...) bytes will be passed.
+ * DFH_K1_PATH_*, the CLASS of bytes the sweep moves (several kernels may share one).  All of them produce the same volumes bit for
+ * bit; they differ in the bytes they move (measurement code counts those of the path taken).  have_workspace: a workspace of dfh_integrate_workspace_bytes(1, ...) bytes will be passed.
  * No reference counterpart. */
 #define DFH_K1_PATH_EXACT 0          /* every voxel through the reference's fp64 chain (fp64 volumes, oversized depth maps) */
-#define DFH_K1_PATH_ROWS 1           /* one 1-KiB z run per wave; T, w loaded and stored for updated 16-byte packs only */
-#define DFH_K1_PATH_COLUMNS 2        /* 4 x 2 x 32 bricks, a wave walks a column of them; T, w of every pack loaded, updated packs stored */
-#define DFH_K1_PATH_COLUMNS_CULLED 3 /* the same behind a depth pyramid + brick classification: bricks no voxel of which can be updated are skipped */
+#define DFH_K1_PATH_ROWS 1           /* T, w loaded and stored for updated 16-byte packs only (the row sweep; the gather-first column walk) */
+#define DFH_K1_PATH_COLUMNS 2        /* T, w of every pack loaded, updated packs stored (the column walk over every 4 x 2 x 32 brick) */
+#define DFH_K1_PATH_COLUMNS_CULLED 3 /* T, w of every pack of the bricks a depth pyramid + brick classification keep loaded, updated packs stored */
 int dfh_integrate_depth_path(int vol_dtype, const int res[3], int x0, int x1, int H, int W, int have_workspace);
 
 /* The same for n_views depth maps in ONE sweep of the volume: what the reference's loops over fuseDepths do
