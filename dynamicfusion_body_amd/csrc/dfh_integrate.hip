@@ -107,6 +107,9 @@ __device__ __forceinline__ bool exact_voxel(const IntegrateParams &p, const Dept
     double cz;
     if (PINHOLE) {
         cz = zd;                                                    // Kinv row 2 == [0,0,1]
+        // ... unless z u or z v overflows (z = inf, or a float64 depth beyond ~1e306): the reference multiplies them with
+        // Kinv's zeros, 0 * inf = NaN, and a NaN sd updates nothing (u, v >= 0 here; 0 * inf is NaN and fails the test too)
+        if (!((zd * u < __builtin_huge_val()) & (zd * v < __builtin_huge_val()))) return false;
     } else {
         cz = (p.Kinv.m[6] * (zd * u) + p.Kinv.m[7] * (zd * v)) + p.Kinv.m[8] * (zd * 1.0);
     }
@@ -173,6 +176,10 @@ __device__ __forceinline__ void pack_coords(const IntegrateParams &p, int &y, in
 //
 // view_pack: one depth view's contribution to the VEC voxels (x, y, z0 + j*ZS): ms[j] = min(tdist, sd) / scale and
 // upd[j] = the reference's update condition; returns whether any voxel of the pack is updated.
+// A depth so large that the reference's z * u can overflow (exact_voxel): -inf in a float32 map, beyond -1e300 in a float64 one.
+__device__ __forceinline__ bool depth_overflows(float d) { return d < -3.402823466e38f; }
+__device__ __forceinline__ bool depth_overflows(double d) { return d < -1e300; }
+
 struct NoHook {
     __device__ __forceinline__ void operator()(bool) const {}
 };
@@ -254,18 +261,22 @@ __device__ __forceinline__ bool view_pack(const IntegrateParams &p, const Integr
     bool any = false;
 #pragma unroll
     for (int j = 0; j < VEC; ++j) {
+        // z > 0 (:197) is decided in the depth map's OWN type: a float64 depth below 2^-149 rounds to 0.0f, yet the reference
+        // updates every voxel of its pixel with l2 < tdist + z, those behind the camera included.  zdf (0 then) serves the band
+        // arithmetic only.  Depths whose z * u can overflow go the exact way.
         const float zdf = -(float)dval[j];
-        const bool hit = inside[j] & (zdf > 0.0f);
+        const bool hit = inside[j] & (dval[j] < (DepthT)0);
+        const bool far = hit & depth_overflows(dval[j]);
         bool ok, redo, freespace;
         if (PINHOLE) {
             const float d32 = zdf - (l2f[j] - p.tdist_f);            // ~ sd + tdist
             const float band = fmaf(fabsf(l2f[j]), 2e-6f, 1e-5f);
             ok = hit & (d32 > 0.0f);
-            redo = amb[j] | (hit & (fabsf(d32) <= band));
+            redo = amb[j] | far | (hit & (fabsf(d32) <= band));
             freespace = d32 > 2.0f * p.tdist_f + band;               // sd > tdist for certain
         } else {
             ok = hit;
-            redo = amb[j];
+            redo = amb[j] | far;
             freespace = false;
         }
         float m = p.ts_f;
@@ -803,7 +814,9 @@ __global__ __launch_bounds__(256) void depth_pyramid_kernel(const PyrViews pv, i
     auto zval = [&](int x, int y) {
         if (x >= W || y >= H) return 0.0f;
         const float z = -(float)depth[(size_t)y * W + x];
-        return z > 0.0f ? z : 0.0f;                       // invalid (0, NaN) pixels never update a voxel
+        // invalid (0, NaN, wrong sign) pixels never update a voxel.  A float64 depth below 2^-149 counts as 0 here although it is
+        // valid: it only updates voxels with l2 < tdist + z, and bounds_culled culls a brick only when tdist + margin <= l2min
+        return z > 0.0f ? z : 0.0f;
     };
     float m = fmaxf(fmaxf(zval(px, py), zval(px + 1, py)), fmaxf(zval(px, py + 1), zval(px + 1, py + 1)));
     {

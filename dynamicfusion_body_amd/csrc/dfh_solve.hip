@@ -645,6 +645,8 @@ __device__ __forceinline__ bool associate_views(const AssocParams &p, const Asso
                 double c0, c1, c2, d2;
                 bool good = associate_backproject(p, views[vi_[j]].lw_cam, views[vi_[j]].Rinv, z[j], u[j], vv[j], xp, c0, c1, c2, d2);
                 if (good && p.max_dist > 0.0) good = d2 <= p.max_dist * p.max_dist;
+                // (strict, best starts at +inf: a depth of -inf -- c and d2 inf or NaN -- or a d2 that overflows is no data row, with
+                // or without the gate; oracle/gn_np.py:associate_depth states the same rule)
                 if (good && d2 < best) { best = d2; c[0] = c0; c[1] = c1; c[2] = c2; any = true; }
             }
         }

@@ -82,6 +82,14 @@ def brick_masks(workspace, res, x_range=None):
     return raw[raw.numel() - tail:raw.numel() - tail + n].view(nb)
 
 
+def integrate_workspace_params_doubles(workspace, n_views):
+    """The views' parameter records the last multi-view sweep through `workspace` uploaded, as an (n_views, record) float64 view:
+    the FIRST region of the workspace (dfh_integrate_multi_workspace_bytes(n) bytes, rounded to 16; a record starts with K, K^-1 and
+    lw).  Single-view sweeps never write it.  For tests that must know which path a call took."""
+    rec = _lib.load().dfh_integrate_multi_workspace_bytes(2) // 16           # doubles per record (two records need no padding)
+    return workspace.view(torch.float64)[:rec * int(n_views)].view(int(n_views), rec)
+
+
 def integrate_depth(T, Wt, depth, K, Kinv, lw, scale, center, tdist, wmax=100.0, tsdf_res=None,
                     res=None, x_range=None, workspace=None):
     """K1 = FusionDM.fuseDepths (reference core/fusion_dm.py:180-217) on device tensors.

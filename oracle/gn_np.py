@@ -247,7 +247,7 @@ def associate_depth(points_idx, K, Kinv, lw_cam, dm, scale, center, half):
     reference's primitives: index -> world (fusion_dm.py:191), world -> camera (:193), pixel
     (util.py:317-320), nearest pixel round-half-even and z = -dm (:196), back-projection
     K^-1 (z [u,v,1]) (:198-200), then back to index space through the inverse extrinsic.
-    Returns (corr_idx (S,3), valid (S,))."""
+    Returns (corr_idx (S,3), valid (S,)); valid = visible, z > 0 and a finite correspondence."""
     P = np.asarray(points_idx, dtype=np.float64)
     H, W = dm.shape
     world = scale * (P - half) + center
@@ -263,6 +263,9 @@ def associate_depth(points_idx, K, Kinv, lw_cam, dm, scale, center, half):
     ccam = uc @ np.asarray(Kinv, dtype=np.float64).T
     cworld = (ccam - t) @ np.linalg.inv(R).T
     cidx = (cworld - center) / scale + half
+    # a non-finite correspondence (a depth of -inf: z = inf, z u = inf or NaN) is not a data row -- this project's own rule, the
+    # reference associates mesh to mesh; the device drops such a sample gated or not (csrc/dfh_solve.hip: associate_views)
+    valid = valid & np.isfinite(cidx).all(axis=1)
     return np.where(valid[:, None], cidx, 0.0), valid
 
 
@@ -281,7 +284,7 @@ def associate_depth_views(points_idx, K, Kinv, lw_cams, dms, scale, center, half
         d2 = d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1] + d[:, 2] * d[:, 2]
         if max_dist > 0:
             ok = ok & (d2 <= max_dist * max_dist)
-        take = ok & (d2 < best)
+        take = ok & (d2 < best)          # (strict, best starts at inf: a finite c whose squared distance overflows is not taken either)
         best = np.where(take, d2, best)
         corr = np.where(take[:, None], c, corr)
         view = np.where(take, v, view)
