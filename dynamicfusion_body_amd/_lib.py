@@ -13,7 +13,7 @@ LIB_PATH = os.environ.get("DFH_LIB_PATH") or os.path.join(_PKG, "libdfusion_hip.
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "dfusion_hip.h")
 
 F32, F64 = 0, 1
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 _c_double_p = ctypes.POINTER(ctypes.c_double)
 _c_int_p = ctypes.POINTER(ctypes.c_int)
@@ -48,9 +48,38 @@ class SolveParams(ctypes.Structure):
                 ("global_lm", _dbl), ("global_xi_out", _vp), ("global_scratch", _vp), ("global_scratch_bytes", ctypes.c_size_t)]
 
 
+class Slab(ctypes.Structure):
+    """dfh_slab: planes [x0, x1) of a res grid."""
+    _fields_ = [("res", _int * 3), ("x0", _int), ("x1", _int)]
+
+
+class Volume(ctypes.Structure):
+    """dfh_volume: the TSDF / weight pair on a slab."""
+    _fields_ = [("tsdf", _vp), ("tsdf_w", _vp), ("dtype", _int), ("slab", Slab)]
+
+
+class Live(ctypes.Structure):
+    """dfh_live: the whole live volume."""
+    _fields_ = [("data", _vp), ("dtype", _int), ("res", _int * 3)]
+
+
+class DepthViews(ctypes.Structure):
+    """dfh_depth_views: n_views depth maps of one size through one camera (depth, lw: host arrays the caller keeps alive)."""
+    _fields_ = [("n_views", _int), ("depth", ctypes.POINTER(_vp)), ("depth_dtype", _int), ("H", _int), ("W", _int),
+                ("K", _dbl * 9), ("Kinv", _dbl * 9), ("lw", _c_double_p), ("scale", _dbl), ("center", _dbl * 3), ("tsdf_res", _int)]
+
+
+class Nodes(ctypes.Structure):
+    """dfh_nodes: the deformation graph's nodes as K3 reads them."""
+    _fields_ = [("pos", _vp), ("dq", _vp), ("w", _vp), ("n_nodes", _int), ("knn", _int)]
+
+
 _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
-STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams}
+_slab_p = ctypes.POINTER(Slab)
+_volume_p = ctypes.POINTER(Volume)
+STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams, "dfh_slab": Slab,
+           "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -58,25 +87,15 @@ _SIGNATURES = {
     "dfh_stream_synchronize": (_int, [_vp]),
     "dfh_set_option": (_int, [ctypes.c_char_p, ctypes.c_long]),
     "dfh_get_option": (ctypes.c_long, [ctypes.c_char_p]),
-    "dfh_integrate_workspace_bytes": (ctypes.c_size_t, [_int, _int, _int, _c_int_p, _int, _int]),
-    "dfh_integrate_depth": (_int, [_vp, _vp, _int, _c_int_p, _int, _int, _int, _vp, _int, _int, _int,
-                                   _c_double_p, _c_double_p, _c_double_p, _dbl, _c_double_p, _dbl, _dbl, _vp, ctypes.c_size_t, _vp]),
-    "dfh_integrate_depth_path": (_int, [_int, _c_int_p, _int, _int, _int, _int, _int]),
-    "dfh_integrate_depth_ocl": (_int, [_vp, _vp, _c_int_p, _int, _int, _vp, _int, _int, ctypes.POINTER(ctypes.c_float),
-                                       ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float, _vp]),
+    "dfh_integrate_workspace_bytes": (ctypes.c_size_t, [_int, _int, _int, _slab_p]),
     "dfh_integrate_multi_workspace_bytes": (ctypes.c_size_t, [_int]),
-    "dfh_integrate_depth_multi": (_int, [_vp, _vp, _int, _c_int_p, _int, _int, _int, _int, ctypes.POINTER(ctypes.c_void_p), _int, _int,
-                                         _int, _c_double_p, _c_double_p, _c_double_p, _dbl, _c_double_p, _dbl, _dbl, _vp,
-                                         ctypes.c_size_t, _vp]),
-    "dfh_integrate_depth_multi_fresh": (_int, [_vp, _vp, _int, _c_int_p, _int, _int, _int, _dbl, _int, ctypes.POINTER(ctypes.c_void_p), _int, _int,
-                                         _int, _c_double_p, _c_double_p, _c_double_p, _dbl, _c_double_p, _dbl, _dbl, _vp,
-                                         ctypes.c_size_t, _vp]),
-    "dfh_fuse_volume_rigid": (_int, [_vp, _vp, _int, _c_int_p, _int, _int, _vp, _int, _c_int_p,
-                                     _c_double_p, _dbl, _dbl, _vp]),
-    "dfh_dqb_workspace_bytes": (ctypes.c_size_t, [_c_int_p, _int, _int]),
-    "dfh_dqb_workspace_bytes_cached": (ctypes.c_size_t, [_c_int_p, _int, _int, _int, _int, _int]),
-    "dfh_fuse_volume_dqb": (_int, [_vp, _vp, _int, _c_int_p, _int, _int, _vp, _int, _c_int_p, _vp, _vp, _vp, _int,
-                                   _int, _c_double_p, _dbl, _dbl, _vp, ctypes.c_size_t, _int, _vp]),
+    "dfh_integrate_depth": (_int, [_volume_p, ctypes.POINTER(DepthViews), _dbl, _dbl, _c_double_p, _vp, ctypes.c_size_t, _vp]),
+    "dfh_integrate_depth_path": (_int, [_int, _slab_p, _int, _int, _int]),
+    "dfh_integrate_depth_ocl": (_int, [_volume_p, _vp, _int, _int, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_float), ctypes.c_float, ctypes.c_float, _vp]),
+    "dfh_fuse_volume_rigid": (_int, [_volume_p, ctypes.POINTER(Live), _c_double_p, _dbl, _dbl, _vp]),
+    "dfh_dqb_workspace_bytes": (ctypes.c_size_t, [_slab_p]),
+    "dfh_dqb_workspace_bytes_cached": (ctypes.c_size_t, [_slab_p, _int, _int, _int]),
+    "dfh_fuse_volume_dqb": (_int, [_volume_p, ctypes.POINTER(Live), ctypes.POINTER(Nodes), _c_double_p, _dbl, _dbl, _vp, ctypes.c_size_t, _int, _vp]),
     "dfh_residual_rigid": (_int, [_vp, _vp, _vp, _int, _c_double_p, _vp, _vp]),
     "dfh_gn_build_rigid": (_int, [_vp, _vp, _vp, _vp, _int, _c_double_p, _vp, _vp]),
     "dfh_residual_data": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _int, _c_double_p, _vp, _vp]),
@@ -87,9 +106,9 @@ _SIGNATURES = {
     "dfh_graph_unsupported": (_int, [_vp, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
     "dfh_dq_blend_points": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp]),
     "dfh_sample_knn": (_int, [_vp, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
-    "dfh_dqb_skip_layout": (_int, [_c_int_p, _int, _int, _c_int_p, _int, _int, ctypes.POINTER(ctypes.c_size_t)]),
-    "dfh_dqb_build_candidates": (_int, [_c_int_p, _int, _int, _vp, _int, _int, _vp, ctypes.c_size_t, _vp]),
-    "dfh_sample_knn_bricks": (_int, [_vp, _int, _vp, _vp, _int, _int, _c_int_p, _int, _int, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
+    "dfh_dqb_skip_layout": (_int, [_slab_p, _c_int_p, _int, _int, ctypes.POINTER(ctypes.c_size_t)]),
+    "dfh_dqb_build_candidates": (_int, [_slab_p, _vp, _int, _int, _vp, ctypes.c_size_t, _vp]),
+    "dfh_sample_knn_bricks": (_int, [_vp, _int, _vp, _vp, _int, _int, _slab_p, _vp, ctypes.c_size_t, _vp, _vp, _vp]),
     "dfh_permute_samples": (_int, [_vp, _int, _int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dfh_gn_partial_doubles": (ctypes.c_size_t, [_int]),
     "dfh_gn_views_bytes": (ctypes.c_size_t, [_int, _int, _int, _int]),
@@ -231,3 +250,9 @@ def darr(values, n):
 def iarr(values):
     vals = [int(v) for v in values]
     return (ctypes.c_int * len(vals))(*vals)
+
+
+def slab(res, x_range=None):
+    """dfh_slab: planes `x_range` (default: all) of a `res` grid."""
+    x0, x1 = (0, res[0]) if x_range is None else x_range
+    return Slab(iarr(res), int(x0), int(x1))

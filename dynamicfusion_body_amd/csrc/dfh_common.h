@@ -25,6 +25,22 @@ int fail(int code, const char *fmt, ...);
         if (!(cond)) return ::dfh::fail(DFH_E_BADARG, __VA_ARGS__); \
     } while (0)
 
+// ---- what every K1-K3 entry point checks of its slab and of its volume pair (`what` names the entry point) ----------
+// An empty slab (x0 == x1) is valid: the callers return DFH_OK (size queries 0) for it before they launch anything.
+inline int check_slab(const char *what, const dfh_slab *s) {
+    DFH_REQUIRE(s, "%s: null slab", what);
+    DFH_REQUIRE(s->res[0] > 0 && s->res[1] > 0 && s->res[2] > 0, "%s: bad grid %dx%dx%d", what, s->res[0], s->res[1], s->res[2]);
+    DFH_REQUIRE(0 <= s->x0 && s->x0 <= s->x1 && s->x1 <= s->res[0], "%s: slab [%d,%d) outside [0,%d)", what, s->x0, s->x1, s->res[0]);
+    DFH_REQUIRE(s->x1 - s->x0 <= 65535, "%s: slab has more than 65535 planes", what);
+    return DFH_OK;
+}
+
+inline int check_volume(const char *what, const dfh_volume *v) {
+    DFH_REQUIRE(v && v->tsdf && v->tsdf_w, "%s: null volume", what);
+    DFH_REQUIRE(v->dtype == DFH_F32 || v->dtype == DFH_F64, "%s: bad volume dtype %d", what, v->dtype);
+    return check_slab(what, &v->slab);
+}
+
 // ---- small fixed-size parameter blocks passed by value to kernels ---------------------
 struct Mat3 { double m[9]; };
 struct Mat34 { double m[12]; };

@@ -1577,12 +1577,35 @@ static int launch_dqb(void *tsdf, void *tsdf_w, const void *live, const double *
     return DFH_OK;
 }
 
-static size_t cand_bytes(const int res[3], int x0, int x1) {
-    int nbx, nby, nbz;
-    nbx = (x1 - x0 + kBX - 1) / kBX;
-    nby = (res[1] + kBY - 1) / kBY;
-    nbz = (res[2] + kBZ - 1) / kBZ;
-    return (((size_t)nbx * nby * nbz * (kCap + 1) * sizeof(int)) + 15) & ~(size_t)15;
+// The grid, live-grid and slab fields of a K2 / K3 parameter block (live_res == nullptr: calls that sample no live volume).
+template <typename Params>
+static void set_grid(Params &p, const dfh_slab &sl, const int *live_res) {
+    p.X = sl.res[0]; p.Y = sl.res[1]; p.Z = sl.res[2];
+    if (live_res) { p.LX = live_res[0]; p.LY = live_res[1]; p.LZ = live_res[2]; }
+    p.x0 = sl.x0; p.nx = sl.x1 - sl.x0;
+}
+
+// ... and K3's node counts and bricks per axis on top (everything but lw, tdist and wmax)
+static DqbParams dqb_params(const dfh_slab &sl, const int *live_res, int n_nodes, int knn) {
+    DqbParams p = {};
+    set_grid(p, sl, live_res);
+    p.N = n_nodes; p.k = knn;
+    p.nbx = (p.nx + kBX - 1) / kBX;
+    p.nby = (p.Y + kBY - 1) / kBY;
+    p.nbz = (p.Z + kBZ - 1) / kBZ;
+    return p;
+}
+
+static size_t cand_bytes(const dfh_slab &sl) {
+    const DqbParams p = dqb_params(sl, nullptr, 0, 0);
+    return (((size_t)p.nbx * p.nby * p.nbz * (kCap + 1) * sizeof(int)) + 15) & ~(size_t)15;
+}
+
+static int check_live(const char *what, const dfh_live *l) {
+    DFH_REQUIRE(l && l->data, "%s: null live volume", what);
+    DFH_REQUIRE(l->dtype == DFH_F32 || l->dtype == DFH_F64, "%s: bad live dtype %d", what, l->dtype);
+    DFH_REQUIRE(l->res[0] > 0 && l->res[1] > 0 && l->res[2] > 0, "%s: bad live grid", what);
+    return DFH_OK;
 }
 
 // k nearest nodes + blend weights of arbitrary points through the bricks' candidate lists (what sample_knn_kernel of
@@ -1641,35 +1664,26 @@ __global__ __launch_bounds__(256) void sample_knn_bricks_kernel(const double *__
     }
 }
 
-static void brick_counts(const int res[3], int x0, int x1, int &nbx, int &nby, int &nbz) {
-    nbx = (x1 - x0 + kBX - 1) / kBX;
-    nby = (res[1] + kBY - 1) / kBY;
-    nbz = (res[2] + kBZ - 1) / kBZ;
-}
-
 }  // namespace dfh
 
-extern "C" int dfh_fuse_volume_rigid(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int x0, int x1,
-                                     const void *live, int live_dtype, const int live_res[3],
-                                     const double lw_dq[8], double tdist, double wmax, void *stream) {
+extern "C" int dfh_fuse_volume_rigid(const dfh_volume *vol, const dfh_live *live_vol, const double lw_dq[8], double tdist, double wmax,
+                                     void *stream) {
     using namespace dfh;
-    DFH_REQUIRE(tsdf && tsdf_w && live && res && live_res && lw_dq, "dfh_fuse_volume_rigid: null pointer");
-    DFH_REQUIRE(vol_dtype == DFH_F32 || vol_dtype == DFH_F64, "dfh_fuse_volume_rigid: bad vol_dtype %d", vol_dtype);
-    DFH_REQUIRE(live_dtype == DFH_F32 || live_dtype == DFH_F64, "dfh_fuse_volume_rigid: bad live_dtype %d", live_dtype);
-    DFH_REQUIRE(res[0] > 0 && res[1] > 0 && res[2] > 0, "dfh_fuse_volume_rigid: bad grid");
-    DFH_REQUIRE(live_res[0] > 0 && live_res[1] > 0 && live_res[2] > 0, "dfh_fuse_volume_rigid: bad live grid");
-    DFH_REQUIRE((long)live_res[0] * live_res[1] * live_res[2] < (1L << 40), "dfh_fuse_volume_rigid: live grid too large");
-    DFH_REQUIRE(0 <= x0 && x0 <= x1 && x1 <= res[0], "dfh_fuse_volume_rigid: slab [%d,%d) outside [0,%d)", x0, x1, res[0]);
-    DFH_REQUIRE(x1 - x0 <= 65535, "dfh_fuse_volume_rigid: slab has more than 65535 planes");
-    if (x1 == x0) return DFH_OK;
+    int rc = check_volume("dfh_fuse_volume_rigid", vol);
+    if (rc == DFH_OK) rc = check_live("dfh_fuse_volume_rigid", live_vol);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(lw_dq, "dfh_fuse_volume_rigid: null pointer");
+    DFH_REQUIRE((long)live_vol->res[0] * live_vol->res[1] * live_vol->res[2] < (1L << 40), "dfh_fuse_volume_rigid: live grid too large");
+    if (vol->slab.x1 == vol->slab.x0) return DFH_OK;
+    void *tsdf = vol->tsdf, *tsdf_w = vol->tsdf_w;
+    const void *live = live_vol->data;
+    const int vol_dtype = vol->dtype, live_dtype = live_vol->dtype;
     RigidParams p;
     for (int i = 0; i < 8; ++i) p.lw.q[i] = lw_dq[i];
     p.tdist = tdist; p.wmax = wmax;
-    p.X = res[0]; p.Y = res[1]; p.Z = res[2];
-    p.LX = live_res[0]; p.LY = live_res[1]; p.LZ = live_res[2];
-    p.x0 = x0; p.nx = x1 - x0;
+    set_grid(p, vol->slab, live_vol->res);
     const size_t esz = vol_dtype == DFH_F32 ? 4 : 8;
-    const bool vec4 = (res[2] % 4 == 0) && ((uintptr_t)tsdf % (4 * esz) == 0) && ((uintptr_t)tsdf_w % (4 * esz) == 0);
+    const bool vec4 = (p.Z % 4 == 0) && ((uintptr_t)tsdf % (4 * esz) == 0) && ((uintptr_t)tsdf_w % (4 * esz) == 0);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (vol_dtype == DFH_F32 && vec4 && !on(opt().k2_exact)) {
         RigidFastParams f;
@@ -1696,53 +1710,50 @@ extern "C" int dfh_fuse_volume_rigid(void *tsdf, void *tsdf_w, int vol_dtype, co
     return launch_rigid<double, double>(tsdf, tsdf_w, live, p, vec4, s);
 }
 
-extern "C" size_t dfh_dqb_workspace_bytes(const int res[3], int x0, int x1) {
-    if (!res || x1 <= x0) return 0;
-    return dfh::cand_bytes(res, x0, x1);
+extern "C" size_t dfh_dqb_workspace_bytes(const dfh_slab *slab) {
+    if (dfh::check_slab("dfh_dqb_workspace_bytes", slab) != DFH_OK || slab->x1 == slab->x0) return 0;
+    return dfh::cand_bytes(*slab);
 }
 
-extern "C" size_t dfh_dqb_workspace_bytes_cached(const int res[3], int x0, int x1, int knn, int n_nodes, int level) {
-    if (!res || x1 <= x0) return 0;
-    const size_t base = dfh::cand_bytes(res, x0, x1);
+extern "C" size_t dfh_dqb_workspace_bytes_cached(const dfh_slab *slab, int knn, int n_nodes, int level) {
+    if (dfh::check_slab("dfh_dqb_workspace_bytes_cached", slab) != DFH_OK || slab->x1 == slab->x0) return 0;
+    const size_t base = dfh::cand_bytes(*slab);
     if (level < 1 || knn < 1 || knn > dfh::kKMax || n_nodes > 65536) return base;         // indices are kept as 16-bit
-    const size_t nvox = (size_t)(x1 - x0) * res[1] * res[2];
+    const size_t nvox = (size_t)(slab->x1 - slab->x0) * slab->res[1] * slab->res[2];
     const size_t idx = (nvox * knn * sizeof(unsigned short) + 15) & ~(size_t)15;
     return base + idx + (level >= 2 ? nvox * (knn + 1) * sizeof(double) : 0);
 }
 
-extern "C" int dfh_fuse_volume_dqb(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int x0, int x1,
-                                   const void *live, int live_dtype, const int live_res[3],
-                                   const double *node_pos, const double *node_dq, const double *node_w, int n_nodes,
-                                   int knn, const double lw_dq[8], double tdist, double wmax,
-                                   void *workspace, size_t workspace_bytes, int rebuild_candidates, void *stream) {
+extern "C" int dfh_fuse_volume_dqb(const dfh_volume *vol, const dfh_live *live_vol, const dfh_nodes *nodes, const double lw_dq[8],
+                                   double tdist, double wmax, void *workspace, size_t workspace_bytes, int rebuild_candidates,
+                                   void *stream) {
     using namespace dfh;
-    DFH_REQUIRE(tsdf && tsdf_w && live && res && live_res && lw_dq && node_pos && node_dq && node_w,
-                "dfh_fuse_volume_dqb: null pointer");
-    DFH_REQUIRE(vol_dtype == DFH_F32 || vol_dtype == DFH_F64, "dfh_fuse_volume_dqb: bad vol_dtype %d", vol_dtype);
-    DFH_REQUIRE(live_dtype == DFH_F32 || live_dtype == DFH_F64, "dfh_fuse_volume_dqb: bad live_dtype %d", live_dtype);
-    DFH_REQUIRE(res[0] > 0 && res[1] > 0 && res[2] > 0, "dfh_fuse_volume_dqb: bad grid");
-    DFH_REQUIRE(live_res[0] > 0 && live_res[1] > 0 && live_res[2] > 0, "dfh_fuse_volume_dqb: bad live grid");
-    DFH_REQUIRE(0 <= x0 && x0 <= x1 && x1 <= res[0], "dfh_fuse_volume_dqb: slab [%d,%d) outside [0,%d)", x0, x1, res[0]);
+    int rc = check_volume("dfh_fuse_volume_dqb", vol);
+    if (rc == DFH_OK) rc = check_live("dfh_fuse_volume_dqb", live_vol);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(nodes && lw_dq && nodes->pos && nodes->dq && nodes->w, "dfh_fuse_volume_dqb: null pointer");
+    const int knn = nodes->knn, n_nodes = nodes->n_nodes;
     DFH_REQUIRE(knn >= 1 && knn <= kKMax, "dfh_fuse_volume_dqb: knn=%d outside [1,%d]", knn, kKMax);
     DFH_REQUIRE(n_nodes >= knn, "dfh_fuse_volume_dqb: %d nodes < knn=%d", n_nodes, knn);
-    if (x1 == x0) return DFH_OK;
-    DFH_REQUIRE(workspace && workspace_bytes >= dfh_dqb_workspace_bytes(res, x0, x1),
-                "dfh_fuse_volume_dqb: workspace too small (need %zu bytes)", dfh_dqb_workspace_bytes(res, x0, x1));
-    DqbParams p;
+    const dfh_slab *sl = &vol->slab;
+    if (sl->x1 == sl->x0) return DFH_OK;
+    DFH_REQUIRE(workspace && workspace_bytes >= dfh_dqb_workspace_bytes(sl),
+                "dfh_fuse_volume_dqb: workspace too small (need %zu bytes)", dfh_dqb_workspace_bytes(sl));
+    void *tsdf = vol->tsdf, *tsdf_w = vol->tsdf_w;
+    const void *live = live_vol->data;
+    const double *node_pos = nodes->pos, *node_dq = nodes->dq, *node_w = nodes->w;
+    const int vol_dtype = vol->dtype, live_dtype = live_vol->dtype;
+    DqbParams p = dqb_params(*sl, live_vol->res, n_nodes, knn);
     for (int i = 0; i < 8; ++i) p.lw.q[i] = lw_dq[i];
     p.tdist = tdist; p.wmax = wmax;
-    p.X = res[0]; p.Y = res[1]; p.Z = res[2];
-    p.LX = live_res[0]; p.LY = live_res[1]; p.LZ = live_res[2];
-    p.x0 = x0; p.nx = x1 - x0; p.N = n_nodes; p.k = knn;
-    brick_counts(res, x0, x1, p.nbx, p.nby, p.nbz);
     const long nbricks = (long)p.nbx * p.nby * p.nbz;
     DFH_REQUIRE(nbricks < (1L << 31), "dfh_fuse_volume_dqb: too many bricks");
     hipStream_t s = static_cast<hipStream_t>(stream);
     int *cand = static_cast<int *>(workspace);
     // a workspace of dfh_dqb_workspace_bytes_cached() also keeps every voxel's k node indices
-    const size_t base = cand_bytes(res, x0, x1);
-    const size_t cached1 = dfh_dqb_workspace_bytes_cached(res, x0, x1, knn, n_nodes, 1);
-    const size_t cached2 = dfh_dqb_workspace_bytes_cached(res, x0, x1, knn, n_nodes, 2);
+    const size_t base = cand_bytes(*sl);
+    const size_t cached1 = dfh_dqb_workspace_bytes_cached(sl, knn, n_nodes, 1);
+    const size_t cached2 = dfh_dqb_workspace_bytes_cached(sl, knn, n_nodes, 2);
     const bool has_idx = cached1 > base && workspace_bytes >= cached1 && !on(opt().k3_no_cache);
     const bool has_w = has_idx && workspace_bytes >= cached2;
     unsigned short *knn_cache = has_idx ? reinterpret_cast<unsigned short *>(static_cast<char *>(workspace) + base) : nullptr;
@@ -1780,44 +1791,40 @@ extern "C" int dfh_fuse_volume_dqb(void *tsdf, void *tsdf_w, int vol_dtype, cons
     return launch_dqb<double, double>(tsdf, tsdf_w, live, node_pos, node_dq, node_w, cand, knn_cache, w_cache, mode, p, s);
 }
 
-extern "C" int dfh_dqb_skip_layout(const int res[3], int x0, int x1, const int live_res[3], int knn, int n_nodes, size_t out[13]) {
+extern "C" int dfh_dqb_skip_layout(const dfh_slab *slab, const int live_res[3], int knn, int n_nodes, size_t out[13]) {
     using namespace dfh;
-    DFH_REQUIRE(res && live_res && out, "dfh_dqb_skip_layout: null pointer");
-    DFH_REQUIRE(res[0] > 0 && res[1] > 0 && res[2] > 0 && 0 <= x0 && x0 < x1 && x1 <= res[0], "dfh_dqb_skip_layout: bad grid / slab");
+    const int rc = check_slab("dfh_dqb_skip_layout", slab);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(live_res && out, "dfh_dqb_skip_layout: null pointer");
     DFH_REQUIRE(knn == 4, "dfh_dqb_skip_layout: the skip belongs to the knn = 4 float32 path");
-    DqbParams p = {};
-    p.X = res[0]; p.Y = res[1]; p.Z = res[2];
-    p.LX = live_res[0]; p.LY = live_res[1]; p.LZ = live_res[2];
-    p.x0 = x0; p.nx = x1 - x0; p.N = n_nodes; p.k = knn;
-    brick_counts(res, x0, x1, p.nbx, p.nby, p.nbz);
-    const size_t cached1 = dfh_dqb_workspace_bytes_cached(res, x0, x1, knn, n_nodes, 1);
-    const size_t cached2 = dfh_dqb_workspace_bytes_cached(res, x0, x1, knn, n_nodes, 2);
+    for (int i = 0; i < 13; ++i) out[i] = 0;
+    if (slab->x1 == slab->x0) return DFH_OK;                            // (no voxels, no tables: out[11] = 0)
+    const DqbParams p = dqb_params(*slab, live_res, n_nodes, knn);
+    const size_t cached1 = dfh_dqb_workspace_bytes_cached(slab, knn, n_nodes, 1);
+    const size_t cached2 = dfh_dqb_workspace_bytes_cached(slab, knn, n_nodes, 2);
     DFH_REQUIRE(cached2 > cached1, "dfh_dqb_skip_layout: no level-2 workspace for these sizes");
     DqbSkip k = {};
     size_t used = 0;
     const bool fits = skip_layout(p, reinterpret_cast<double *>(cached1), k, &used);        // (pointer arithmetic on offsets only)
     out[0] = reinterpret_cast<size_t>(k.U); out[1] = reinterpret_cast<size_t>(k.S); out[2] = reinterpret_cast<size_t>(k.mb);
-    out[3] = reinterpret_cast<size_t>(k.db); out[4] = 0; out[5] = 0;
+    out[3] = reinterpret_cast<size_t>(k.db);
     out[6] = (size_t)k.CX; out[7] = (size_t)k.CY; out[8] = (size_t)k.WZ; out[9] = (size_t)k.SCX; out[10] = (size_t)k.SCY;
     out[11] = fits && skip_sizes_ok(p) ? 1 : 0;
     out[12] = reinterpret_cast<size_t>(k.used);
     return DFH_OK;
 }
 
-extern "C" int dfh_dqb_build_candidates(const int res[3], int x0, int x1, const double *node_pos, int n_nodes, int knn,
+extern "C" int dfh_dqb_build_candidates(const dfh_slab *slab, const double *node_pos, int n_nodes, int knn,
                                         void *workspace, size_t workspace_bytes, void *stream) {
     using namespace dfh;
-    DFH_REQUIRE(res && node_pos, "dfh_dqb_build_candidates: null pointer");
-    DFH_REQUIRE(res[0] > 0 && res[1] > 0 && res[2] > 0, "dfh_dqb_build_candidates: bad grid");
-    DFH_REQUIRE(0 <= x0 && x0 <= x1 && x1 <= res[0], "dfh_dqb_build_candidates: slab [%d,%d) outside [0,%d)", x0, x1, res[0]);
+    const int rc = check_slab("dfh_dqb_build_candidates", slab);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(node_pos, "dfh_dqb_build_candidates: null pointer");
     DFH_REQUIRE(knn >= 1 && knn <= kKMax && n_nodes >= knn, "dfh_dqb_build_candidates: knn=%d, %d nodes", knn, n_nodes);
-    if (x1 == x0) return DFH_OK;
-    DFH_REQUIRE(workspace && workspace_bytes >= dfh_dqb_workspace_bytes(res, x0, x1),
-                "dfh_dqb_build_candidates: workspace too small (need %zu bytes)", dfh_dqb_workspace_bytes(res, x0, x1));
-    DqbParams p = {};
-    p.X = res[0]; p.Y = res[1]; p.Z = res[2];
-    p.x0 = x0; p.nx = x1 - x0; p.N = n_nodes; p.k = knn;
-    brick_counts(res, x0, x1, p.nbx, p.nby, p.nbz);
+    if (slab->x1 == slab->x0) return DFH_OK;
+    DFH_REQUIRE(workspace && workspace_bytes >= dfh_dqb_workspace_bytes(slab),
+                "dfh_dqb_build_candidates: workspace too small (need %zu bytes)", dfh_dqb_workspace_bytes(slab));
+    const DqbParams p = dqb_params(*slab, nullptr, n_nodes, knn);
     const long nbricks = (long)p.nbx * p.nby * p.nbz;
     DFH_REQUIRE(nbricks < (1L << 31), "dfh_dqb_build_candidates: too many bricks");
     hipLaunchKernelGGL(dqb_candidates_kernel, dim3((unsigned)((nbricks + 255) / 256)), dim3(256), 0, static_cast<hipStream_t>(stream),
@@ -1827,20 +1834,19 @@ extern "C" int dfh_dqb_build_candidates(const int res[3], int x0, int x1, const 
 }
 
 extern "C" int dfh_sample_knn_bricks(const double *sample_pos, int n_samples, const double *node_pos, const double *node_w,
-                                     int n_nodes, int knn, const int res[3], int x0, int x1, const void *workspace,
+                                     int n_nodes, int knn, const dfh_slab *slab, const void *workspace,
                                      size_t workspace_bytes, int *nbr_out, double *weights_out, void *stream) {
     using namespace dfh;
+    const int rc = check_slab("dfh_sample_knn_bricks", slab);
+    if (rc != DFH_OK) return rc;
     DFH_REQUIRE(n_samples >= 0, "dfh_sample_knn_bricks: negative sample count");
     if (n_samples == 0) return DFH_OK;
-    DFH_REQUIRE(sample_pos && node_pos && node_w && res && nbr_out && weights_out, "dfh_sample_knn_bricks: null pointer");
+    DFH_REQUIRE(sample_pos && node_pos && node_w && nbr_out && weights_out, "dfh_sample_knn_bricks: null pointer");
     DFH_REQUIRE(knn >= 1 && knn <= kKMax && n_nodes >= knn, "dfh_sample_knn_bricks: knn=%d, %d nodes", knn, n_nodes);
-    DFH_REQUIRE(res[0] > 0 && res[1] > 0 && res[2] > 0 && 0 <= x0 && x0 < x1 && x1 <= res[0], "dfh_sample_knn_bricks: bad grid / slab");
-    DFH_REQUIRE(workspace && workspace_bytes >= dfh_dqb_workspace_bytes(res, x0, x1),
-                "dfh_sample_knn_bricks: workspace too small (need %zu bytes)", dfh_dqb_workspace_bytes(res, x0, x1));
-    DqbParams p = {};
-    p.X = res[0]; p.Y = res[1]; p.Z = res[2];
-    p.x0 = x0; p.nx = x1 - x0; p.N = n_nodes; p.k = knn;
-    brick_counts(res, x0, x1, p.nbx, p.nby, p.nbz);
+    if (slab->x1 == slab->x0) return DFH_OK;                            // (no lattice, no lists: nothing is written)
+    DFH_REQUIRE(workspace && workspace_bytes >= dfh_dqb_workspace_bytes(slab),
+                "dfh_sample_knn_bricks: workspace too small (need %zu bytes)", dfh_dqb_workspace_bytes(slab));
+    const DqbParams p = dqb_params(*slab, nullptr, n_nodes, knn);
     dim3 grid((unsigned)((n_samples + 255) / 256)), block(256);
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (knn <= 4)

@@ -780,7 +780,7 @@ __global__ __launch_bounds__(256) void fill_pair_kernel(T *__restrict__ a, T va,
     for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { a[i] = va; b[i] = vb; }
 }
 
-// Parameters of up to kParamChunk views from the kernel-argument segment into device memory (see dfh_integrate_depth_multi)
+// Parameters of up to kParamChunk views from the kernel-argument segment into device memory (see integrate_several)
 constexpr int kParamChunk = 6;
 struct ParamChunk {
     IntegrateParams v[kParamChunk];
@@ -1018,18 +1018,17 @@ static void fold_affine(IntegrateParams &p) {
     p.wmax_f = (float)p.wmax;
 }
 
-// One view's parameters (shared by the single- and the multi-view entry points); returns whether K is a pinhole matrix.
-static bool fill_params(IntegrateParams &p, const int res[3], int tsdf_res, int x0, int x1, int H, int W, const double K[9],
-                        const double Kinv[9], const double lw[12], double scale, const double center[3], double tdist,
-                        double wmax, bool vec4) {
+// One view's parameters (shared by the one-view and the several-view sweeps); returns whether K is a pinhole matrix.
+static bool fill_params(IntegrateParams &p, const dfh_slab &sl, const dfh_depth_views &vw, int view, double tdist, double wmax, bool vec4) {
+    const double *K = vw.K, *Kinv = vw.Kinv;
     for (int i = 0; i < 9; ++i) { p.K.m[i] = K[i]; p.Kinv.m[i] = Kinv[i]; }
-    for (int i = 0; i < 12; ++i) p.lw.m[i] = lw[i];
-    p.scale = scale; p.cx = center[0]; p.cy = center[1]; p.cz = center[2];
-    p.half = (double)tsdf_res / 2.0;                    // np.zeros(3) + tsdf_res/2 (:183)
+    for (int i = 0; i < 12; ++i) p.lw.m[i] = vw.lw[12 * view + i];
+    p.scale = vw.scale; p.cx = vw.center[0]; p.cy = vw.center[1]; p.cz = vw.center[2];
+    p.half = (double)vw.tsdf_res / 2.0;                 // np.zeros(3) + tsdf_res/2 (:183)
     p.tdist = tdist; p.wmax = wmax;
-    p.X = res[0]; p.Y = res[1]; p.Z = res[2];
-    p.x0 = x0; p.nx = x1 - x0; p.H = H; p.W = W;
-    p.zpacks = vec4 ? res[2] / 4 : res[2];
+    p.X = sl.res[0]; p.Y = sl.res[1]; p.Z = sl.res[2];
+    p.x0 = sl.x0; p.nx = sl.x1 - sl.x0; p.H = vw.H; p.W = vw.W;
+    p.zpacks = vec4 ? sl.res[2] / 4 : sl.res[2];
     p.zp_shift = -1;
     for (int b = 0; b < 31; ++b) if (p.zpacks == (1 << b)) p.zp_shift = b;
     p.pyr = nullptr; p.cull = 0;
@@ -1121,11 +1120,12 @@ struct K1Plan {
     bool gather_first;
 };
 
-static K1Plan single_view_plan(int vol_dtype, const int res[3], int x0, int x1, bool fast_ok, bool vec4, bool have_ws) {
+static K1Plan single_view_plan(int vol_dtype, const dfh_slab &sl, bool fast_ok, bool vec4, bool have_ws) {
     if (vol_dtype != DFH_F32 || !fast_ok) return {DFH_K1_PATH_EXACT, false, false, false};
-    const long slab_voxels = (long)(x1 - x0) * res[1] * res[2];
+    const int *res = sl.res, nx = sl.x1 - sl.x0;
+    const long slab_voxels = (long)nx * res[1] * res[2];
     const long bricks_min = opt().k1_bricks_min >= 0 ? opt().k1_bricks_min : kEarlyRowsMaxVoxels / 256 + 1;
-    const long slab_bricks = (long)((res[1] + 3) / 4) * ((res[2] + 15) / 16) * ((x1 - x0 + kBrX - 1) / kBrX);
+    const long slab_bricks = (long)((res[1] + 3) / 4) * ((res[2] + 15) / 16) * ((nx + kBrX - 1) / kBrX);
     if (vec4 && !on(opt().k1_no_bricks) && slab_bricks >= bricks_min) {
         const bool want_cull = !on(opt().k1_bricks_nocull) && (opt().k1_cull >= 0 ? opt().k1_cull != 0 : (size_t)slab_voxels * 8 > ((size_t)256 << 20));
         if (!want_cull || have_ws) {
@@ -1136,51 +1136,59 @@ static K1Plan single_view_plan(int vol_dtype, const int res[3], int x0, int x1, 
     return {DFH_K1_PATH_ROWS, false, false, false};
 }
 
+// What dfh_integrate_depth checks of its views (the maps' pointers only when there are any).
+static int check_views(const char *what, const dfh_depth_views *v) {
+    DFH_REQUIRE(v, "%s: null views", what);
+    DFH_REQUIRE(v->n_views >= 0 && v->n_views <= kMaxViews, "%s: %d views (at most %d per call)", what, v->n_views, kMaxViews);
+    if (v->n_views == 0) return DFH_OK;
+    DFH_REQUIRE(v->depth && v->lw, "%s: null pointer", what);
+    for (int i = 0; i < v->n_views; ++i) DFH_REQUIRE(v->depth[i], "%s: depth map %d is null", what, i);
+    DFH_REQUIRE(v->depth_dtype == DFH_F32 || v->depth_dtype == DFH_F64, "%s: bad depth_dtype %d", what, v->depth_dtype);
+    DFH_REQUIRE(v->H >= 2 && v->W >= 2 && (long)v->H * v->W < (1L << 31), "%s: bad depth map size %dx%d", what, v->H, v->W);
+    return DFH_OK;
+}
+
+// 16-byte packs of four voxels along z: whole rows of them, both buffers aligned
+static bool vec4_ok(const dfh_volume &vol) {
+    const size_t esz = vol.dtype == DFH_F32 ? 4 : 8;
+    return (vol.slab.res[2] % 4 == 0) && ((uintptr_t)vol.tsdf % (4 * esz) == 0) && ((uintptr_t)vol.tsdf_w % (4 * esz) == 0) &&
+           !on(opt().k1_force_scalar);
+}
+
 }  // namespace dfh
 
-extern "C" size_t dfh_integrate_workspace_bytes(int n_views, int H, int W, const int res[3], int x0, int x1) {
-    if (n_views <= 0 || H < 2 || W < 2 || !res || res[1] <= 0 || res[2] <= 0 || x1 < x0) return 0;
+extern "C" size_t dfh_integrate_workspace_bytes(int n_views, int H, int W, const dfh_slab *slab) {
+    if (n_views <= 0 || H < 2 || W < 2 || dfh::check_slab("dfh_integrate_workspace_bytes", slab) != DFH_OK || slab->x1 == slab->x0) return 0;
     dim3 grid;
     int n_bricks = 0;
-    dfh::brick_geom(dfh::kBrY, res[1], res[2], x1 - x0, grid, n_bricks);
+    dfh::brick_geom(dfh::kBrY, slab->res[1], slab->res[2], slab->x1 - slab->x0, grid, n_bricks);
     return dfh::params_bytes(n_views) + dfh::pyr_bytes(n_views, H, W) + ((size_t)n_bricks * sizeof(unsigned short) + 15) / 16 * 16;
 }
 
-extern "C" int dfh_integrate_depth_path(int vol_dtype, const int res[3], int x0, int x1, int H, int W, int have_workspace) {
+extern "C" int dfh_integrate_depth_path(int vol_dtype, const dfh_slab *slab, int H, int W, int have_workspace) {
     using namespace dfh;
-    DFH_REQUIRE(res && res[0] > 0 && res[1] > 0 && res[2] > 0 && 0 <= x0 && x0 <= x1 && x1 <= res[0], "dfh_integrate_depth_path: bad grid or slab");
+    const int rc = check_slab("dfh_integrate_depth_path", slab);
+    if (rc != DFH_OK || slab->x1 == slab->x0) return rc;
     const bool fast_ok = H <= kFastMaxDim && W <= kFastMaxDim;
-    const bool vec4 = res[2] % 4 == 0 && !on(opt().k1_force_scalar);
-    return single_view_plan(vol_dtype, res, x0, x1, fast_ok, vec4, have_workspace != 0).path;
+    const bool vec4 = slab->res[2] % 4 == 0 && !on(opt().k1_force_scalar);
+    return single_view_plan(vol_dtype, *slab, fast_ok, vec4, have_workspace != 0).path;
 }
 
-extern "C" int dfh_integrate_depth(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3],
-                                   int tsdf_res, int x0, int x1, const void *depth, int depth_dtype,
-                                   int H, int W, const double K[9], const double Kinv[9],
-                                   const double lw[12], double scale, const double center[3],
-                                   double tdist, double wmax, void *workspace, size_t workspace_bytes, void *stream) {
+// One view (checked by dfh_integrate_depth): the sweep single_view_plan names.
+static int integrate_one(const dfh_volume &vol, const dfh_depth_views &vw, int view, double tdist, double wmax, void *workspace,
+                         size_t workspace_bytes, hipStream_t s) {
     using namespace dfh;
-    DFH_REQUIRE(tsdf && tsdf_w && depth && res && K && Kinv && lw && center, "dfh_integrate_depth: null pointer");
-    DFH_REQUIRE(vol_dtype == DFH_F32 || vol_dtype == DFH_F64, "dfh_integrate_depth: bad vol_dtype %d", vol_dtype);
-    DFH_REQUIRE(depth_dtype == DFH_F32 || depth_dtype == DFH_F64, "dfh_integrate_depth: bad depth_dtype %d", depth_dtype);
-    DFH_REQUIRE(res[0] > 0 && res[1] > 0 && res[2] > 0, "dfh_integrate_depth: bad grid %dx%dx%d", res[0], res[1], res[2]);
-    DFH_REQUIRE(0 <= x0 && x0 <= x1 && x1 <= res[0], "dfh_integrate_depth: slab [%d,%d) outside [0,%d)", x0, x1, res[0]);
-    DFH_REQUIRE(H >= 2 && W >= 2, "dfh_integrate_depth: depth map %dx%d too small", H, W);
-    DFH_REQUIRE((long)H * W < (1L << 31), "dfh_integrate_depth: depth map too large");
-    DFH_REQUIRE(x1 - x0 <= 65535, "dfh_integrate_depth: slab has more than 65535 planes");
-    if (x1 == x0) return DFH_OK;
-
+    void *tsdf = vol.tsdf, *tsdf_w = vol.tsdf_w;
+    const void *depth = vw.depth[view];
+    const int vol_dtype = vol.dtype, depth_dtype = vw.depth_dtype, H = vw.H, W = vw.W;
     IntegrateParams p;
-    const size_t esz = vol_dtype == DFH_F32 ? 4 : 8;
-    const bool vec4 = (res[2] % 4 == 0) && ((uintptr_t)tsdf % (4 * esz) == 0) && ((uintptr_t)tsdf_w % (4 * esz) == 0) &&
-                      !on(opt().k1_force_scalar);
-    const bool pinhole = fill_params(p, res, tsdf_res, x0, x1, H, W, K, Kinv, lw, scale, center, tdist, wmax, vec4);
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool vec4 = vec4_ok(vol);
+    const bool pinhole = fill_params(p, vol.slab, vw, view, tdist, wmax, vec4);
     // fixed-point pixel coordinates need (dim-1) << 20 to fit in int32
-    const bool fast_ok = H <= kFastMaxDim && W <= kFastMaxDim && scale > 0.0 && tdist > 0.0;
+    const bool fast_ok = H <= kFastMaxDim && W <= kFastMaxDim && vw.scale > 0.0 && tdist > 0.0;
 
-    const bool have_ws = workspace && workspace_bytes >= dfh_integrate_workspace_bytes(1, H, W, res, x0, x1);
-    const K1Plan plan = single_view_plan(vol_dtype, res, x0, x1, fast_ok, vec4, have_ws);
+    const bool have_ws = workspace && workspace_bytes >= dfh_integrate_workspace_bytes(1, H, W, &vol.slab);
+    const K1Plan plan = single_view_plan(vol_dtype, vol.slab, fast_ok, vec4, have_ws);
     if (plan.bricks) {
         const bool cull = plan.cull, gf = plan.gather_first;
         dim3 grid;
@@ -1236,71 +1244,41 @@ extern "C" size_t dfh_integrate_multi_workspace_bytes(int n_views) {
 }
 
 // fresh: the volumes start as (fresh_value, 0): filled here, or -- brick sweep -- by the sweep itself
-static int integrate_multi_fill(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int x0, int x1, double fresh_value, void *stream) {
+static int integrate_fill(const dfh_volume &vol, double fresh_value, hipStream_t s) {
     using namespace dfh;
-    DFH_REQUIRE(tsdf && tsdf_w && res, "dfh_integrate_depth_multi_fresh: null pointer");
-    DFH_REQUIRE(vol_dtype == DFH_F32 || vol_dtype == DFH_F64, "dfh_integrate_depth_multi_fresh: bad vol_dtype %d", vol_dtype);
-    DFH_REQUIRE(res[0] > 0 && res[1] > 0 && res[2] > 0 && 0 <= x0 && x0 <= x1 && x1 <= res[0], "dfh_integrate_depth_multi_fresh: bad grid or slab");
-    const size_t n = (size_t)(x1 - x0) * res[1] * res[2];
-    if (n == 0) return DFH_OK;
+    const size_t n = (size_t)(vol.slab.x1 - vol.slab.x0) * vol.slab.res[1] * vol.slab.res[2];
     const unsigned nb = (unsigned)((n + 255) / 256 < 65536 * 16 ? (n + 255) / 256 : 65536 * 16);
-    if (vol_dtype == DFH_F32)
-        hipLaunchKernelGGL(fill_pair_kernel<float>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (float *)tsdf, (float)fresh_value, (float *)tsdf_w, 0.0f, n);
+    if (vol.dtype == DFH_F32)
+        hipLaunchKernelGGL(fill_pair_kernel<float>, dim3(nb), dim3(256), 0, s, (float *)vol.tsdf, (float)fresh_value, (float *)vol.tsdf_w, 0.0f, n);
     else
-        hipLaunchKernelGGL(fill_pair_kernel<double>, dim3(nb), dim3(256), 0, (hipStream_t)stream, (double *)tsdf, fresh_value, (double *)tsdf_w, 0.0, n);
+        hipLaunchKernelGGL(fill_pair_kernel<double>, dim3(nb), dim3(256), 0, s, (double *)vol.tsdf, fresh_value, (double *)vol.tsdf_w, 0.0, n);
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;
 }
 
-static int integrate_multi_impl(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int tsdf_res, int x0, int x1,
-                                int n_views, const void *const *depth, int depth_dtype, int H, int W,
-                                const double K[9], const double Kinv[9], const double *lw, double scale,
-                                const double center[3], double tdist, double wmax, void *workspace,
-                                size_t workspace_bytes, void *stream, bool fresh, double fresh_value) {
+// Several views in one sweep of a float32 volume (checked by dfh_integrate_depth; the workspace holds at least the views' parameters).
+static int integrate_several(const dfh_volume &vol, const dfh_depth_views &vw, double tdist, double wmax, const double *fresh_value,
+                             void *workspace, size_t workspace_bytes, hipStream_t s) {
     using namespace dfh;
-    DFH_REQUIRE(n_views >= 0 && n_views <= kMaxViews, "dfh_integrate_depth_multi: %d views (at most %d per call)", n_views, kMaxViews);
-    if (n_views == 0) return fresh ? integrate_multi_fill(tsdf, tsdf_w, vol_dtype, res, x0, x1, fresh_value, stream) : DFH_OK;
-    DFH_REQUIRE(tsdf && tsdf_w && depth && res && K && Kinv && lw && center, "dfh_integrate_depth_multi: null pointer");
-    for (int v = 0; v < n_views; ++v) DFH_REQUIRE(depth[v], "dfh_integrate_depth_multi: depth map %d is null", v);
-    DFH_REQUIRE(vol_dtype == DFH_F32 || vol_dtype == DFH_F64, "dfh_integrate_depth_multi: bad vol_dtype %d", vol_dtype);
-    DFH_REQUIRE(depth_dtype == DFH_F32 || depth_dtype == DFH_F64, "dfh_integrate_depth_multi: bad depth_dtype %d", depth_dtype);
-    const size_t esz = vol_dtype == DFH_F32 ? 4 : 8;
-    const bool vec4 = res[0] > 0 && res[1] > 0 && res[2] > 0 && (res[2] % 4 == 0) && ((uintptr_t)tsdf % (4 * esz) == 0) &&
-                      ((uintptr_t)tsdf_w % (4 * esz) == 0) && !on(opt().k1_force_scalar);
-    const bool fast_ok = vol_dtype == DFH_F32 && H <= kFastMaxDim && W <= kFastMaxDim && scale > 0.0 && tdist > 0.0 &&
-                         workspace && workspace_bytes >= dfh_integrate_multi_workspace_bytes(n_views) && !on(opt().k1_no_multi);
-    if (!fast_ok || n_views == 1 || x1 <= x0) {
-        // one sweep per view: the same results (every argument is checked there)
-        if (fresh) {
-            const int rc = integrate_multi_fill(tsdf, tsdf_w, vol_dtype, res, x0, x1, fresh_value, stream);
-            if (rc != DFH_OK) return rc;
-        }
-        for (int v = 0; v < n_views; ++v) {
-            const int rc = dfh_integrate_depth(tsdf, tsdf_w, vol_dtype, res, tsdf_res, x0, x1, depth[v], depth_dtype, H, W, K, Kinv,
-                                               lw + 12 * v, scale, center, tdist, wmax, workspace, workspace_bytes, stream);
-            if (rc != DFH_OK) return rc;
-        }
-        return DFH_OK;
-    }
-    DFH_REQUIRE(res[0] > 0 && res[1] > 0 && res[2] > 0, "dfh_integrate_depth_multi: bad grid %dx%dx%d", res[0], res[1], res[2]);
-    DFH_REQUIRE(0 <= x0 && x0 <= x1 && x1 <= res[0], "dfh_integrate_depth_multi: slab [%d,%d) outside [0,%d)", x0, x1, res[0]);
-    DFH_REQUIRE(H >= 2 && W >= 2 && (long)H * W < (1L << 31), "dfh_integrate_depth_multi: bad depth map size %dx%d", H, W);
-    DFH_REQUIRE(x1 - x0 <= 65535, "dfh_integrate_depth_multi: slab has more than 65535 planes");
+    void *tsdf = vol.tsdf, *tsdf_w = vol.tsdf_w;
+    const void *const *depth = vw.depth;
+    const int n_views = vw.n_views, depth_dtype = vw.depth_dtype, H = vw.H, W = vw.W;
+    const bool fresh = fresh_value != nullptr;
+    const bool vec4 = vec4_ok(vol);
     IntegrateParams hp[kMaxViews];
     ViewPtrs vp;
     bool pinhole = true;
-    const bool have_pyr = workspace_bytes >= dfh_integrate_workspace_bytes(n_views, H, W, res, x0, x1);
+    const bool have_pyr = workspace_bytes >= dfh_integrate_workspace_bytes(n_views, H, W, &vol.slab);
     const bool nocull = on(opt().k1_bricks_nocull);
     const bool bricks = vec4 && !on(opt().k1_no_bricks) && (have_pyr || nocull);
     const bool cull = bricks && have_pyr && !nocull;
     for (int v = 0; v < n_views; ++v) {
-        pinhole = fill_params(hp[v], res, tsdf_res, x0, x1, H, W, K, Kinv, lw + 12 * v, scale, center, tdist, wmax, vec4) && pinhole;
+        pinhole = fill_params(hp[v], vol.slab, vw, v, tdist, wmax, vec4) && pinhole;
         vp.depth[v] = depth[v];
         hp[v].cull = cull ? 1 : 0;
         if (cull) attach_pyramid(hp[v], workspace, n_views, v, H, W);
     }
     vp.n = n_views;
-    hipStream_t s = static_cast<hipStream_t>(stream);
     // the views' parameters travel as kernel arguments of a tiny launch that writes them into the workspace: a hipMemcpyAsync
     // from this (pageable) stack array is staged by the runtime and left the device idle for ~40 us per call
     for (int v0 = 0; v0 < n_views; v0 += kParamChunk) {
@@ -1326,7 +1304,7 @@ static int integrate_multi_impl(void *tsdf, void *tsdf_w, int vol_dtype, const i
 #undef DFH_CLASSIFY
         }
         const bool nt = use_nt((size_t)p.nx * p.Y * p.Z);
-#define DFH_MCOL(DT, PH, BY, FR, NT) hipLaunchKernelGGL((integrate_depth_multi_column_kernel<DT, PH, BY, FR, NT>), bgrid, dim3(256), 0, s, (float *)tsdf, (float *)tsdf_w, dv, vp, g, mask, (float)fresh_value)
+#define DFH_MCOL(DT, PH, BY, FR, NT) hipLaunchKernelGGL((integrate_depth_multi_column_kernel<DT, PH, BY, FR, NT>), bgrid, dim3(256), 0, s, (float *)tsdf, (float *)tsdf_w, dv, vp, g, mask, fresh ? (float)*fresh_value : 0.0f)
 #define DFH_MCOL_FR(DT, PH, BY, NT) do { if (fresh) DFH_MCOL(DT, PH, BY, true, NT); else DFH_MCOL(DT, PH, BY, false, NT); } while (0)
 #define DFH_MCOL_SHAPE(DT, PH) do { if (nt) DFH_MCOL_FR(DT, PH, kBrY, true); else DFH_MCOL_FR(DT, PH, kBrY, false); } while (0)
         if (depth_dtype == DFH_F32) { if (pinhole) DFH_MCOL_SHAPE(float, true); else DFH_MCOL_SHAPE(float, false); }
@@ -1338,7 +1316,7 @@ static int integrate_multi_impl(void *tsdf, void *tsdf_w, int vol_dtype, const i
         return DFH_OK;
     }
     if (fresh) {                                                    // (the plain multi-view sweep loads what it updates)
-        const int rc = integrate_multi_fill(tsdf, tsdf_w, vol_dtype, res, x0, x1, fresh_value, stream);
+        const int rc = integrate_fill(vol, *fresh_value, s);
         if (rc != DFH_OK) return rc;
     }
     dim3 grid((unsigned)(((long)p.Y * p.zpacks + 255) / 256), (unsigned)((p.nx + p.planes_per_block - 1) / p.planes_per_block)), block(256);
@@ -1355,40 +1333,43 @@ static int integrate_multi_impl(void *tsdf, void *tsdf_w, int vol_dtype, const i
     return DFH_OK;
 }
 
-extern "C" int dfh_integrate_depth_multi(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int tsdf_res, int x0, int x1,
-                                         int n_views, const void *const *depth, int depth_dtype, int H, int W,
-                                         const double K[9], const double Kinv[9], const double *lw, double scale,
-                                         const double center[3], double tdist, double wmax, void *workspace,
-                                         size_t workspace_bytes, void *stream) {
-    return integrate_multi_impl(tsdf, tsdf_w, vol_dtype, res, tsdf_res, x0, x1, n_views, depth, depth_dtype, H, W, K, Kinv, lw, scale, center,
-                                tdist, wmax, workspace, workspace_bytes, stream, false, 0.0);
+extern "C" int dfh_integrate_depth(const dfh_volume *vol, const dfh_depth_views *views, double tdist, double wmax,
+                                   const double *fresh_value, void *workspace, size_t workspace_bytes, void *stream) {
+    using namespace dfh;
+    int rc = check_volume("dfh_integrate_depth", vol);
+    if (rc == DFH_OK) rc = check_views("dfh_integrate_depth", views);
+    if (rc != DFH_OK || vol->slab.x1 == vol->slab.x0) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const int n_views = views->n_views;
+    // one sweep for all the views: float32 volumes, maps the fixed-point pixel coordinates can address, a workspace for the views' parameters
+    const bool several = n_views > 1 && vol->dtype == DFH_F32 && views->H <= kFastMaxDim && views->W <= kFastMaxDim && views->scale > 0.0 &&
+                         tdist > 0.0 && workspace && workspace_bytes >= dfh_integrate_multi_workspace_bytes(n_views) && !on(opt().k1_no_multi);
+    if (several) return integrate_several(*vol, *views, tdist, wmax, fresh_value, workspace, workspace_bytes, s);
+    // otherwise one sweep per view: the same results
+    if (fresh_value) rc = integrate_fill(*vol, *fresh_value, s);
+    for (int v = 0; v < n_views && rc == DFH_OK; ++v) rc = integrate_one(*vol, *views, v, tdist, wmax, workspace, workspace_bytes, s);
+    return rc;
 }
 
-extern "C" int dfh_integrate_depth_multi_fresh(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int tsdf_res, int x0, int x1,
-                                               double fresh_value, int n_views, const void *const *depth, int depth_dtype, int H, int W,
-                                               const double K[9], const double Kinv[9], const double *lw, double scale,
-                                               const double center[3], double tdist, double wmax, void *workspace,
-                                               size_t workspace_bytes, void *stream) {
-    return integrate_multi_impl(tsdf, tsdf_w, vol_dtype, res, tsdf_res, x0, x1, n_views, depth, depth_dtype, H, W, K, Kinv, lw, scale, center,
-                                tdist, wmax, workspace, workspace_bytes, stream, true, fresh_value);
-}
-
-extern "C" int dfh_integrate_depth_ocl(float *tsdf, float *tsdf_w, const int res[3], int x0, int x1, const float *depth, int H, int W,
+extern "C" int dfh_integrate_depth_ocl(const dfh_volume *vol, const float *depth, int H, int W,
                                        const float proj[12], const float kinv_row2[3], float tdist, float wmax, void *stream) {
     using namespace dfh;
-    DFH_REQUIRE(tsdf && tsdf_w && res && depth && proj && kinv_row2, "dfh_integrate_depth_ocl: null pointer");
-    DFH_REQUIRE(res[0] > 0 && res[1] > 0 && res[2] > 0, "dfh_integrate_depth_ocl: bad grid %dx%dx%d", res[0], res[1], res[2]);
-    DFH_REQUIRE(0 <= x0 && x0 <= x1 && x1 <= res[0], "dfh_integrate_depth_ocl: slab [%d,%d) outside [0,%d)", x0, x1, res[0]);
+    const int rc = check_volume("dfh_integrate_depth_ocl", vol);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(vol->dtype == DFH_F32, "dfh_integrate_depth_ocl: the OpenCL arithmetic is float32, volume dtype %d", vol->dtype);
+    DFH_REQUIRE(depth && proj && kinv_row2, "dfh_integrate_depth_ocl: null pointer");
     DFH_REQUIRE(H >= 2 && W >= 2 && (long)H * W < (1L << 31), "dfh_integrate_depth_ocl: bad depth map size %dx%d", H, W);
-    if (x1 == x0) return DFH_OK;
+    const dfh_slab &sl = vol->slab;
+    if (sl.x1 == sl.x0) return DFH_OK;
     OclParams p;
     for (int i = 0; i < 12; ++i) p.proj[i] = proj[i];
     for (int i = 0; i < 3; ++i) p.kinv2[i] = kinv_row2[i];
     p.tdist = tdist; p.wmax = wmax;
-    p.X = res[0]; p.Y = res[1]; p.Z = res[2]; p.x0 = x0; p.nx = x1 - x0; p.H = H; p.W = W;
+    p.X = sl.res[0]; p.Y = sl.res[1]; p.Z = sl.res[2]; p.x0 = sl.x0; p.nx = sl.x1 - sl.x0; p.H = H; p.W = W;
     const long n = (long)p.nx * p.Y * p.Z;
     DFH_REQUIRE((n + 255) / 256 < (1L << 31), "dfh_integrate_depth_ocl: slab too large");
-    hipLaunchKernelGGL(integrate_depth_ocl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, tsdf, tsdf_w, depth, p);
+    hipLaunchKernelGGL(integrate_depth_ocl_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (float *)vol->tsdf,
+                       (float *)vol->tsdf_w, depth, p);
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;
 }

@@ -481,7 +481,7 @@ class Fusion:
         reference's method of this name sets out to do (core/fusion.py:73-99; at HEAD it reads an undefined `tsdf.shape`, calls a
         free `fuseDepths` and iterates `len(depths)`).  From depth maps: the volume starts at +tdist with weight 0
         (core/fusion.py:80, core/fusion_dm.py:100-101) and the views are fused in order in ONE sweep of the volume
-        (dfh_integrate_depth_multi: the same bits as one fuseDepths call per view, FusionDM.compute_live_tsdf's loop,
+        (dfh_integrate_depth with all the views: the same bits as one fuseDepths call per view, FusionDM.compute_live_tsdf's loop,
         core/fusion_dm.py:166-170).  scale / center: FusionDM.fuseDepths' voxel -> world map (defaults as there)."""
         if tsdf is not None:
             if not _is_tensor(tsdf) and (type(tsdf) is not np.ndarray or tsdf.ndim != 3):

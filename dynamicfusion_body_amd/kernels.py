@@ -25,6 +25,35 @@ def _check_volume_pair(T, Wt, res, x_range):
                          % (tuple(T.shape), tuple(Wt.shape), want, tuple(res)))
 
 
+def _volume(T, Wt, res, x_range, tsdf_res=None):
+    """The defaults every K1-K3 entry point applies (the whole grid, all its planes, tsdf_res = res[0]), the volume pair's checks
+    and the dfh_volume of the call: (dfh_volume, tsdf_res)."""
+    if res is None:
+        res = tuple(T.shape)
+    _check_volume_pair(T, Wt, res, (0, res[0]) if x_range is None else x_range)
+    vol = _lib.Volume(T.data_ptr(), Wt.data_ptr(), dtype_code(T), _lib.slab(res, x_range))
+    return vol, int(res[0] if tsdf_res is None else tsdf_res)
+
+
+def _check_depth(d):
+    if not (isinstance(d, torch.Tensor) and d.is_cuda and d.dim() == 2 and d.is_contiguous()):
+        raise ValueError("depth must be a contiguous 2-D CUDA tensor")
+
+
+def _integrate(vol, tsdf_res, depths, K, Kinv, lws, scale, center, tdist, wmax, fresh, workspace):
+    """One dfh_integrate_depth call: the maps `depths` (at most 16, one shape and dtype) into `vol`."""
+    n = len(depths)
+    H, W = depths[0].shape
+    ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in depths])
+    lw = _lib.darr(np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in lws]), 12 * n)
+    views = _lib.DepthViews(n, ptrs, dtype_code(depths[0]), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), lw, float(scale),
+                            _lib.darr(np.asarray(center, dtype=np.float64), 3), tsdf_res)
+    ws_ptr, ws_bytes = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if isinstance(workspace, torch.Tensor) else (0, 0)
+    rc = _lib.load().dfh_integrate_depth(vol, views, float(tdist), float(wmax), None if fresh is None else ctypes.c_double(float(fresh)),
+                                         ws_ptr, ws_bytes, current_stream_ptr())
+    _lib.check(rc, "dfh_integrate_depth")
+
+
 _ws_cache = {}
 
 
@@ -40,7 +69,7 @@ def integrate_workspace(n_views, H, W, res, x_range=None, device=None):
     key = (dev.index, current_stream_ptr(), int(n_views), int(H), int(W), int(res[1]), int(res[2]), nx)
     ws = _ws_cache.get(key)
     if ws is None:
-        nbytes = lib.dfh_integrate_workspace_bytes(int(n_views), int(H), int(W), _lib.iarr(res), 0, nx)
+        nbytes = lib.dfh_integrate_workspace_bytes(int(n_views), int(H), int(W), _lib.slab(res, (0, nx)))
         ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
         if len(_ws_cache) > 64:
             _ws_cache.clear()
@@ -60,10 +89,8 @@ def integrate_path(T, depth, res=None, x_range=None, workspace=True):
     lib = _lib.load()
     if res is None:
         res = tuple(T.shape)
-    if x_range is None:
-        x_range = (0, res[0])
     H, W = depth.shape
-    code = lib.dfh_integrate_depth_path(dtype_code(T), _lib.iarr(res), int(x_range[0]), int(x_range[1]), int(H), int(W), 1 if workspace else 0)
+    code = lib.dfh_integrate_depth_path(dtype_code(T), _lib.slab(res, x_range), int(H), int(W), 1 if workspace else 0)
     if code < 0:
         _lib.check(code, "dfh_integrate_depth_path")
     return K1_PATHS[code]
@@ -99,28 +126,13 @@ def integrate_depth(T, Wt, depth, K, Kinv, lw, scale, center, tdist, wmax=100.0,
             negative depths.  Runs asynchronously on the current stream.  workspace: scratch from
             integrate_workspace(1, H, W) (default: a cached one); False = sweep without brick culling."""
     require_gpu()
-    lib = _lib.load()
-    if res is None:
-        res = tuple(T.shape)
-    if x_range is None:
-        x_range = (0, res[0])
-    if tsdf_res is None:
-        tsdf_res = res[0]
-    _check_volume_pair(T, Wt, res, x_range)
-    if x_range[1] == x_range[0]:
+    vol, tsdf_res = _volume(T, Wt, res, x_range, tsdf_res)
+    if vol.slab.x1 == vol.slab.x0:
         return T, Wt
-    if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dim() == 2 and depth.is_contiguous()):
-        raise ValueError("depth must be a contiguous 2-D CUDA tensor")
-    H, W = depth.shape
+    _check_depth(depth)
     if workspace is None and T.dtype == torch.float32:
-        workspace = integrate_workspace(1, H, W, res, x_range, T.device)
-    ws_ptr, ws_bytes = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if isinstance(workspace, torch.Tensor) else (0, 0)
-    rc = lib.dfh_integrate_depth(T.data_ptr(), Wt.data_ptr(), dtype_code(T), _lib.iarr(res), int(tsdf_res),
-                                 int(x_range[0]), int(x_range[1]), depth.data_ptr(), dtype_code(depth),
-                                 int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), _lib.darr(lw, 12),
-                                 float(scale), _lib.darr(np.asarray(center, dtype=np.float64), 3),
-                                 float(tdist), float(wmax), ws_ptr, ws_bytes, current_stream_ptr())
-    _lib.check(rc, "dfh_integrate_depth")
+        workspace = integrate_workspace(1, *depth.shape, vol.slab.res, (vol.slab.x0, vol.slab.x1), T.device)
+    _integrate(vol, tsdf_res, [depth], K, Kinv, [lw], scale, center, tdist, wmax, None, workspace)
     return T, Wt
 
 
@@ -129,47 +141,36 @@ def integrate_depth_ocl(T, Wt, depth, proj, kinv_row2, tdist, wmax=100.0, res=No
     device volumes, in place.  proj: float32 3x4 index -> pixel map (K lw IND, :695); kinv_row2: third row of K^-1 (float32)."""
     require_gpu()
     lib = _lib.load()
-    if res is None:
-        res = tuple(T.shape)
-    if x_range is None:
-        x_range = (0, res[0])
-    _check_volume_pair(T, Wt, res, x_range)
+    vol, _ = _volume(T, Wt, res, x_range)
     if T.dtype != torch.float32:
         raise ValueError("the OpenCL arithmetic is float32: volumes must be float32")
     if not (isinstance(depth, torch.Tensor) and depth.is_cuda and depth.dim() == 2 and depth.is_contiguous() and depth.dtype == torch.float32):
         raise ValueError("depth must be a contiguous 2-D float32 CUDA tensor")
-    if x_range[1] == x_range[0]:
+    if vol.slab.x1 == vol.slab.x0:
         return T, Wt
     pr = (ctypes.c_float * 12)(*np.asarray(proj, dtype=np.float32).reshape(12).tolist())
     kr = (ctypes.c_float * 3)(*np.asarray(kinv_row2, dtype=np.float32).reshape(3).tolist())
     H, W = depth.shape
-    _lib.check(lib.dfh_integrate_depth_ocl(T.data_ptr(), Wt.data_ptr(), _lib.iarr(res), int(x_range[0]), int(x_range[1]), depth.data_ptr(),
-                                           int(H), int(W), pr, kr, ctypes.c_float(float(tdist)), ctypes.c_float(float(wmax)),
-                                           current_stream_ptr()), "dfh_integrate_depth_ocl")
+    _lib.check(lib.dfh_integrate_depth_ocl(vol, depth.data_ptr(), int(H), int(W), pr, kr, ctypes.c_float(float(tdist)),
+                                           ctypes.c_float(float(wmax)), current_stream_ptr()), "dfh_integrate_depth_ocl")
     return T, Wt
 
 
 def integrate_depth_views(T, Wt, depths, K, Kinv, lws, scale, center, tdist, wmax=100.0, tsdf_res=None, res=None,
                           x_range=None, workspace=None, fresh=None):
-    """Several views in one sweep of the volume (dfh_integrate_depth_multi): same result, bit for bit, as
+    """Several views in one sweep of the volume (dfh_integrate_depth with n_views > 1): same result, bit for bit, as
     integrate_depth called once per view in this order (what the reference's loops over fuseDepths do,
     core/fusion_dm.py:152-154,166-170), with T and w read and written once.  depths: list of (H, W) CUDA tensors of one
     shape and dtype; lws: list of 3x4 extrinsics.  More than 16 views are taken 16 at a time.
     fresh=value: T and Wt are first set to (value, 0) -- a live volume from scratch, core/fusion_dm.py:152-153 -- as part of the
-    same sweep (dfh_integrate_depth_multi_fresh): what T.fill_(value); Wt.zero_() in front of this call give, bit for bit."""
+    same sweep (dfh_integrate_depth's fresh_value): what T.fill_(value); Wt.zero_() in front of this call give, bit for bit."""
     require_gpu()
     lib = _lib.load()
     depths, lws = list(depths), list(lws)
     if len(depths) != len(lws):
         raise ValueError('length of camera matrix array must equal that of depth maps')        # core/fusion_dm.py:96-97
-    if res is None:
-        res = tuple(T.shape)
-    if x_range is None:
-        x_range = (0, res[0])
-    if tsdf_res is None:
-        tsdf_res = res[0]
-    _check_volume_pair(T, Wt, res, x_range)
-    if x_range[1] == x_range[0]:
+    vol, tsdf_res = _volume(T, Wt, res, x_range, tsdf_res)
+    if vol.slab.x1 == vol.slab.x0:
         return T, Wt
     if not depths:
         if fresh is not None:
@@ -177,33 +178,24 @@ def integrate_depth_views(T, Wt, depths, K, Kinv, lws, scale, center, tdist, wma
             Wt.zero_()
         return T, Wt
     for d in depths:
-        if not (isinstance(d, torch.Tensor) and d.is_cuda and d.dim() == 2 and d.is_contiguous()):
-            raise ValueError("depth must be a contiguous 2-D CUDA tensor")
+        _check_depth(d)
         if d.shape != depths[0].shape or d.dtype != depths[0].dtype:
             raise ValueError("all depth maps of one call must have the same shape and dtype")
     H, W = depths[0].shape
+    slab = vol.slab
     for i in range(0, len(depths), 16):
         dd, ll = depths[i:i + 16], lws[i:i + 16]
-        n = len(dd)
-        nbytes = lib.dfh_integrate_workspace_bytes(n, int(H), int(W), _lib.iarr(res), int(x_range[0]), int(x_range[1]))
+        nbytes = lib.dfh_integrate_workspace_bytes(len(dd), int(H), int(W), slab)
         ws = workspace if (workspace is not None and workspace.numel() * workspace.element_size() >= nbytes) else \
-            integrate_workspace(n, H, W, res, x_range, T.device)
-        ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dd])
-        lw_flat = np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in ll])
-        tail = (n, ptrs, dtype_code(dd[0]), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), _lib.darr(lw_flat, 12 * n), float(scale),
-                _lib.darr(np.asarray(center, dtype=np.float64), 3), float(tdist), float(wmax), ws.data_ptr(),
-                ws.numel() * ws.element_size(), current_stream_ptr())
-        head = (T.data_ptr(), Wt.data_ptr(), dtype_code(T), _lib.iarr(res), int(tsdf_res), int(x_range[0]), int(x_range[1]))
-        if fresh is not None and i == 0:
-            _lib.check(lib.dfh_integrate_depth_multi_fresh(*head, float(fresh), *tail), "dfh_integrate_depth_multi_fresh")
-        else:
-            _lib.check(lib.dfh_integrate_depth_multi(*head, *tail), "dfh_integrate_depth_multi")
+            integrate_workspace(len(dd), H, W, slab.res, (slab.x0, slab.x1), T.device)
+        _integrate(vol, tsdf_res, dd, K, Kinv, ll, scale, center, tdist, wmax, fresh if i == 0 else None, ws)
     return T, Wt
 
 
 def _check_live(live):
     if not (isinstance(live, torch.Tensor) and live.is_cuda and live.dim() == 3 and live.is_contiguous()):
         raise ValueError("live TSDF must be a contiguous 3-D CUDA tensor")
+    return _lib.Live(live.data_ptr(), dtype_code(live), _lib.iarr(live.shape))
 
 
 def fuse_volume_rigid(T, Wt, live, lw_dq, tdist, wmax=100.0, res=None, x_range=None):
@@ -211,17 +203,11 @@ def fuse_volume_rigid(T, Wt, live, lw_dq, tdist, wmax=100.0, res=None, x_range=N
     T, Wt: planes [x0,x1) of the canonical grid `res`; live: the whole live volume."""
     require_gpu()
     lib = _lib.load()
-    if res is None:
-        res = tuple(T.shape)
-    if x_range is None:
-        x_range = (0, res[0])
-    _check_volume_pair(T, Wt, res, x_range)
-    _check_live(live)
-    if x_range[1] == x_range[0]:
+    vol, _ = _volume(T, Wt, res, x_range)
+    live = _check_live(live)
+    if vol.slab.x1 == vol.slab.x0:
         return T, Wt
-    rc = lib.dfh_fuse_volume_rigid(T.data_ptr(), Wt.data_ptr(), dtype_code(T), _lib.iarr(res), int(x_range[0]),
-                                   int(x_range[1]), live.data_ptr(), dtype_code(live), _lib.iarr(live.shape),
-                                   _lib.darr(lw_dq, 8), float(tdist), float(wmax), current_stream_ptr())
+    rc = lib.dfh_fuse_volume_rigid(vol, live, _lib.darr(lw_dq, 8), float(tdist), float(wmax), current_stream_ptr())
     _lib.check(rc, "dfh_fuse_volume_rigid")
     return T, Wt
 
@@ -232,12 +218,10 @@ def dqb_workspace(res, x_range=None, device=None, knn=None, n_nodes=None, level=
     calls with rebuild_candidates=False then skip the node search / the weight computation."""
     require_gpu()
     lib = _lib.load()
-    if x_range is None:
-        x_range = (0, res[0])
     if knn is not None and n_nodes is not None:
-        nbytes = lib.dfh_dqb_workspace_bytes_cached(_lib.iarr(res), int(x_range[0]), int(x_range[1]), int(knn), int(n_nodes), int(level))
+        nbytes = lib.dfh_dqb_workspace_bytes_cached(_lib.slab(res, x_range), int(knn), int(n_nodes), int(level))
     else:
-        nbytes = lib.dfh_dqb_workspace_bytes(_lib.iarr(res), int(x_range[0]), int(x_range[1]))
+        nbytes = lib.dfh_dqb_workspace_bytes(_lib.slab(res, x_range))
     return torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.int32, device=device or "cuda")
 
 
@@ -246,13 +230,11 @@ def dqb_skip_tables(workspace, res, live_res, n_nodes, x_range=None, knn=4):
     steady-state fuse_volume_dqb call through it: {"U": live-cell mask words, "S": uint8 per brick (1 = its voxels took the constant-live stream), "reach": uint8 per
     brick, "bound": float32 per brick (voxels; -1 = not computed: the live volume ruled the skip out; option k3_skip = 2 computes all), "used": int16 (bricks, 16) node ids, "n_listed": 16-voxel rows left to the warp kernel, "n_runs": all such rows, "ok": sizes admit the skip}.  For tests and
     measurement code."""
-    import ctypes
     lib = _lib.load()
     if x_range is None:
         x_range = (0, res[0])
     out = (ctypes.c_size_t * 13)()
-    _lib.check(lib.dfh_dqb_skip_layout(_lib.iarr(res), int(x_range[0]), int(x_range[1]), _lib.iarr(live_res), int(knn), int(n_nodes), out),
-               "dfh_dqb_skip_layout")
+    _lib.check(lib.dfh_dqb_skip_layout(_lib.slab(res, x_range), _lib.iarr(live_res), int(knn), int(n_nodes), out), "dfh_dqb_skip_layout")
     raw = workspace.view(torch.uint8)
     nx = int(x_range[1]) - int(x_range[0])
     nb = (-(-nx // 4)) * (-(-int(res[1]) // 4)) * (-(-int(res[2]) // 16))
@@ -273,12 +255,10 @@ def dqb_build_candidates(workspace, res, node_pos, knn, x_range=None):
     rebuild_candidates=True); needed up front only by solve.sample_knn(..., bricks=...)."""
     require_gpu()
     lib = _lib.load()
-    if x_range is None:
-        x_range = (0, res[0])
     P = node_pos if isinstance(node_pos, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(node_pos, dtype=np.float64)))
     P = P.to(device="cuda", dtype=torch.float64).contiguous()
-    _lib.check(lib.dfh_dqb_build_candidates(_lib.iarr(res), int(x_range[0]), int(x_range[1]), P.data_ptr(), int(P.shape[0]), int(knn),
-                                            workspace.data_ptr(), workspace.numel() * 4, current_stream_ptr()), "dfh_dqb_build_candidates")
+    _lib.check(lib.dfh_dqb_build_candidates(_lib.slab(res, x_range), P.data_ptr(), int(P.shape[0]), int(knn), workspace.data_ptr(),
+                                            workspace.numel() * 4, current_stream_ptr()), "dfh_dqb_build_candidates")
     return workspace
 
 
@@ -303,22 +283,16 @@ def fuse_volume_dqb(T, Wt, live, node_pos, node_dq, node_w, knn, lw_dq, tdist, w
     positions, knn and slab are unchanged."""
     require_gpu()
     lib = _lib.load()
-    if res is None:
-        res = tuple(T.shape)
-    if x_range is None:
-        x_range = (0, res[0])
-    _check_volume_pair(T, Wt, res, x_range)
-    _check_live(live)
+    vol, _ = _volume(T, Wt, res, x_range)
+    live = _check_live(live)
     P, Q, Wn = _node_tensors(node_pos, node_dq, node_w)
-    if x_range[1] == x_range[0]:
+    if vol.slab.x1 == vol.slab.x0:
         return T, Wt
     if workspace is None:
-        workspace = dqb_workspace(res, x_range)
+        workspace = dqb_workspace(vol.slab.res, (vol.slab.x0, vol.slab.x1))
         rebuild_candidates = True
-    rc = lib.dfh_fuse_volume_dqb(T.data_ptr(), Wt.data_ptr(), dtype_code(T), _lib.iarr(res), int(x_range[0]),
-                                 int(x_range[1]), live.data_ptr(), dtype_code(live), _lib.iarr(live.shape),
-                                 P.data_ptr(), Q.data_ptr(), Wn.data_ptr(), int(P.shape[0]), int(knn),
-                                 _lib.darr(lw_dq, 8), float(tdist), float(wmax), workspace.data_ptr(),
+    nodes = _lib.Nodes(P.data_ptr(), Q.data_ptr(), Wn.data_ptr(), int(P.shape[0]), int(knn))
+    rc = lib.dfh_fuse_volume_dqb(vol, live, nodes, _lib.darr(lw_dq, 8), float(tdist), float(wmax), workspace.data_ptr(),
                                  workspace.numel() * 4, 1 if rebuild_candidates else 0, current_stream_ptr())
     _lib.check(rc, "dfh_fuse_volume_dqb")
     return T, Wt

@@ -166,7 +166,7 @@ class SlabFrame:
         ident = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0, 0]), (N, 1))
         self.fs.set_graph(node_pos, ident, node_w)
         self.ws_dqb = kernels.dqb_workspace((R, R, R), (self.a, self.b), knn=knn, n_nodes=N)
-        self.ws_views = None                     # dfh_integrate_depth_multi's scratch (parameters + depth pyramids): sized on first use
+        self.ws_views = None                     # the multi-view dfh_integrate_depth's scratch (parameters + depth pyramids): sized on first use
         self._side = None                        # side stream of step(): the live-volume sweep beside the plan build
         self.updated = None                      # event recorded by step() right after the TSDF update
         self.knn_bricks = None

@@ -135,11 +135,11 @@ def sample_knn(sample_pos, node_pos, node_w, knn, bricks=None):
     S = Sp.shape[0]
     nbr = torch.empty((S, knn), dtype=torch.int32, device="cuda")
     wts = torch.empty((S, knn), dtype=torch.float64, device="cuda")
-    if bricks is not None:
-        res, (x0, x1), ws = bricks
-        _lib.check(lib.dfh_sample_knn_bricks(Sp.data_ptr(), S, P.data_ptr(), Wn.data_ptr(), P.shape[0], int(knn), _lib.iarr(res),
-                                             int(x0), int(x1), ws.data_ptr(), ws.numel() * ws.element_size(), nbr.data_ptr(),
-                                             wts.data_ptr(), current_stream_ptr()), "dfh_sample_knn_bricks")
+    if bricks is not None and bricks[1][0] != bricks[1][1]:            # (an empty slab has no lists: the plain search below)
+        res, x_range, ws = bricks
+        _lib.check(lib.dfh_sample_knn_bricks(Sp.data_ptr(), S, P.data_ptr(), Wn.data_ptr(), P.shape[0], int(knn), _lib.slab(res, x_range),
+                                             ws.data_ptr(), ws.numel() * ws.element_size(), nbr.data_ptr(), wts.data_ptr(),
+                                             current_stream_ptr()), "dfh_sample_knn_bricks")
         return nbr, wts
     _lib.check(lib.dfh_sample_knn(Sp.data_ptr(), S, P.data_ptr(), Wn.data_ptr(), P.shape[0], int(knn), nbr.data_ptr(),
                                   wts.data_ptr(), current_stream_ptr()), "dfh_sample_knn")

@@ -14,7 +14,7 @@
  *    the OpenCL kernel's idx = x*RES_Z*RES_Y + y*RES_Z + z, :637).  A volume buffer holds
  *    the axis-0 planes [x0, x1) of a res[0] x res[1] x res[2] grid (slab partition across
  *    GPUs); voxel indices used in the arithmetic are always GLOBAL.
- *  - `vol_dtype` / `depth_dtype`: DFH_F32 or DFH_F64.  fp32 volumes are the product
+ *  - a volume's `dtype` / `depth_dtype`: DFH_F32 or DFH_F64. fp32 volumes are the product
  *    layout (16 B/voxel read-modify-write); fp64 volumes reproduce the reference's float64
  *    arrays bit for bit and exist for parity checking.
  *  - Calls are asynchronous on `stream` (a hipStream_t; NULL = default stream).
@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define DFH_ABI_VERSION 7
+#define DFH_ABI_VERSION 8
 
 #define DFH_F32 0
 #define DFH_F64 1
@@ -60,31 +60,59 @@ int dfh_stream_synchronize(void *stream);
 int dfh_set_option(const char *name, long value);
 long dfh_get_option(const char *name);
 
+/* ---- what the TSDF entry points (K1-K3) share, as structs in HOST memory read during the call.
+ * dfh_slab: the axis-0 planes [x0, x1) of a res grid (> 0 each), 0 <= x0 <= x1 <= res[0], at most 65535 planes; voxel indices stay
+ *   GLOBAL.  x0 == x1: nothing to do (DFH_OK before any launch, size queries give 0).  Anything else: DFH_E_BADARG (size queries 0).
+ * dfh_volume: the T / w pair holding a slab's planes, both of `dtype`.  dfh_live: the WHOLE live volume. */
+typedef struct dfh_slab { int res[3]; int x0, x1; } dfh_slab;
+typedef struct dfh_volume { void *tsdf, *tsdf_w; int dtype; dfh_slab slab; } dfh_volume;
+typedef struct dfh_live { const void *data; int dtype; int res[3]; } dfh_live;
+typedef struct dfh_depth_views {     /* n_views depth maps of one size through one camera */
+    int n_views;                     /* 0..16 */
+    const void *const *depth;        /* HOST array of n_views device pointers: H x W row-major, negative depths, 0 = no measurement */
+    int depth_dtype, H, W;           /* H, W >= 2 */
+    double K[9], Kinv[9];            /* 3x3 row-major */
+    const double *lw;                /* HOST, n_views x 12: a 3x4 row-major extrinsic per view */
+    double scale, center[3];
+    int tsdf_res;                    /* the ctor's tsdf_res (core/fusion_dm.py:60,:183) */
+} dfh_depth_views;
+/* the graph's nodes, device fp64: pos n_nodes x 3, dq n_nodes x 8, w n_nodes (the nodes' 4th tuple entry, 2*radius, core/fusion.py:116) */
+typedef struct dfh_nodes { const double *pos, *dq, *w; int n_nodes, knn; /* 1 <= knn <= 8, knn <= n_nodes */ } dfh_nodes;
+
 /* A1  FusionDM.fuseDepths(dm, lw, tsdf, tsdf_w, scale, center, wmax)  core/fusion_dm.py:180-217
  * (CPU-path semantics; the OpenCL variant :600-737 is NOT what is reproduced).
- * For every voxel i=(x,y,z), x in [x0,x1):
+ * For every voxel i=(x,y,z), x in [x0,x1), and every view in turn:
  *   pos  = scale*(i - tsdf_res/2) + center                       (:183,:191)
  *   lpos = lw*[pos,1];  (u,v) = (K*lpos)_{0,1}/(K*lpos)_2, skipped if (K*lpos)_2 == 0   (:193-194)
  *   visible iff 0<=u<W-1 and 0<=v<H-1                            (:195)
  *   z = -depth[rint(v)][rint(u)] (round-half-even), valid iff z>0   (:196-197)
  *   sd = (Kinv*(z*[u,v,1]))_2 - lpos_2;  update iff sd > -tdist   (:198-203)
  *   T <- (scale*T*w + min(tdist,sd)) / (scale*(1+w));  w <- min(1+w, wmax)   (:209-210)
- * tsdf/tsdf_w: planes [x0,x1) of the volume, dtype vol_dtype.  depth: H x W row-major,
- * negative depths, 0 = no measurement, dtype depth_dtype.  K, Kinv: 3x3 row-major;
- * lw: 3x4 row-major; center: 3.  tsdf_res is the ctor's tsdf_res (:60,:183).
- * workspace (may be NULL): device scratch of dfh_integrate_workspace_bytes(1, H, W, res, x0, x1) bytes.  With it, float32
+ * One view (n_views == 1).  workspace (may be NULL): device scratch of dfh_integrate_workspace_bytes(1, H, W, slab) bytes.  With it, float32
  * volumes are swept in 4 x 4 x 16 voxel bricks after a classification pass (same call, same stream) that marks the bricks
  * whose eight projected corners prove that the view updates none of their voxels -- outside the image, or behind the
  * surface by more than tdist according to a max-depth pyramid of the depth map -- and the sweep skips those: same result,
- * bit for bit, about half the projection work for a typical view.  Without it every voxel is projected. */
-size_t dfh_integrate_workspace_bytes(int n_views, int H, int W, const int res[3], int x0, int x1);
-int dfh_integrate_depth(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int tsdf_res,
-                        int x0, int x1, const void *depth, int depth_dtype, int H, int W,
-                        const double K[9], const double Kinv[9], const double lw[12],
-                        double scale, const double center[3], double tdist, double wmax,
-                        void *workspace, size_t workspace_bytes, void *stream);
+ * bit for bit, about half the projection work for a typical view.  Without it every voxel is projected.
+ * Several views (n_views <= 16) go in ONE sweep of the volume: what the reference's loops over fuseDepths do
+ * (core/fusion_dm.py:152-154 initial fusion, :166-170 compute_live_tsdf), with every voxel's T and w read once, updated
+ * view by view in registers -- the float32 operations of consecutive one-view calls, so the same bits -- and written once.
+ * workspace: device scratch; dfh_integrate_workspace_bytes(n_views, H, W, slab) bytes enable the brick
+ * sweep with the per-(brick, view) classification described above (a brick runs only the views that may update it, a brick
+ * no view updates is never loaded), dfh_integrate_multi_workspace_bytes(n_views)
+ * bytes (the views' folded projection parameters only) the plain sweep; without a workspace, for float64 volumes and for
+ * depth maps beyond 2048 pixels a side the call runs one sweep per view.
+ * fresh_value != NULL, a live volume from scratch: the volumes are first set to (*fresh_value, 0) -- the reference's
+ * np.zeros(...) + tdist and np.zeros(...) in front of its fuseDepths loops, core/fusion_dm.py:100-101,152-153 -- and the views are
+ * then fused: the result is that of the two fills followed by the call without fresh_value, bit for bit (*fresh_value is rounded to
+ * the volume's type).  With the column sweep the fill is part of the sweep: nothing is read and every voxel of the slab is written
+ * once (a 256^3 live volume of three views: fills 38 + sweep 89 -> sweep 84 us); otherwise the slab is filled by a launch of its own first.
+ * n_views == 0 only fills; without fresh_value it does nothing. */
+size_t dfh_integrate_workspace_bytes(int n_views, int H, int W, const dfh_slab *slab);
+size_t dfh_integrate_multi_workspace_bytes(int n_views);
+int dfh_integrate_depth(const dfh_volume *vol, const dfh_depth_views *views, double tdist, double wmax,
+                        const double *fresh_value /* NULL: keep the volumes */, void *workspace, size_t workspace_bytes, void *stream);
 
-/* Which sweep dfh_integrate_depth takes for float32 volumes of this slab and depth-map size (no launch): one of
+/* Which sweep a one-view dfh_integrate_depth takes for float32 volumes of this slab and depth-map size (no launch): one of
  * DFH_K1_PATH_*, the CLASS of bytes the sweep moves (several kernels may share one).  All of them produce the same volumes bit for
  * bit; they differ in the bytes they move (measurement code counts those of the path taken).  have_workspace: a workspace of dfh_integrate_workspace_bytes(1, ...) bytes will be passed.
  * No reference counterpart. */
@@ -92,44 +120,16 @@ int dfh_integrate_depth(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3
 #define DFH_K1_PATH_ROWS 1           /* T, w loaded and stored for updated 16-byte packs only (the row sweep; the gather-first column walk) */
 #define DFH_K1_PATH_COLUMNS 2        /* T, w of every pack loaded, updated packs stored (the column walk over every 4 x 2 x 32 brick) */
 #define DFH_K1_PATH_COLUMNS_CULLED 3 /* T, w of every pack of the bricks a depth pyramid + brick classification keep loaded, updated packs stored */
-int dfh_integrate_depth_path(int vol_dtype, const int res[3], int x0, int x1, int H, int W, int have_workspace);
-
-/* The same for n_views depth maps in ONE sweep of the volume: what the reference's loops over fuseDepths do
- * (core/fusion_dm.py:152-154 initial fusion, :166-170 compute_live_tsdf), with every voxel's T and w read once, updated
- * view by view in registers -- the float32 operations of consecutive dfh_integrate_depth calls, so the same bits --
- * and written once.  depth: HOST array of n_views device pointers (all H x W, depth_dtype); lw: n_views x 12.
- * n_views <= 16.  workspace: device scratch; dfh_integrate_workspace_bytes(n_views, H, W, res, x0, x1) bytes enable the brick
- * sweep with the per-(brick, view) classification described above (a brick runs only the views that may update it, a brick
- * no view updates is never loaded), dfh_integrate_multi_workspace_bytes(n_views)
- * bytes (the views' folded projection parameters only) the plain sweep; without a workspace, for float64 volumes and for
- * depth maps beyond 2048 pixels a side the call runs one sweep per view. */
-size_t dfh_integrate_multi_workspace_bytes(int n_views);
-int dfh_integrate_depth_multi(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int tsdf_res, int x0, int x1,
-                              int n_views, const void *const *depth, int depth_dtype, int H, int W,
-                              const double K[9], const double Kinv[9], const double *lw, double scale,
-                              const double center[3], double tdist, double wmax, void *workspace,
-                              size_t workspace_bytes, void *stream);
-
-/* A live volume from scratch: the volumes are first set to (fresh_value, 0) -- the reference's np.zeros(...) + tdist and
- * np.zeros(...) in front of its fuseDepths loops, core/fusion_dm.py:100-101,152-153 -- and the n_views depth maps are then fused as
- * by dfh_integrate_depth_multi: the result is that of the two fills followed by that call, bit for bit (fresh_value is rounded to
- * the volume's type).  With the column sweep the fill is part of the sweep: nothing is read and every voxel of the slab is written
- * once (a 256^3 live volume of three views: fills 38 + sweep 89 -> sweep 84 us); otherwise the slab is filled by a launch of its own first.
- * n_views == 0 only fills. */
-int dfh_integrate_depth_multi_fresh(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int tsdf_res, int x0, int x1,
-                                    double fresh_value, int n_views, const void *const *depth, int depth_dtype, int H, int W,
-                                    const double K[9], const double Kinv[9], const double *lw, double scale,
-                                    const double center[3], double tdist, double wmax, void *workspace,
-                                    size_t workspace_bytes, void *stream);
+int dfh_integrate_depth_path(int vol_dtype, const dfh_slab *slab, int H, int W, int have_workspace);
 
 /* A2 (optional)  the arithmetic of the reference's OpenCL kernel `fuse_depth`  core/fusion_dm.py:630-674 -- NOT that of the CPU
  * path above: index -> pixel through one float32 3x4 map proj = K lw IND (:640-646,:695), bilinear depth (:605-622), pixels without
  * or with near depth (pz <= tdist) carve free space (dz = -tdist, :652-653), dz = voxel depth - measured depth (:655-658), update
  * iff dz < tdist: w' = min(1 + w, wmax), T <- ((w' - 1) T + max(-tdist, dz)) / w', w <- w' (:667-672).  All float32, in the kernel
- * text's operation order, no contraction.  tsdf / tsdf_w: float32 planes [x0,x1), updated in place (the reference's host code
+ * text's operation order, no contraction.  vol: float32 planes [x0,x1) (any other dtype: DFH_E_BADARG), updated in place (the reference's host code
  * copies its inputs first, :690-691); depth float32 H x W; tdist / wmax as the float literals the reference bakes in ("%ff" of
  * the Python values, :682-687).  A pixel coordinate that is NaN (w == 0) is skipped (undefined in the reference). */
-int dfh_integrate_depth_ocl(float *tsdf, float *tsdf_w, const int res[3], int x0, int x1, const float *depth, int H, int W,
+int dfh_integrate_depth_ocl(const dfh_volume *vol, const float *depth, int H, int W,
                             const float proj[12], const float kinv_row2[3], float tdist, float wmax, void *stream);
 
 /* A3  FusionDM.updateTSDF(curr_tsdf, wmax)                     core/fusion_dm.py:300-316
@@ -139,11 +139,8 @@ int dfh_integrate_depth_ocl(float *tsdf, float *tsdf_w, const int res[3], int x0
  *   s = interpolate_tsdf(q, live)            (core/util.py:102-137: None outside [0,R-1]^3, ceil() upper
  *                                             corner, y/z fractions swapped -- reproduced)
  *   update iff s is not None and s > -tdist: T <- (T*w + min(tdist,s))/(1+w); w <- min(1+w, wmax)
- * live: the full live volume live_res[0] x live_res[1] x live_res[2] (every rank holds all of it: the warp
- * gathers across slab boundaries), dtype live_dtype. */
-int dfh_fuse_volume_rigid(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int x0, int x1,
-                          const void *live, int live_dtype, const int live_res[3],
-                          const double lw_dq[8], double tdist, double wmax, void *stream);
+ * live: the full live volume (every rank holds all of it: the warp gathers across slab boundaries). */
+int dfh_fuse_volume_rigid(const dfh_volume *vol, const dfh_live *live, const double lw_dq[8], double tdist, double wmax, void *stream);
 
 /* A4-A6  Fusion.updateTSDF(curr_tsdf, wmax)                    core/fusion.py:153-198
  * For every canonical voxel i, x in [x0,x1):
@@ -153,8 +150,7 @@ int dfh_fuse_volume_rigid(void *tsdf, void *tsdf_w, int vol_dtype, const int res
  *   s   = interpolate_tsdf(q, live); update iff s is not None and s > -tdist              (:178-179)
  *   wi  = sum_j |v_j - i| / knn ; wt = w, or wi if w == 0                                 (:180-187)
  *   T <- (T*wt + min(tdist,s)*wi)/(wi + wt) ; w <- min(wi + wt, wmax)                      (:189-190)
- * node_pos: n_nodes x 3, node_dq: n_nodes x 8, node_w: n_nodes (the nodes' 4th tuple entry, 2*radius,
- * :116), all device fp64.  1 <= knn <= 8.  workspace: device scratch of dfh_dqb_workspace_bytes() bytes
+ * nodes: dfh_nodes above.  workspace: device scratch of dfh_dqb_workspace_bytes() bytes
  * holding per-brick candidate node lists; they depend only on (node_pos, knn, grid, slab) and are rebuilt
  * when rebuild_candidates != 0.  A workspace of dfh_dqb_workspace_bytes_cached() bytes (16-byte aligned; the
  * plain size when n_nodes > 65536) additionally keeps per voxel the knn node indices (level 1: 2*knn bytes) and
@@ -166,13 +162,10 @@ int dfh_fuse_volume_rigid(void *tsdf, void *tsdf_w, int vol_dtype, const int res
  * live voxels holding exactly tdist -- a per-brick bound on |warp(i) - i| from the brick's candidate nodes' DQs, a per-cell
  * "all 64 live voxels == tdist" mask -- skip the warp: s = tdist whatever the position; same bits (dfh_dqb_skip_layout;
  * option k3_skip = 0 switches it off). */
-size_t dfh_dqb_workspace_bytes(const int res[3], int x0, int x1);
-size_t dfh_dqb_workspace_bytes_cached(const int res[3], int x0, int x1, int knn, int n_nodes, int level);
-int dfh_fuse_volume_dqb(void *tsdf, void *tsdf_w, int vol_dtype, const int res[3], int x0, int x1,
-                        const void *live, int live_dtype, const int live_res[3],
-                        const double *node_pos, const double *node_dq, const double *node_w, int n_nodes,
-                        int knn, const double lw_dq[8], double tdist, double wmax,
-                        void *workspace, size_t workspace_bytes, int rebuild_candidates, void *stream);
+size_t dfh_dqb_workspace_bytes(const dfh_slab *slab);
+size_t dfh_dqb_workspace_bytes_cached(const dfh_slab *slab, int knn, int n_nodes, int level);
+int dfh_fuse_volume_dqb(const dfh_volume *vol, const dfh_live *live, const dfh_nodes *nodes, const double lw_dq[8], double tdist,
+                        double wmax, void *workspace, size_t workspace_bytes, int rebuild_candidates, void *stream);
 
 /* ---- warp-field solve ------------------------------------------------------------------------------
  * All arrays device fp64 unless noted; point / normal / node arrays are row-major (n x 3, n x 8).
@@ -230,16 +223,17 @@ int dfh_sample_knn(const double *sample_pos, int n_samples, const double *node_p
  * the 16 node ids (uint16, ascending, 0xffff = none, first = 0xfffe: too many) its voxels blend.  For tests and measurement code:
  * the proof obligation "no voxel moves further than its brick's bound" is checked against [3] (tests/test_gpu_fuse_volume.py).
  * No reference counterpart. */
-int dfh_dqb_skip_layout(const int res[3], int x0, int x1, const int live_res[3], int knn, int n_nodes, size_t out[13]);
+int dfh_dqb_skip_layout(const dfh_slab *slab, const int live_res[3], int knn, int n_nodes, size_t out[13]);
 /* The same through the per-brick candidate lists of a dfh_fuse_volume_dqb workspace (built for the same node_pos, knn,
  * grid and slab by dfh_dqb_build_candidates or by a dfh_fuse_volume_dqb call with rebuild_candidates != 0): a point
  * scans the list of the brick of its nearest voxel centre (the lists carry the head-room that makes this exact for
  * off-lattice points); points outside the slab's lattice and bricks whose list overflowed scan every node.
- * Same output as dfh_sample_knn, bit for bit. */
-int dfh_dqb_build_candidates(const int res[3], int x0, int x1, const double *node_pos, int n_nodes, int knn,
+ * Same output as dfh_sample_knn, bit for bit.  An empty slab (x0 == x1) has no lists: both calls return DFH_OK and write nothing
+ * (dfh_sample_knn is the call for such points). */
+int dfh_dqb_build_candidates(const dfh_slab *slab, const double *node_pos, int n_nodes, int knn,
                              void *workspace, size_t workspace_bytes, void *stream);
 int dfh_sample_knn_bricks(const double *sample_pos, int n_samples, const double *node_pos, const double *node_w,
-                          int n_nodes, int knn, const int res[3], int x0, int x1, const void *workspace,
+                          int n_nodes, int knn, const dfh_slab *slab, const void *workspace,
                           size_t workspace_bytes, int *nbr_out, double *weights_out, void *stream);
 
 /* ---- deformation-graph maintenance: the device side of Fusion.update_graph / construct_graph ---------------------

@@ -1,0 +1,118 @@
+"""CPU: what the K1-K3 entry points that take a dfh_slab or a dfh_volume do with arguments they cannot use.  Validation comes
+before any HIP call, so no GPU is needed: device pointers are dummy non-null integers that nothing dereferences."""
+import ctypes
+import functools
+from concurrent.futures import ThreadPoolExecutor
+
+import pytest
+
+from dynamicfusion_body_amd import _lib, build
+
+OK, BADARG = 0, -1
+PTR = 0x1000                                    # a "device pointer"
+G = (4, 4, 4)
+EYE8 = (ctypes.c_double * 8)(1.0)
+OUT13 = (ctypes.c_size_t * 13)()
+
+# name -> which bad slab
+BAD_SLABS = {
+    "res with a zero": ((4, 0, 4), (0, 4)),
+    "x0 > x1": (G, (3, 2)),
+    "x1 > res[0]": (G, (0, 5)),
+    "65536 planes": ((70000, 4, 4), (0, 65536)),
+}
+
+
+@pytest.fixture(scope="module")
+def lib():
+    build.build_library()
+    return _lib.load()
+
+
+def _volume(slab, dtype=_lib.F32):
+    return _lib.Volume(PTR, PTR, dtype, slab)
+
+
+def _views(n=1):
+    ptrs = (ctypes.c_void_p * 1)(PTR)
+    eye = (ctypes.c_double * 9)(1, 0, 0, 0, 1, 0, 0, 0, 1)
+    v = _lib.DepthViews(n, ptrs, _lib.F32, 8, 8, eye, eye, (ctypes.c_double * 12)(), 1.0, (ctypes.c_double * 3)(), 4)
+    v.keep = ptrs
+    return v
+
+
+LIVE = _lib.Live(PTR, _lib.F32, _lib.iarr(G))
+NODES = _lib.Nodes(PTR, PTR, PTR, 8, 4)
+F12, F3 = (ctypes.c_float * 12)(), (ctypes.c_float * 3)()
+
+# entry point -> call(lib, slab or None); the calls that take a dfh_volume come below
+SLAB_CALLS = {
+    "dfh_integrate_depth_path": lambda lib, s: lib.dfh_integrate_depth_path(_lib.F32, s, 8, 8, 1),
+    "dfh_dqb_skip_layout": lambda lib, s: lib.dfh_dqb_skip_layout(s, _lib.iarr(G), 4, 8, OUT13),
+    "dfh_dqb_build_candidates": lambda lib, s: lib.dfh_dqb_build_candidates(s, PTR, 8, 4, PTR, 1 << 20, None),
+    "dfh_sample_knn_bricks": lambda lib, s: lib.dfh_sample_knn_bricks(PTR, 5, PTR, PTR, 8, 4, s, PTR, 1 << 20, PTR, PTR, None),
+}
+SIZE_QUERIES = {
+    "dfh_integrate_workspace_bytes": lambda lib, s: lib.dfh_integrate_workspace_bytes(1, 8, 8, s),
+    "dfh_dqb_workspace_bytes": lambda lib, s: lib.dfh_dqb_workspace_bytes(s),
+    "dfh_dqb_workspace_bytes_cached": lambda lib, s: lib.dfh_dqb_workspace_bytes_cached(s, 4, 8, 2),
+}
+VOLUME_CALLS = {
+    "dfh_integrate_depth": lambda lib, v: lib.dfh_integrate_depth(v, _views(), 0.1, 100.0, None, None, 0, None),
+    "dfh_integrate_depth_ocl": lambda lib, v: lib.dfh_integrate_depth_ocl(v, PTR, 8, 8, F12, F3, 0.1, 100.0, None),
+    "dfh_fuse_volume_rigid": lambda lib, v: lib.dfh_fuse_volume_rigid(v, LIVE, EYE8, 0.1, 100.0, None),
+    "dfh_fuse_volume_dqb": lambda lib, v: lib.dfh_fuse_volume_dqb(v, LIVE, NODES, EYE8, 0.1, 100.0, PTR, 1 << 20, 1, None),
+}
+
+
+def on_own_thread(test):
+    """dfh_last_error() is kept per thread: the refused calls are made on a thread of their own, so that the main thread's
+    message stays what the tests that read it there expect."""
+    @functools.wraps(test)
+    def run(*args, **kwargs):
+        with ThreadPoolExecutor(1) as ex:
+            return ex.submit(test, *args, **kwargs).result()
+    return run
+
+
+def _refused(lib, name, rc):
+    assert rc == BADARG, (name, rc)
+    assert name.encode() in lib.dfh_last_error(), (name, lib.dfh_last_error())
+
+
+@pytest.mark.parametrize("name", sorted(SLAB_CALLS))
+@on_own_thread
+def test_slab_calls_refuse_bad_slabs(lib, name):
+    _refused(lib, name, SLAB_CALLS[name](lib, None))
+    for res, x_range in BAD_SLABS.values():
+        _refused(lib, name, SLAB_CALLS[name](lib, _lib.slab(res, x_range)))
+    assert SLAB_CALLS[name](lib, _lib.slab(G, (2, 2))) == OK
+
+
+@pytest.mark.parametrize("name", sorted(SIZE_QUERIES))
+@on_own_thread
+def test_size_queries_give_zero(lib, name):
+    assert SIZE_QUERIES[name](lib, None) == 0
+    for res, x_range in BAD_SLABS.values():
+        assert SIZE_QUERIES[name](lib, _lib.slab(res, x_range)) == 0, (name, res, x_range)
+    assert SIZE_QUERIES[name](lib, _lib.slab(G, (2, 2))) == 0
+    assert SIZE_QUERIES[name](lib, _lib.slab(G)) > 0
+
+
+@pytest.mark.parametrize("name", sorted(VOLUME_CALLS))
+@on_own_thread
+def test_volume_calls_refuse_bad_volumes(lib, name):
+    _refused(lib, name, VOLUME_CALLS[name](lib, None))
+    for res, x_range in BAD_SLABS.values():
+        _refused(lib, name, VOLUME_CALLS[name](lib, _volume(_lib.slab(res, x_range))))
+    _refused(lib, name, VOLUME_CALLS[name](lib, _volume(_lib.slab(G), dtype=2)))
+    assert VOLUME_CALLS[name](lib, _volume(_lib.slab(G, (2, 2)))) == OK
+
+
+@on_own_thread
+def test_integrate_depth_without_views(lib):
+    """No views and no fresh value: nothing to do, on a full slab too (no launch); a fresh value on an empty slab likewise."""
+    assert lib.dfh_integrate_depth(_volume(_lib.slab(G)), _views(0), 0.1, 100.0, None, None, 0, None) == OK
+    assert lib.dfh_integrate_depth(_volume(_lib.slab(G, (2, 2))), _views(0), 0.1, 100.0, ctypes.c_double(0.1), None, 0, None) == OK
+    _refused(lib, "dfh_integrate_depth", lib.dfh_integrate_depth(_volume(_lib.slab(G)), None, 0.1, 100.0, None, None, 0, None))
+    _refused(lib, "dfh_integrate_depth", lib.dfh_integrate_depth(_volume(_lib.slab(G)), _views(17), 0.1, 100.0, None, None, 0, None))

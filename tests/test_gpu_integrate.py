@@ -144,7 +144,7 @@ def test_random_views_vs_oracle(res, hw, pinhole, ddt, wmax, reps, vol_dtype):
 @pytest.mark.parametrize("vol_dtype", [torch.float32, torch.float64])
 @pytest.mark.parametrize("res,hw,pinhole,ddt,wmax,reps", CASES)
 def test_multi_view_sweep_equals_consecutive_sweeps(res, hw, pinhole, ddt, wmax, reps, vol_dtype):
-    """dfh_integrate_depth_multi: all views in one sweep of the volume = one dfh_integrate_depth per view in the same
+    """dfh_integrate_depth with several views: all views in one sweep of the volume = one dfh_integrate_depth per view in the same
     order, bit for bit (fp32 volumes: the fused kernel; fp64 volumes: the documented per-view fallback); whole grid
     and slabs; with and without the caller's workspace."""
     rng = np.random.default_rng(hash((res, hw, pinhole, 7)) % (2 ** 31))
@@ -211,8 +211,8 @@ def test_multi_view_sweep_many_views_and_errors():
 
 
 def test_fresh_live_volume_equals_fill_then_sweep(monkeypatch):
-    """dfh_integrate_depth_multi_fresh (the fill of a live volume folded into the multi-view sweep, core/fusion_dm.py:152-153 +
-    :166-170) against T.fill_(value); W.zero_(); dfh_integrate_depth_multi -- every voxel, bit for bit: brick sweep (every brick is
+    """dfh_integrate_depth with a fresh_value (the fill of a live volume folded into the multi-view sweep, core/fusion_dm.py:152-153 +
+    :166-170) against T.fill_(value); W.zero_(); the same call without it -- every voxel, bit for bit: brick sweep (every brick is
     written, culled or not), a slab with global plane indices, the plain sweep (option k1_no_bricks), one view, no view, more
     than 16 views, a ragged grid and a float64 volume; the volumes start as garbage."""
     rng = np.random.default_rng(21)

@@ -31,7 +31,7 @@ F32_MAX = float(np.finfo(np.float32).max)
 
 K1_OPTIONS = ("k1_no_bricks", "k1_bricks_min", "k1_cull", "k1_gather_first", "k1_nzi", "k1_late_loads", "k1_force_scalar", "k1_prefetch")
 COLUMNS = {"k1_bricks_min": 0, "k1_nzi": 16}
-# name -> (options, how): "single" = one dfh_integrate_depth per view, "multi" = dfh_integrate_depth_multi, "fresh" = its fresh
+# name -> (options, how): "single" = one dfh_integrate_depth per view, "multi" = one dfh_integrate_depth for all the views, "fresh" = its fresh
 # variant, "f64" = a float64 volume (the exact kernel).  Grids whose Z is no multiple of 4 (and k1_force_scalar) take VEC = 1
 # instances of the row and multi-view sweeps; they have no column walk and fall back to rows.
 SWEEPS = {
@@ -75,7 +75,7 @@ def run_sweep(name, res, tsdf_res, K, Kinv, scale, center, tdist, wmax, views, d
             for lw, d in zip(lws, ds):
                 kernels.integrate_depth(T, Wt, d, K, Kinv, lw, scale, center, tdist, wmax, tsdf_res=tsdf_res)
         else:
-            # one view would be handed to the single-view sweeps (integrate_multi_impl: n_views == 1): every case passes two or more
+            # one view would be handed to the single-view sweeps (dfh_integrate_depth: n_views == 1): every case passes two or more
             assert len(views) >= 2, "the multi-view sweeps need at least two views"
             if how == "fresh":
                 T.fill_(float("nan")); Wt.fill_(7.0)                                   # garbage: the sweep writes every voxel

@@ -16,16 +16,16 @@ def lib_path():
     return build.build_library()
 
 
-def test_render_symbols_declared_exported_bound_at_abi7(lib_path):
-    """The rasterizer's entry points (added with ABI 5) are declared, exported and bound in the library of ABI 7 (7 passed the
-    GN problem and live frame as structs)."""
+def test_render_symbols_declared_exported_bound_at_abi8(lib_path):
+    """The rasterizer's entry points (added with ABI 5) are declared, exported and bound in the library of ABI 8 (7 passed the
+    GN problem and live frame as structs, 8 the slab, volume, views and nodes of K1-K3)."""
     declared = _lib.declared_symbols()
     lib = ctypes.CDLL(lib_path)
     for name in RENDER_SYMBOLS:
         assert name in declared, name
         assert hasattr(lib, name), name
         assert name in _lib._SIGNATURES, name
-    assert _lib.ABI_VERSION == 7 and _lib.load().dfh_version() == 7
+    assert _lib.ABI_VERSION == 8 and _lib.load().dfh_version() == 8
 
 
 def test_render_workspace_size_query(lib_path):

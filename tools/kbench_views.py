@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""K1 with V views: V consecutive sweeps (dfh_integrate_depth) against one fused sweep (dfh_integrate_depth_multi)."""
+"""K1 with V views: V consecutive sweeps (dfh_integrate_depth) against one fused sweep (dfh_integrate_depth with V views)."""
 import argparse, os, sys
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
