@@ -63,6 +63,11 @@ class Live(ctypes.Structure):
     _fields_ = [("data", _vp), ("dtype", _int), ("res", _int * 3)]
 
 
+class VolumeTerm(ctypes.Structure):
+    """dfh_gn_volume_term: the live TSDF volume the data term is associated against, and the term's settings."""
+    _fields_ = [("live", Live), ("value_to_vox", _dbl), ("band", _dbl), ("max_dist", _dbl), ("min_grad", _dbl)]
+
+
 class DepthViews(ctypes.Structure):
     """dfh_depth_views: n_views depth maps of one size through one camera (depth, lw: host arrays the caller keeps alive)."""
     _fields_ = [("n_views", _int), ("depth", ctypes.POINTER(_vp)), ("depth_dtype", _int), ("H", _int), ("W", _int),
@@ -79,7 +84,8 @@ _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
 _volume_p = ctypes.POINTER(Volume)
 STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams, "dfh_slab": Slab,
-           "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes}
+           "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes,
+           "dfh_gn_volume_term": VolumeTerm}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -114,6 +120,7 @@ _SIGNATURES = {
     "dfh_gn_views_bytes": (ctypes.c_size_t, [_int, _int, _int, _int]),
     "dfh_gn_pack_views": (_int, [_vp, _int, ctypes.POINTER(ctypes.c_void_p), _int, _int, _int, _c_double_p, _vp]),
     "dfh_gn_associate": (_int, [_problem_p, _frame_p, _vp]),
+    "dfh_gn_associate_volume": (_int, [_problem_p, ctypes.POINTER(VolumeTerm), _vp]),
     "dfh_gn_build": (_int, [_problem_p, _frame_p, _vp]),
     "dfh_gn_solve": (_int, [_problem_p, _frame_p, ctypes.POINTER(SolveParams), _vp]),
     "dfh_gn_pack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),

@@ -53,6 +53,28 @@ __device__ __forceinline__ D3 dqb_warp_normal_exact(const double *q, double nx, 
 
 __device__ __forceinline__ double round_f32(double v) { return (double)(float)v; }
 
+// normalised blend of a sample's k node DQs with its static weights (identity when the blend vanishes); returns |b|_8
+// (1 in the degenerate case).  Shared by the GN kernels of dfh_solve.hip and the volume association (dfh_associate_volume.hip).
+constexpr int kBlendKMax = 8;         // knn <= 8 (idx / w hold kBlendKMax entries)
+__device__ __forceinline__ double blend_static(const double *__restrict__ node_dq, const int *idx, const double *w, int k, double *bh) {
+    double b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+    for (int j = 0; j < kBlendKMax; ++j) {
+        if (j < k) {
+#pragma unroll
+            for (int c = 0; c < 8; ++c) b[c] = b[c] + w[j] * node_dq[8 * idx[j] + c];
+        }
+    }
+    double nb = sqrt(((b[0] * b[0] + b[1] * b[1]) + (b[2] * b[2] + b[3] * b[3])) +
+                     ((b[4] * b[4] + b[5] * b[5]) + (b[6] * b[6] + b[7] * b[7])));
+    if (nb == 0.0) { bh[0] = 1.0; for (int c = 1; c < 8; ++c) bh[c] = 0.0; nb = 1.0; }
+    else {
+        const double inv = 1.0 / nb;                      // one division, eight products (each within 1 ulp of b / nb): the GN path has
+        for (int c = 0; c < 8; ++c) bh[c] = b[c] * inv;   // no reference rounding to meet (the residual evaluators use blend_from_indices)
+    }
+    return nb;
+}
+
 // interpolate_tsdf(pos, tsdf), core/util.py:102-137.  Returns false where the reference
 // returns None (:107-108).  x1/y1/z1 = ceil (:113-115); the y-fraction blends the z1 samples
 // and the z-fraction the y1 samples (:121-137) -- reproduced, not fixed.

@@ -530,26 +530,8 @@ struct AssocParams {
     int H, W, k;
 };
 
-// normalised blend of a sample's k node DQs with its static weights (identity when the blend vanishes); returns |b|_8
-// (1 in the degenerate case)
-__device__ __forceinline__ double blend_static(const double *__restrict__ node_dq, const int *idx, const double *w, int k, double *bh) {
-    double b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < kKMaxS; ++j) {
-        if (j < k) {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) b[c] = b[c] + w[j] * node_dq[8 * idx[j] + c];
-        }
-    }
-    double nb = sqrt(((b[0] * b[0] + b[1] * b[1]) + (b[2] * b[2] + b[3] * b[3])) +
-                     ((b[4] * b[4] + b[5] * b[5]) + (b[6] * b[6] + b[7] * b[7])));
-    if (nb == 0.0) { bh[0] = 1.0; for (int c = 1; c < 8; ++c) bh[c] = 0.0; nb = 1.0; }
-    else {
-        const double inv = 1.0 / nb;                      // one division, eight products (each within 1 ulp of b / nb): the GN path has
-        for (int c = 0; c < 8; ++c) bh[c] = b[c] * inv;   // no reference rounding to meet (the residual evaluators use blend_from_indices)
-    }
-    return nb;
-}
+// (blend_static, the normalised blend of a sample's k node DQs with its static weights: dfh_dq.h)
+static_assert(kBlendKMax == kKMaxS, "blend_static reads kKMaxS index / weight slots");
 
 // One live view of a frame in device memory (dfh_gn_pack_views): extrinsic, the inverse of its 3x3 part, the depth map.
 struct AssocView {

@@ -230,19 +230,32 @@ class Fusion:
         exceeds `tolerance` are removed from `_vertices / _normals / _neighbor_look_up / _correspondences`, `_faces`
         is dropped and the nodes are re-anchored to their nearest remaining vertex (:297-313).  Not reproduced: at
         HEAD the pruned index is shadowed by the inner loop variable (`idx_pruned.append(idx)` appends a LIVE vertex
-        index, :273-274) -- the intended canonical index is used.  `live_vertices` replaces the marching-cubes call."""
+        index, :273-274) -- the intended canonical index is used.  `live_vertices` replaces the marching-cubes call.
+        method='sdf' (not in the reference): the correspondences come straight from the live VOLUME (WarpSolver.associate_volume,
+        band = the truncation distance, no gate; the volume holds distances in voxels) and `keep` is the association's validity;
+        the pruning bookkeeping is the same."""
         if self._vertices is None or self._normals is None or len(self._neighbor_look_up) == 0:
             raise ValueError('canonical vertices / normals / _neighbor_look_up have not been set')
         self._curr_tsdf = curr_tsdf
-        lverts = self.marching_cubes(curr_tsdf, step_size=1)[0] if live_vertices is None else np.asarray(live_vertices)
-        if len(lverts) < self._knn:
-            raise ValueError('fewer live vertices than knn')
         V = np.asarray(self._vertices, dtype=np.float64)
         Nn = np.asarray(self._normals, dtype=np.float64)
         nbr = np.asarray(self._neighbor_look_up, dtype=np.int64)
         pos, dq, w, _ = self.node_arrays()
-        vp, wn = _solve.warp_points(V, Nn, np.asarray(self._lw, dtype=np.float64), nbr=nbr, node_dq=dq, node_pos=pos, node_w=w)
-        corr, cost, keep = _solve.closest_correspondences(vp, wn, np.asarray(lverts, dtype=np.float64), self._knn, tolerance)
+        if method == 'sdf':
+            # the volume data term (dfh_gn_associate_volume): every warped vertex takes one Newton step along the live volume's
+            # trilinear gradient onto its zero level set -- no marching cubes of the live volume, no search; vertices whose cell
+            # is not inside the truncation band (or has no usable gradient) get no correspondence and are the ones pruned
+            sv = _solve.WarpSolver(knn=nbr.shape[1], distributed=False)
+            sv.set_graph(pos, dq, w)
+            sv.set_samples(V, Nn, nbr=nbr, sort=False)
+            sv.associate_volume(self._live_to_device(curr_tsdf), np.asarray(self._lw, dtype=np.float64), band=self._tdist)
+            corr, keep = sv.corr, sv.valid
+        else:
+            lverts = self.marching_cubes(curr_tsdf, step_size=1)[0] if live_vertices is None else np.asarray(live_vertices)
+            if len(lverts) < self._knn:
+                raise ValueError('fewer live vertices than knn')
+            vp, wn = _solve.warp_points(V, Nn, np.asarray(self._lw, dtype=np.float64), nbr=nbr, node_dq=dq, node_pos=pos, node_w=w)
+            corr, cost, keep = _solve.closest_correspondences(vp, wn, np.asarray(lverts, dtype=np.float64), self._knn, tolerance)
         corr = corr.cpu().numpy()
         keep = keep.cpu().numpy().astype(bool)
         self._correspondences = corr
@@ -272,10 +285,11 @@ class Fusion:
         the reference: the optional global `_lw` pre-fit on `computef_lw` (:350-364) and the /8
         relaxation of `regularization_weight` while the cost reduction stays in (5 %, 90 %)
         (:405-412), and -- with method='clpts' and no explicit correspondences -- the re-association against
-        the stored live volume after the `_lw` pre-fit and before every later round (:364-365, :370-371)."""
+        the stored live volume after the `_lw` pre-fit and before every later round (:364-365, :370-371).  method='sdf': the
+        same three-round schedule with setupCorrespondences(method='sdf') as the re-association."""
         if correspondences is not None:
             self._correspondences = correspondences
-        reassociate = method == 'clpts' and correspondences is None and self._curr_tsdf is not None
+        reassociate = method in ('clpts', 'sdf') and correspondences is None and self._curr_tsdf is not None
         V, Nn, nbr, C = self._vertex_state()
         pos, dq, w, vidx = self.node_arrays()
         self._itercounter += 1
@@ -285,8 +299,8 @@ class Fusion:
             lw, _ = _solve.solve_rigid_gn(np.asarray(self._lw, dtype=np.float64), x1, n1, C, iters=iterations)
             self._lw = lw
             if reassociate:
-                self.setupCorrespondences(self._curr_tsdf, method='clpts')       # :364-365 (may prune vertices)
-        rounds = 3 if method == 'clpts' else 1
+                self.setupCorrespondences(self._curr_tsdf, method=method)        # :364-365 (may prune vertices)
+        rounds = 3 if method in ('clpts', 'sdf') else 1
 
         def make_solver():
             V, Nn, nbr, C = self._vertex_state()
@@ -302,7 +316,7 @@ class Fusion:
         for rnd in range(rounds):
             if rnd > 0 and reassociate:
                 self._write_back(sv)
-                self.setupCorrespondences(self._curr_tsdf, method='clpts')       # :370-371
+                self.setupCorrespondences(self._curr_tsdf, method=method)        # :370-371
                 sv = make_solver()
             costs = sv.solve_lm(np.asarray(self._lw, dtype=np.float64), regularization_weight, iters=iterations, lm_abs=1e-3,
                                 huber=huber_delta)

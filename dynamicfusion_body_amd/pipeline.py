@@ -113,6 +113,20 @@ class FrameSolver:
             self.solver.build_associated(depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.half, self.lw, rw, max_dist, huber)
             self.solver.global_step(lm_rel)
 
+    def gn_iteration_volume(self, live, band, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.0, n_iters=1, min_grad=0.5,
+                            value_to_vox=1.0):
+        """gn_iteration with the volume data term: associate against the live TSDF volume (WarpSolver.associate_volume) -> build
+        (+ all-reduce) -> PCG -> twist update, n_iters times; asynchronous."""
+        self.solver.iterate_volume(live, self.lw, rw, band, max_dist, huber, lm_abs, lm_rel, n_iters=n_iters, n_global=0,
+                                   min_grad=min_grad, value_to_vox=value_to_vox)
+
+    def global_iteration_volume(self, live, band, rw=5.0, max_dist=2.0, huber=0.0, lm_rel=0.1, n_iters=1, min_grad=0.5, value_to_vox=1.0):
+        """The rigid mode alone with the volume data term, from the built normal equations (associate against the volume ->
+        build (+ all-reduce) -> WarpSolver.global_step), n_iters times; asynchronous.  (There is no sampled rigid-mode step for
+        volumes.)"""
+        self.solver.iterate_volume(live, self.lw, rw, band, max_dist, huber, n_iters=0, n_global=n_iters, global_lm=lm_rel,
+                                   min_grad=min_grad, value_to_vox=value_to_vox)
+
     def solve(self, depth, lw_cam, rw=5.0, iters=10, **kw):
         costs = []
         for _ in range(iters):
@@ -277,8 +291,14 @@ class SlabFrame:
         return _mesh.render(verts, faces, normals, self.K, lws, H, W, scale=self.scale, center=self.center, half=self.R / 2)
 
     def step(self, depth, lw_cam, gn_iters=10, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.5, stage_ms=None,
-             update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None):
-        """Defaults (regulariser weight, LM damping, association gate and Huber threshold in voxels, the per-frame decay of the warp
+             update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None,
+             data_term="depth"):
+        """data_term: "depth" = projective association against the depth maps (one projection and one pixel per sample and
+        view; the live sweep overlaps the whole solve); "volume" = association against the live TSDF volume the frame fuses from
+        all views anyway (FrameSolver.gn_iteration_volume: one trilinear cell per sample whatever the number of views, band =
+        the truncation distance; the live sweep is joined -- and, on several ranks, all-gathered -- BEFORE the solve, the rigid-mode
+        steps come from the built system, and data_views / global_stride do not apply).
+        Defaults (regulariser weight, LM damping, association gate and Huber threshold in voxels, the per-frame decay of the warp
         field `relax` = 0.8) are the ones under which the loop follows a +-0.6 voxel oscillation of the bench scene with a BOUNDED
         warp field: max node translation 0.85 voxel at frame 400, 1.01 at frame 1 200, sample count constant (tools/soak.py;
         tests/test_gpu_pipeline.py::test_soak_300_frames runs 300 of them).  Without the decay (relax = 1, round 3) nothing
@@ -289,6 +309,8 @@ class SlabFrame:
         on_updated: optional callable, called once the launches of this frame's TSDF update are queued and `self.updated` is
         recorded -- the place where a consumer of the updated canonical slab (mesh extraction on another stream) queues its
         first launches, ahead of the sample refresh's."""
+        if data_term not in ("depth", "volume"):
+            raise ValueError("data_term must be 'depth' or 'volume'")
         import time as _t
         t0 = [_t.perf_counter()]
 
@@ -336,16 +358,33 @@ class SlabFrame:
         # the rigid mode first (two steps: one twist shared by all nodes, fitted to the data rows -- FrameSolver.global_iteration),
         # then the node iterations (one host call: nothing between their launches depends on the host)
         ng = self.GLOBAL_ITERS if global_iters is None else int(global_iters)
-        if ng > 0:
+        live_full = None
+        if data_term == "volume":
+            # the solve reads the live volume: the side stream (which has overlapped the plan's launches) joins here, and the
+            # whole volume is gathered now -- the TSDF update below reuses it
+            if not joined:
+                torch.cuda.current_stream().wait_stream(self._side)
+                joined = True
+            live_full = self.D.allgather_planes(self.live, R) if self.ws > 1 else self.live
+            # band = the truncation distance AS STORED (the sweep's fresh value, rounded to the volume's type): the band test is
+            # strict, so the cells that touch a voxel no view updated drop out
+            band = float(torch.tensor(self.tvox, dtype=self.live.dtype))
+            if ng > 0:
+                self.fs.global_iteration_volume(live_full, band, rw=rw, max_dist=max_dist, huber=huber, lm_rel=global_lm, n_iters=ng)
+            self.fs.gn_iteration_volume(live_full, band, rw=rw, lm_abs=lm_abs, lm_rel=lm_rel, max_dist=max_dist, huber=huber,
+                                        n_iters=gn_iters)
+        elif ng > 0:
             # (every `global_stride`-th tile of THIS rank's samples: with the samples sharded over ranks a stride > 1 thins another
             # subsample than one GPU does -- the same estimator on other data; stride 1 is partition-independent)
             self.fs.global_iteration(solve_depth, solve_lw, max_dist=max_dist, huber=huber, lm_rel=global_lm, n_iters=ng,
                                      stride=self.GLOBAL_STRIDE if global_stride is None else int(global_stride))
-        self.fs.gn_iteration(solve_depth, solve_lw, rw=rw, lm_abs=lm_abs, lm_rel=lm_rel, max_dist=max_dist, huber=huber, n_iters=gn_iters)
+        if data_term == "depth":
+            self.fs.gn_iteration(solve_depth, solve_lw, rw=rw, lm_abs=lm_abs, lm_rel=lm_rel, max_dist=max_dist, huber=huber, n_iters=gn_iters)
         mark("solve")
         if not joined:
             torch.cuda.current_stream().wait_stream(self._side)
-        live_full = self.D.allgather_planes(self.live, R) if self.ws > 1 else self.live
+        if live_full is None:
+            live_full = self.D.allgather_planes(self.live, R) if self.ws > 1 else self.live
         mark("allgather")
         sv = self.fs.solver
         kernels.fuse_volume_dqb(self.T, self.Wt, live_full, sv.node_pos, sv.node_dq, sv.node_w, self.knn, self.ident_lw, self.tvox,

@@ -215,6 +215,13 @@ class _AsyncScalar:
         return v
 
 
+def _check_live(live):
+    """What the volume data term accepts as a live volume (checked before anything is loaded or launched)."""
+    if not (isinstance(live, torch.Tensor) and live.is_cuda and live.dim() == 3 and live.is_contiguous()
+            and live.dtype in (torch.float32, torch.float64)):
+        raise ValueError("live must be a contiguous 3-D CUDA tensor, float32 or float64")
+
+
 # ------------------------------------------------------------------------------ non-rigid solver
 class WarpSolver:
     """Gauss-Newton / LM solver for the node dual quaternions.
@@ -223,7 +230,8 @@ class WarpSolver:
     set_samples() canonical sample points + normals; computes (or takes) their k nearest nodes and
                   static blend weights, sorts the samples by node tuple and builds the 6x6
                   block pattern of J^T J
-    set_correspondences() / associate_depth()  fixed correspondences or projective association
+    set_correspondences() / associate_depth() / associate_volume()  fixed correspondences, projective association against
+                  depth maps, or association against a live TSDF volume
     step()        one iteration: build -> PCG -> twist update (asynchronous)
     """
 
@@ -238,6 +246,7 @@ class WarpSolver:
         self.node_nbr = None
         self.S = 0
         self._prob, self._frm, self._sp = _lib.Problem(), _lib.Frame(), _lib.SolveParams()     # the C ABI's structs, refilled per call
+        self._term = _lib.VolumeTerm()
         if _dist.ranks_share_a_gpu():                  # (whether or not THIS solver runs collectives: ADVICE round 2)
             # several processes time-share this GPU (a rehearsal of the multi-GPU job on one card): co-residency of the
             # persistent PCG's workgroups is not guaranteed across processes -> two launches per iteration, no grid barrier
@@ -654,6 +663,34 @@ class WarpSolver:
         the observed surface (dfh_gn_associate)."""
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
         _lib.check(self.lib.dfh_gn_associate(self._problem(lw_dq), frame, current_stream_ptr()), "dfh_gn_associate")
+
+    def associate_volume(self, live, lw_dq, band, max_dist=0.0, min_grad=0.5, value_to_vox=1.0):
+        """Association of the warped samples against a live TSDF VOLUME (dfh_gn_associate_volume): one trilinear cell per
+        sample, one Newton step along the interpolant's gradient onto its zero level set -- whatever the number of views
+        that were fused into the volume.  live: the WHOLE live volume, a contiguous 3-D CUDA tensor, float32 or float64,
+        holding distances in units of 1 / value_to_vox voxels.  A cell is used iff all eight corners lie strictly inside
+        +-band voxels (band = the truncation distance drops the cells a fresh sweep never touched), its gradient is at
+        least min_grad, and -- max_dist > 0 -- the Newton point lies within max_dist voxels.  Writes corr / valid."""
+        _check_live(live)
+        t = self._term
+        t.live.data, t.live.dtype, t.live.res = live.data_ptr(), dtype_code(live), _lib.iarr(live.shape)
+        t.value_to_vox, t.band, t.max_dist, t.min_grad = float(value_to_vox), float(band), float(max_dist), float(min_grad)
+        _lib.check(self.lib.dfh_gn_associate_volume(self._problem(lw_dq), t, current_stream_ptr()), "dfh_gn_associate_volume")
+
+    def iterate_volume(self, live, lw_dq, rw, band, max_dist=0.0, huber=0.0, lm_abs=0.0, lm_rel=0.0, n_iters=1, n_global=0,
+                       global_lm=0.1, min_grad=0.5, value_to_vox=1.0):
+        """The loop of iterate_associated with the volume data term: n_global x [associate_volume -> build -> global_step],
+        then n_iters x [associate_volume -> build -> solve_update]; asynchronous.  The association is a launch of its own in
+        front of the unchanged build (which all-reduces: the sharded multi-rank solve works as it does for depth maps)."""
+        _check_live(live)
+        for _ in range(int(n_global)):
+            self.associate_volume(live, lw_dq, band, max_dist, min_grad, value_to_vox)
+            self.build(lw_dq, rw, huber)
+            self.global_step(global_lm)
+        for _ in range(int(n_iters)):
+            self.associate_volume(live, lw_dq, band, max_dist, min_grad, value_to_vox)
+            self.build(lw_dq, rw, huber)
+            self.solve_update(lm_abs, lm_rel)
 
     # -- iteration ---------------------------------------------------------------------------
     def build(self, lw_dq, rw, huber=0.0):

@@ -357,6 +357,39 @@ int dfh_gn_pack_views(void *out, int n_views, const void *const *depth, int dept
 /* corr / valid of the problem's samples against the frame (no system is touched). */
 int dfh_gn_associate(const dfh_gn_problem *problem, const dfh_gn_frame *frame, void *stream);
 
+/* The volume data term: corr / valid of the problem's samples against a live TSDF VOLUME (no system is touched; the contract of
+ * dfh_gn_associate: reads the samples, nbr, weights, node_dq, lw_dq and knn, writes corr and valid; dfh_gn_build(problem, NULL)
+ * then builds from them).  One trilinear cell per sample, whatever the number of views that were fused into the volume.  Not in
+ * the reference, whose Fusion.setupCorrespondences(volume) runs marching cubes on the live volume and a KD-tree search
+ * (core/fusion.py:255-276).  Everything is fp64, operation by operation in this order, no contraction:
+ *  1. x' = (X0, X1, X2): the sample warped exactly as dfh_gn_associate warps it (the normalised static blend of its knn node DQs,
+ *     then dqb_warp with the blend and with lw_dq, positions rounded to float32 where Fusion.warp rounds them).
+ *  2. in grid: per axis a, 0 <= Xa and Xa < res[a] - 1, tested on the doubles (NaN and infinities fail); ia = floor(Xa),
+ *     fa = Xa - ia.
+ *  3. corners u[a][b][c] = (double)live[((i0+a)*res[1] + (i1+b))*res[2] + (i2+c)] * value_to_vox: the STANDARD trilinear cell, f0
+ *     with axis 0, f1 with axis 1, f2 with axis 2 -- NOT interpolate_tsdf's sampler (core/util.py:102-137: ceil() corners, y / z
+ *     fractions swapped), the reference's quirk that dfh_fuse_volume_rigid / _dqb reproduce for updateTSDF only.
+ *  4. band: all eight corners satisfy fabs(u) < band (strict; a NaN corner fails).  A voxel a fresh dfh_integrate_depth sweep never
+ *     updated holds exactly tdist: with band = tdist the cells behind the surface and in free space drop out without a weight volume.
+ *  5. e[a][b] = u[a][b][0] + f2*(u[a][b][1] - u[a][b][0]);  h[a] = e[a][0] + f1*(e[a][1] - e[a][0]);  s = h[0] + f0*(h[1] - h[0]);
+ *     g0 = h[1] - h[0];  dy[a] = e[a][1] - e[a][0], g1 = dy[0] + f0*(dy[1] - dy[0]);  dz[a][b] = u[a][b][1] - u[a][b][0],
+ *     m[a] = dz[a][0] + f1*(dz[a][1] - dz[a][0]), g2 = m[0] + f0*(m[1] - m[0])     (s and its gradient g at x', in voxels).
+ *  6. G = (g0*g0 + g1*g1) + g2*g2; usable iff G >= min_grad*min_grad and G > 0 (always: t below divides by it); with
+ *     max_dist > 0 also s*s <= (max_dist*max_dist)*G, i.e. |c - x'| <= max_dist without a square root.
+ *  7. t = s / G, corr = x' - t*g (one Newton step onto the zero level set of the interpolant), valid = 1.  If any test fails:
+ *     valid = 0 and corr = (0, 0, 0) -- every row is written on every call.
+ * DFH_E_BADARG (before any HIP call): null problem / term / node_dq / live.data, null sample_pos / nbr / weights / corr / valid
+ * with n_samples > 0, knn outside 1..8, n_nodes < 1, n_samples < 0, a live dtype other than DFH_F32 / DFH_F64, a res < 2,
+ * value_to_vox zero or not finite, band not > 0, min_grad negative or NaN, max_dist NaN.  n_samples == 0: DFH_OK, no launch. */
+typedef struct dfh_gn_volume_term {
+    dfh_live live;        /* the WHOLE live volume, z fastest, DFH_F32 or DFH_F64, every res >= 2 */
+    double value_to_vox;  /* stored value * value_to_vox = distance in voxels; finite, != 0 */
+    double band;          /* > 0, voxels: a cell is usable iff all 8 corners have |u| < band (strict) */
+    double max_dist;      /* gate in voxels on |c - x'|; <= 0: none */
+    double min_grad;      /* >= 0: usable iff |g|^2 >= min_grad^2 */
+} dfh_gn_volume_term;
+int dfh_gn_associate_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, void *stream);
+
 /* The normal equations of the problem.  frame == NULL: corr / valid are inputs.  frame != NULL: the association is fused into
  * the data-row kernel -- every sample is warped once, associated as by dfh_gn_associate (corr / valid receive the same values,
  * bit for bit) and the valid ones go straight on to their Jacobian rows; it needs the data plan and DFH_F32 maps. */
