@@ -1653,6 +1653,15 @@ __global__ __launch_bounds__(256) void sample_knn_bricks_kernel(const double *__
             if (j0 + u < total && d2 < bd[KS - 1]) topk_insert<KS>(bd, bi, d2, g[u]);
         }
     }
+    // A non-finite point (never `inside`: it scanned every node and no d2 compared below +inf, the slots keep index -1): nodes
+    // 0..k-1 with weight 0, as dfh_sample_knn writes them.
+    bool full = true;
+#pragma unroll
+    for (int j = 0; j < KS; ++j) full = full && (j >= p.k || bi[j] >= 0);
+    if (!full) {
+        for (int j = 0; j < p.k; ++j) { nbr[(size_t)i * p.k + j] = j; wts[(size_t)i * p.k + j] = 0.0; }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < KS; ++j) {
         if (j < p.k) {

@@ -290,6 +290,16 @@ __global__ __launch_bounds__(256) void closest_corr_kernel(const double *__restr
         __syncthreads();
     }
     if (!act) return;
+    // A non-finite position has no neighbours (no d2 compares below +inf, the slots keep index -1): no correspondence.
+    bool full = true;
+#pragma unroll
+    for (int j = 0; j < kKMaxS; ++j) full = full && (j >= k || bi[j] >= 0);
+    if (!full) {
+        corr[3 * (size_t)i] = 0.0; corr[3 * (size_t)i + 1] = 0.0; corr[3 * (size_t)i + 2] = 0.0;
+        if (cost_out) cost_out[i] = __builtin_huge_val();
+        keep[i] = 0;
+        return;
+    }
     const double nx = wnrm[3 * (size_t)i], ny = wnrm[3 * (size_t)i + 1], nz = wnrm[3 * (size_t)i + 2];
     double best_cost = 1.0;                                     // fusion_dm.py:234
     int best = bi[0];                                           // lverts[nidxs[0]], :233
@@ -338,7 +348,7 @@ __global__ __launch_bounds__(256) void nearest_point_kernel(const double *__rest
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        idx_out[qi] = si[0];
+        idx_out[qi] = si[0] == 0x7fffffff ? -1 : si[0];  // (a non-finite query: no thread found a point; d2 = +inf)
         if (d2_out) d2_out[qi] = sd[0];
     }
 }
@@ -397,10 +407,12 @@ __global__ __launch_bounds__(256) void sample_knn_kernel(const double *__restric
     const int i = blockIdx.x * 256 + tid;
     const bool act = i < S;
     const double px = act ? spos[3 * (size_t)i] : 0.0, py = act ? spos[3 * (size_t)i + 1] : 0.0, pz = act ? spos[3 * (size_t)i + 2] : 0.0;
-    // ---- bounding box of the workgroup's samples
+    // ---- bounding box of the workgroup's samples (the finite ones: a non-finite sample has no neighbours and must not
+    //      widen the box of the samples it shares the workgroup with)
     {
         const double big = __builtin_huge_val();
-        double v[6] = {act ? px : big, act ? py : big, act ? pz : big, act ? -px : big, act ? -py : big, act ? -pz : big};   // min of (x, -x)
+        const bool fin = act && isfinite(px) && isfinite(py) && isfinite(pz);
+        double v[6] = {fin ? px : big, fin ? py : big, fin ? pz : big, fin ? -px : big, fin ? -py : big, fin ? -pz : big};   // min of (x, -x)
 #pragma unroll
         for (int c = 0; c < 6; ++c) {
 #pragma unroll
@@ -492,6 +504,14 @@ __global__ __launch_bounds__(256) void sample_knn_kernel(const double *__restric
         }
     }
     if (!act) return;
+    // A non-finite sample found no neighbour (the slots keep index -1): nodes 0..k-1 with weight 0, as dfh_sample_knn_bricks does.
+    bool full = true;
+#pragma unroll
+    for (int j = 0; j < kKMaxS; ++j) full = full && (j >= k || bi[j] >= 0);
+    if (!full) {
+        for (int j = 0; j < k; ++j) { nbr[(size_t)i * k + j] = j; wts[(size_t)i * k + j] = 0.0; }
+        return;
+    }
 #pragma unroll
     for (int j = 0; j < kKMaxS; ++j) {
         if (j < k) {

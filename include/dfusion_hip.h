@@ -205,14 +205,20 @@ int dfh_warp_points(const double *verts, const double *normals, const int *nbr, 
 /* The selection loop of setupCorrespondences (core/fusion_dm.py:229-244; core/fusion.py:258-276, 'clpts'):
  * for every warped vertex the knn nearest live vertices (nearest first), best = the first with the smallest
  * cost |wn . (vp - p)| below the initial best_cost 1 (else the nearest), keep = best_cost <= tolerance.
- * corr_out n x 3, cost_out n (may be NULL), keep_out n uint8. */
+ * corr_out n x 3, cost_out n (may be NULL), keep_out n uint8.
+ * A warped vertex whose position is not finite (NaN or +-inf in any coordinate; in general: fewer than knn live vertices at a
+ * finite squared distance) has no neighbours: corr_out = (0, 0, 0), cost_out = +inf, keep_out = 0.  A NaN normal at a finite
+ * position is the reference's case "no cost below 1": best = the nearest, cost = 1. */
 int dfh_closest_correspondences(const double *warped_pos, const double *warped_nrm, int n_verts, const double *live_verts,
                                 int n_live, int knn, double tolerance, double *corr_out, double *cost_out,
                                 unsigned char *keep_out, void *stream);
 
 /* k nearest nodes (nearest first; KDTree.query order, core/fusion.py:121-123) and the Gaussian DQB
  * weights exp(-(|p - v_j| / (2 w_j))^2) (:537) of arbitrary sample points.  Both are static while the
- * graph is unchanged.  nbr_out: n_samples x knn int32; weights_out: n_samples x knn. */
+ * graph is unchanged.  nbr_out: n_samples x knn int32; weights_out: n_samples x knn.
+ * A sample whose position is not finite (in general: fewer than knn nodes at a finite squared distance) has no neighbours:
+ * nbr_out = 0 .. knn-1 and every weight 0 (valid indices, a vanishing blend); the finite samples around it are unaffected.
+ * dfh_sample_knn_bricks does the same. */
 int dfh_sample_knn(const double *sample_pos, int n_samples, const double *node_pos, const double *node_w, int n_nodes,
                    int knn, int *nbr_out, double *weights_out, void *stream);
 /* Where the constant-live skip of dfh_fuse_volume_dqb (float32 volumes, knn = 4, stored neighbourhoods, m_lw = identity; round 4)
@@ -240,7 +246,8 @@ int dfh_sample_knn_bricks(const double *sample_pos, int n_samples, const double 
  * (core/fusion.py:101-123, 201-239; the greedy radius subsampling of the unsupported vertices, core/util.py:27-47, is
  * sequential by definition and stays with the caller).
  * dfh_nearest_points: idx_out[q] = nearest cloud point of query q (KDTree(cloud).query(q), :209-212 -- a node's anchor
- *   vertex; ties go to the lower index), d2_out (may be NULL) its squared distance.
+ *   vertex; ties go to the lower index), d2_out (may be NULL) its squared distance.  A query that is not finite (no cloud
+ *   point at a finite squared distance): idx_out = -1, d2_out = +inf.
  * dfh_graph_unsupported: flag_out[v] = 1 iff min over the vertex's knn nodes nbr[v][.] of |node - v| / node_w >= 1
  *   (the "unsupported surface point" test, :215-219).
  * dfh_dq_blend_points: dq_out[p] = Fusion.dq_blend(points[p]) over the nodes nbr[p][.] (:527-551; the DQ a newly

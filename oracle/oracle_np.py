@@ -459,17 +459,97 @@ def closest_correspondences(warped_pos, warped_nrm, live_verts, k, tolerance):
     vp = np.asarray(warped_pos, dtype=np.float64)
     wn = np.asarray(warped_nrm, dtype=np.float64)
     lv = np.asarray(live_verts, dtype=np.float64)
-    nidx = knn_bruteforce(vp, lv, k)                      # (V,k)
-    P = lv[nidx]
-    d = vp[:, None, :] - P
-    cost = np.abs(wn[:, None, 0] * d[..., 0] + wn[:, None, 1] * d[..., 1] + wn[:, None, 2] * d[..., 2])
-    best_cost = np.ones(len(vp))
-    best = P[:, 0, :].copy()
-    for j in range(k):
-        better = cost[:, j] < best_cost
-        best_cost = np.where(better, cost[:, j], best_cost)
-        best = np.where(better[:, None], P[:, j, :], best)
-    return best, best_cost, best_cost <= tolerance
+    with np.errstate(invalid="ignore", over="ignore"):
+        nidx = knn_bruteforce(vp, lv, k)                      # (V,k)
+        P = lv[nidx]
+        d = vp[:, None, :] - P
+        cost = np.abs(wn[:, None, 0] * d[..., 0] + wn[:, None, 1] * d[..., 1] + wn[:, None, 2] * d[..., 2])
+        best_cost = np.ones(len(vp))
+        best = P[:, 0, :].copy()
+        for j in range(k):
+            better = cost[:, j] < best_cost
+            best_cost = np.where(better, cost[:, j], best_cost)
+            best = np.where(better[:, None], P[:, j, :], best)
+    # a row with fewer than k live vertices at a finite squared distance (a non-finite warped position) has no neighbours:
+    # include/dfusion_hip.h defines corr = 0, cost = +inf, keep = 0 (the reference leaves it undefined)
+    none = _finite_d2(vp, lv).sum(axis=1) < k
+    best = np.where(none[:, None], 0.0, best)
+    best_cost = np.where(none, np.inf, best_cost)
+    return best, best_cost, (best_cost <= tolerance) & ~none
+
+
+def _sq_dist(a, b):
+    """(dx dx + dy dy) + dz dz of every a against every b: the operation order of the device kernels."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = np.asarray(a, dtype=np.float64)[:, None, :] - np.asarray(b, dtype=np.float64)[None, :, :]
+        return d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]
+
+
+def _finite_d2(a, b):
+    return _sq_dist(a, b) < np.inf                        # (False for NaN and for an overflowed distance)
+
+
+# ------------------------------------------------------------------------------------------------
+# the small device kernels of the solver's set-up and the graph maintenance: definitions, no reference counterpart beyond the
+# lines cited (include/dfusion_hip.h)
+# ------------------------------------------------------------------------------------------------
+
+def nearest_points(query, cloud):
+    """dfh_nearest_points (KDTree(cloud).query(q), core/fusion.py:209-212): per query the lexicographic minimum of
+    (d2, index) over the cloud.  Returns (idx (Q,) int32, d2 (Q,)); a query without a cloud point at a finite squared
+    distance (a non-finite query): idx = -1, d2 = +inf."""
+    d2 = _sq_dist(query, cloud)
+    d2 = np.where(d2 < np.inf, d2, np.inf)
+    idx = np.argmin(d2, axis=1)                           # the first minimum: ties go to the lower index
+    best = d2[np.arange(len(d2)), idx]
+    return np.where(best < np.inf, idx, -1).astype(np.int32), best
+
+
+def sample_knn(pos, node_pos, node_w, k):
+    """dfh_sample_knn / dfh_sample_knn_bricks: (nbr (S,k) int32, weights (S,k)) -- knn_bruteforce and the Gaussian weights
+    exp(-(sqrt(d2) / (2 w))^2) of core/fusion.py:537; a sample with fewer than k nodes at a finite squared distance (a non-finite
+    sample): nodes 0..k-1, weights 0."""
+    node_w = np.asarray(node_w, dtype=np.float64)
+    d2 = _sq_dist(pos, node_pos)
+    none = (d2 < np.inf).sum(axis=1) < k
+    nbr = np.argsort(np.where(none[:, None], 0.0, d2), axis=1, kind="stable")[:, :k]      # (rows of zeros sort to 0..k-1)
+    t = np.sqrt(np.take_along_axis(np.where(none[:, None], 0.0, d2), nbr, axis=1)) / (2.0 * node_w[nbr])
+    return nbr.astype(np.int32), np.where(none[:, None], 0.0, np.exp(-1.0 * (t * t)))
+
+
+def unsupported_vertices(vertices, nbr, node_pos, node_w):
+    """dfh_graph_unsupported, the test of update_graph (core/fusion.py:215-219): True where the minimum over the vertex's
+    nodes nbr[v] of |node - v| / w is >= 1."""
+    v = np.asarray(vertices, dtype=np.float64)
+    d = np.asarray(node_pos, dtype=np.float64)[nbr] - v[:, None, :]
+    r = np.sqrt(d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1] + d[..., 2] * d[..., 2]) / np.asarray(node_w, dtype=np.float64)[nbr]
+    return r.min(axis=1) >= 1.0
+
+
+def permute_samples(order, pos, nrm, nbr, weights):
+    """dfh_permute_samples: out[i] = in[order[i]] for the four per-sample arrays."""
+    return pos[order], nrm[order], nbr[order], weights[order]
+
+
+def pack_upper(system, rows, col, src, n_nodes, n_upper):
+    """dfh_gn_pack_upper: the blocks with col >= row at their place src[b] among the packed ones, then the tail (J^T r, cost,
+    count).  system: flat (36 B + 6 N + 2)."""
+    B = len(col)
+    blocks = system[:36 * B].reshape(B, 36)
+    up = col >= rows
+    packed = np.zeros(36 * n_upper + 6 * n_nodes + 2)
+    packed[:36 * n_upper].reshape(n_upper, 36)[src[up]] = blocks[up]
+    packed[36 * n_upper:] = system[36 * B:]
+    return packed
+
+
+def unpack_upper(packed, rows, col, src, n_nodes, n_upper):
+    """dfh_gn_unpack_upper: every block from the packed block src[b] -- as it is when col >= row, transposed when col < row
+    (its mirror's data) -- then the tail."""
+    B = len(col)
+    pb = packed[:36 * n_upper].reshape(n_upper, 6, 6)[src]
+    blocks = np.where((col >= rows)[:, None, None], pb, pb.transpose(0, 2, 1))
+    return np.concatenate([blocks.reshape(-1), packed[36 * n_upper:]])
 
 
 # ------------------------------------------------------------------------------------------------ A2 (optional)

@@ -1,5 +1,6 @@
-"""CPU: what the K1-K3 entry points that take a dfh_slab or a dfh_volume do with arguments they cannot use.  Validation comes
-before any HIP call, so no GPU is needed: device pointers are dummy non-null integers that nothing dereferences."""
+"""CPU: what the K1-K3 entry points that take a dfh_slab or a dfh_volume, and the point-query / residual / graph entry points of the
+solve, do with arguments they cannot use.  Validation comes before any HIP call, so no GPU is needed: device pointers are dummy
+non-null integers that nothing dereferences."""
 import ctypes
 import functools
 from concurrent.futures import ThreadPoolExecutor
@@ -116,3 +117,69 @@ def test_integrate_depth_without_views(lib):
     assert lib.dfh_integrate_depth(_volume(_lib.slab(G, (2, 2))), _views(0), 0.1, 100.0, ctypes.c_double(0.1), None, 0, None) == OK
     _refused(lib, "dfh_integrate_depth", lib.dfh_integrate_depth(_volume(_lib.slab(G)), None, 0.1, 100.0, None, None, 0, None))
     _refused(lib, "dfh_integrate_depth", lib.dfh_integrate_depth(_volume(_lib.slab(G)), _views(17), 0.1, 100.0, None, None, 0, None))
+
+
+# ---- the point-query, residual and graph entry points: sizes first, then "nothing to do", then pointers ----------------------
+# call(lib, n, knn, m, ptr): n rows, m live vertices / cloud points / nodes, every pointer = ptr
+POINT_CALLS = {
+    "dfh_closest_correspondences": lambda lib, n, knn, m, p: lib.dfh_closest_correspondences(p, p, n, p, m, knn, 0.2, p, None, p, None),
+    "dfh_nearest_points": lambda lib, n, knn, m, p: lib.dfh_nearest_points(p, n, p, m, p, None, None),
+    "dfh_graph_unsupported": lambda lib, n, knn, m, p: lib.dfh_graph_unsupported(p, n, p, knn, p, p, m, p, None),
+    "dfh_dq_blend_points": lambda lib, n, knn, m, p: lib.dfh_dq_blend_points(p, n, p, knn, p, p, p, m, p, None),
+    "dfh_sample_knn": lambda lib, n, knn, m, p: lib.dfh_sample_knn(p, n, p, p, m, knn, p, p, None),
+    "dfh_residual_data": lambda lib, n, knn, m, p: lib.dfh_residual_data(p, p, p, p, n, knn, p, p, p, m, EYE8 if p else None, p, None),
+    "dfh_residual_reg": lambda lib, n, knn, m, p: lib.dfh_residual_reg(p, n, knn, p, p, p, 1.0, p, None),
+    "dfh_warp_points": lambda lib, n, knn, m, p: lib.dfh_warp_points(p, p, p, n, knn, p, p, p, m, EYE8 if p else None, p, p, None),
+    "dfh_permute_samples": lambda lib, n, knn, m, p: lib.dfh_permute_samples(p, n, knn, p, p, p, p, p, p, p, p, None),
+}
+NEEDS_M_GE_KNN = ("dfh_closest_correspondences", "dfh_sample_knn")          # knn neighbours out of m points
+NEEDS_M_GE_1 = ("dfh_nearest_points", "dfh_graph_unsupported", "dfh_dq_blend_points", "dfh_residual_data")
+NO_KNN = ("dfh_nearest_points",)
+
+
+@pytest.mark.parametrize("name", sorted(POINT_CALLS))
+@on_own_thread
+def test_point_calls_refuse_bad_sizes_and_null_pointers(lib, name):
+    call = POINT_CALLS[name]
+    _refused(lib, name, call(lib, -1, 4, 8, PTR))                           # a negative count
+    _refused(lib, name, call(lib, 5, 4, 8, None))                           # null pointers with a positive count
+    if name not in NO_KNN:
+        if name == "dfh_warp_points":                                       # (knn matters only with a neighbour table: it has one here)
+            _refused(lib, name, call(lib, 5, 0, 8, PTR))
+            _refused(lib, name, call(lib, 5, 9, 8, PTR))
+        else:
+            _refused(lib, name, call(lib, 0, 0, 8, PTR))                    # knn 0 and knn 9, refused even with nothing to do
+            _refused(lib, name, call(lib, 0, 9, 16, PTR))
+    if name in NEEDS_M_GE_KNN:
+        _refused(lib, name, call(lib, 5, 4, 3, PTR))                        # n_live / n_nodes < knn
+        _refused(lib, name, call(lib, 0, 4, 3, None))
+        _refused(lib, name, call(lib, 5, 1, 0, PTR))
+        _refused(lib, name, call(lib, 5, 4, -1, PTR))
+    if name in NEEDS_M_GE_1:
+        _refused(lib, name, call(lib, 5, 4, 0, PTR))                        # n_cloud = 0 / no nodes
+        _refused(lib, name, call(lib, 0, 4, 0, None))
+        _refused(lib, name, call(lib, 5, 4, -3, PTR))
+    assert call(lib, 0, 4, 8, None) == OK                                   # a count of 0 with null pointers: nothing to do
+    assert call(lib, 0, 8, 8, PTR) == OK and call(lib, 0, 1, 8, PTR) == OK  # (knn 8 and 1 are inside the range)
+
+
+@on_own_thread
+def test_warp_points_refuses_normals_out_without_normals(lib):
+    _refused(lib, "dfh_warp_points", lib.dfh_warp_points(PTR, None, None, 5, 1, None, None, None, 0, EYE8, PTR, PTR, None))
+    _refused(lib, "dfh_warp_points", lib.dfh_warp_points(PTR, PTR, PTR, 5, 4, PTR, PTR, PTR, 0, EYE8, PTR, PTR, None))      # a table, no nodes
+    _refused(lib, "dfh_warp_points", lib.dfh_warp_points(PTR, PTR, PTR, 5, 4, None, PTR, PTR, 8, EYE8, PTR, PTR, None))
+    _refused(lib, "dfh_warp_points", lib.dfh_warp_points(PTR, PTR, None, 5, 4, None, None, None, 0, None, PTR, PTR, None))  # no lw_dq
+
+
+@pytest.mark.parametrize("name", ["dfh_gn_pack_upper", "dfh_gn_unpack_upper"])
+@on_own_thread
+def test_pack_upper_refuses_bad_arguments(lib, name):
+    fn = getattr(lib, name)
+    _refused(lib, name, fn(None, None, None, None, 0, 0, 0, None, None))     # (these two always launch: no "nothing to do" form)
+    for i in range(4):
+        ptrs = [PTR] * 4
+        ptrs[i] = None
+        _refused(lib, name, fn(*ptrs, 4, 2, 3, PTR, None))
+    _refused(lib, name, fn(PTR, PTR, PTR, PTR, 4, 2, 3, None, None))
+    for counts in ((-1, 2, 3), (4, -1, 3), (4, 2, -1)):
+        _refused(lib, name, fn(PTR, PTR, PTR, PTR, *counts, PTR, None))
