@@ -2721,6 +2721,20 @@ __global__ __launch_bounds__(256) void apply_twist_kernel(double *__restrict__ n
                     step * xi[6 * a + 4], step * xi[6 * a + 5]);
 }
 
+// The multi-launch PCG's twist update, all or nothing like the persistent kernel's: x is final when this launch starts, so every
+// workgroup looks at all 6N entries itself (same answer in each; no atomics, no host round trip) and applies its 256 twists only
+// if every one is finite -- a NaN or an infinity in the system leaves node_dq as it was before the solve.
+__global__ __launch_bounds__(256) void apply_twist_if_finite_kernel(double *__restrict__ node_dq, const double *__restrict__ xi, int N,
+                                                                     double step) {
+    bool bad = false;
+    for (int r = (int)threadIdx.x; r < 6 * N; r += 256) bad = bad || !(fabs(xi[r]) < __builtin_huge_val());
+    if (__syncthreads_or(bad ? 1 : 0)) return;
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= N) return;
+    apply_twist_one(node_dq + 8 * (size_t)a, step * xi[6 * a], step * xi[6 * a + 1], step * xi[6 * a + 2], step * xi[6 * a + 3],
+                    step * xi[6 * a + 4], step * xi[6 * a + 5]);
+}
+
 }  // namespace dfh
 
 // =================================================================================== C ABI
@@ -3394,7 +3408,7 @@ static int pcg_solve_impl(const int *row_ptr, const int *col, double *vals, cons
         double *t = p_prev; p_prev = p_cur; p_cur = t;
     }
     if (update_dq)
-        hipLaunchKernelGGL(apply_twist_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, s, update_dq, x_out, n_nodes, update_step);
+        hipLaunchKernelGGL(apply_twist_if_finite_kernel, dim3((n_nodes + 255) / 256), dim3(256), 0, s, update_dq, x_out, n_nodes, update_step);
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;
 }

@@ -435,8 +435,10 @@ size_t dfh_pcg_workspace_bytes(int n_nodes, int iters);
 int dfh_pcg_solve(const int *row_ptr, const int *col, double *vals, const double *rhs, int n_nodes, int iters,
                   double lm_abs, double lm_rel, double *x_out, void *workspace, size_t workspace_bytes, void *stream);
 
-/* dfh_pcg_solve followed by dfh_apply_twist(node_dq, x_out, n_nodes, step) in the same launch where the persistent
- * kernel runs (each row's wave updates its own node): one GN iteration's solve + update. */
+/* dfh_pcg_solve followed by the twist update node_dq[a] <- exp(step * x_out[a]) (x) node_dq[a] (dfh_apply_twist's arithmetic), in
+ * the same launch where the persistent kernel runs: one GN iteration's solve + update.  On BOTH paths the update is all or
+ * nothing: it is applied only if every entry of x_out is finite; a NaN or an infinity anywhere in x_out (a non-finite rhs or
+ * matrix, a timed-out barrier) leaves node_dq bit for bit as it was before the call. */
 int dfh_pcg_solve_update(const int *row_ptr, const int *col, double *vals, const double *rhs, int n_nodes, int iters,
                          double lm_abs, double lm_rel, double *x_out, void *workspace, size_t workspace_bytes, double *node_dq,
                          double step, void *stream);

@@ -348,20 +348,92 @@ def damp_blocks(N, keys, blocks, lm_abs, lm_rel):
     return out
 
 
-def pcg_cg1(N, keys, blocks, Jtr, iters, lm_abs=0.0, lm_rel=0.0):
-    """x after `iters` iterations of the single-reduction preconditioned CG of Chronopoulos & Gear on
-    (A + lm_abs I + lm_rel diag A) x = -J^T r with the block-Jacobi preconditioner -- the recurrence of
-    pcg_cg1_kernel (csrc/dfh_solve.hip): u = M^-1 r, w = A u, gamma = r.u, delta = w.u, beta = gamma/gamma_old,
-    alpha = gamma / (delta - beta gamma / alpha_old), p = u + beta p, s = w + beta s, t = v + beta t (v = M^-1 w),
-    x += alpha p, r -= alpha s, u -= alpha t."""
+def block_jacobi_inverse(D):
+    """inv6 / inv6_row of csrc/dfh_solve.hip for (n, 6, 6) blocks: Cholesky D = L L^T with the kernel's rule for a
+    rank-deficient block -- a pivot d <= 0 becomes 1 (the kernel: d > 0 ? sqrt(d) : 1) -- then L^-T L^-1.  Equal to
+    the inverse on SPD blocks; the identity on an all-zero block; SPD on any PSD block (the preconditioner only has to be SPD).
+    Every sum runs term by term in the kernel's order (and the column scaling is a product with 1 / pivot, as there), so that a
+    pivot which is zero up to rounding falls on the same side of the rule in both."""
+    D = np.asarray(D, dtype=np.float64)
+    n = D.shape[0]
+    L = np.zeros((n, 6, 6))
+    for j in range(6):
+        d = D[:, j, j].copy()
+        for k in range(j):
+            d = d - L[:, j, k] * L[:, j, k]
+        pos = d > 0.0
+        d = np.where(pos, np.sqrt(np.where(pos, d, 1.0)), 1.0)
+        L[:, j, j] = d
+        inv_d = 1.0 / d
+        for i in range(j + 1, 6):
+            v = D[:, i, j].copy()
+            for k in range(j):
+                v = v - L[:, i, k] * L[:, j, k]
+            L[:, i, j] = v * inv_d
+    Li = np.zeros((n, 6, 6))
+    for c in range(6):
+        for i in range(c, 6):
+            v = np.full(n, 1.0 if i == c else 0.0)
+            for k in range(c, i):
+                v = v - L[:, i, k] * Li[:, k, c]
+            Li[:, i, c] = v / L[:, i, i]
+    out = np.zeros((n, 6, 6))
+    for i in range(6):
+        for j in range(6):
+            v = np.zeros(n)
+            for k in range(max(i, j), 6):
+                v = v + Li[:, k, i] * Li[:, k, j]
+            out[:, i, j] = v
+    return out
+
+
+def _damped_system(N, keys, blocks, lm_abs, lm_rel):
+    """(A as BSR, M^-1 as a function) of the damped system: the block-Jacobi inverse of every row's diagonal block
+    (block_jacobi_inverse), the identity where a row has no diagonal block."""
     Bd = damp_blocks(N, keys, blocks, lm_abs, lm_rel)
     A = blocks_to_bsr(N, keys, Bd)
     diag = np.full(N, -1, dtype=np.int64)
     dsel = np.flatnonzero(keys // N == keys % N)
     diag[keys[dsel] // N] = dsel
-    D = np.where((diag >= 0)[:, None, None], Bd[np.maximum(diag, 0)], np.eye(6)[None])
-    Minv = np.linalg.inv(D)
-    M = lambda v: np.einsum('nij,nj->ni', Minv, v.reshape(N, 6)).reshape(-1)
+    Minv = np.tile(np.eye(6), (N, 1, 1))
+    Minv[diag >= 0] = block_jacobi_inverse(Bd[diag[diag >= 0]])
+    return A, lambda v: np.einsum('nij,nj->ni', Minv, v.reshape(N, 6)).reshape(-1)
+
+
+def pcg_textbook(N, keys, blocks, Jtr, iters, lm_abs=0.0, lm_rel=0.0, iterates=None):
+    """x after `iters` iterations of the two-reduction preconditioned CG on the system of pcg_cg1 -- the recurrence of the
+    multi-launch path (pcg_init_kernel / pcg_spmv_kernel / pcg_update_xr_kernel, csrc/dfh_solve.hip): z = M^-1 r, p = z + beta p
+    with beta = rz / rz_old (0 when rz_old == 0), alpha = rz / p.Ap (0 when p.Ap == 0), x += alpha p, r -= alpha A p.
+    iterates: a list that receives x after every iteration (iterates[k - 1] is what `iters = k` returns)."""
+    A, M = _damped_system(N, keys, blocks, lm_abs, lm_rel)
+    x = np.zeros(6 * N)
+    r = -Jtr.reshape(-1).copy()
+    z = M(r)
+    p = np.zeros_like(x)
+    rz, rz_prev = float(r @ z), 0.0
+    for it in range(iters):
+        beta = rz / rz_prev if rz_prev != 0.0 else 0.0
+        p = z + beta * p
+        Ap = A @ p
+        pAp = float(p @ Ap)
+        alpha = rz / pAp if pAp != 0.0 else 0.0
+        x = x + alpha * p
+        if iterates is not None:
+            iterates.append(x.copy())
+        r = r - alpha * Ap
+        z = M(r)
+        rz_prev, rz = rz, float(r @ z)
+    return x
+
+
+def pcg_cg1(N, keys, blocks, Jtr, iters, lm_abs=0.0, lm_rel=0.0, iterates=None):
+    """x after `iters` iterations of the single-reduction preconditioned CG of Chronopoulos & Gear on
+    (A + lm_abs I + lm_rel diag A) x = -J^T r with the block-Jacobi preconditioner -- the recurrence of
+    pcg_cg1_kernel (csrc/dfh_solve.hip): u = M^-1 r, w = A u, gamma = r.u, delta = w.u, beta = gamma/gamma_old,
+    alpha = gamma / (delta - beta gamma / alpha_old), p = u + beta p, s = w + beta s, t = v + beta t (v = M^-1 w),
+    x += alpha p, r -= alpha s, u -= alpha t.  M^-1 is block_jacobi_inverse of the damped diagonal blocks (the kernel's
+    pivot rule for rank-deficient blocks).  iterates: as in pcg_textbook."""
+    A, M = _damped_system(N, keys, blocks, lm_abs, lm_rel)
     x = np.zeros(6 * N)
     r = -Jtr.reshape(-1).copy()
     u = M(r)
@@ -376,6 +448,8 @@ def pcg_cg1(N, keys, blocks, Jtr, iters, lm_abs=0.0, lm_rel=0.0):
         alpha = gamma / denom if denom != 0.0 else 0.0
         p = u + beta * p; s = w + beta * s; t = v + beta * t
         x = x + alpha * p; r = r - alpha * s; u = u - alpha * t
+        if iterates is not None:
+            iterates.append(x.copy())
         if it == iters - 1:
             break
         w = A @ u

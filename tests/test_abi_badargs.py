@@ -183,3 +183,63 @@ def test_pack_upper_refuses_bad_arguments(lib, name):
     _refused(lib, name, fn(PTR, PTR, PTR, PTR, 4, 2, 3, None, None))
     for counts in ((-1, 2, 3), (4, -1, 3), (4, 2, -1)):
         _refused(lib, name, fn(PTR, PTR, PTR, PTR, *counts, PTR, None))
+
+
+# ---- the block-Jacobi PCG: sizes, pointers and the workspace are checked before anything is launched or written -----------------
+def _pcg_buffers(n=4, iters=3):
+    """Host arrays standing in for the device buffers (a refused call dereferences none): a 4-row diagonal system, x_out,
+    node_dq and a workspace of exactly the size the library asks for, each filled with a pattern."""
+    ws_bytes = 8 * (36 * n + 30 * n + 3 * (iters + 2) + 2 * (iters + 1) * ((n + 3) // 4) + 72 * n)
+    b = {
+        "row_ptr": (ctypes.c_int * (n + 1))(*range(n + 1)),
+        "col": (ctypes.c_int * n)(*range(n)),
+        "vals": (ctypes.c_double * (36 * n))(*([2.5] * (36 * n))),
+        "rhs": (ctypes.c_double * (6 * n))(*([1.5] * (6 * n))),
+        "x": (ctypes.c_double * (6 * n))(*([-7.25] * (6 * n))),
+        "ws": (ctypes.c_ubyte * ws_bytes)(*([0xA5] * ws_bytes)),
+        "dq": (ctypes.c_double * (8 * n))(*([0.125] * (8 * n))),
+    }
+    return b, ws_bytes
+
+
+def _pcg_call(lib, update, b, n, iters, ws_bytes, null=None):
+    p = {k: (None if k == null else ctypes.addressof(v)) for k, v in b.items()}
+    args = (p["row_ptr"], p["col"], p["vals"], p["rhs"], n, iters, 1e-3, 1e-2, p["x"], p["ws"], ws_bytes)
+    if update:
+        return lib.dfh_pcg_solve_update(*args, p["dq"], 1.0, None)
+    return lib.dfh_pcg_solve(*args, None)
+
+
+@pytest.mark.parametrize("update", [False, True])
+@on_own_thread
+def test_pcg_solve_refuses_bad_arguments_and_writes_nothing(lib, update):
+    n, iters = 4, 3
+    b, ws_bytes = _pcg_buffers(n, iters)
+    assert lib.dfh_pcg_workspace_bytes(n, iters) == ws_bytes
+    before = {k: bytes(v) for k, v in b.items()}
+    name = "dfh_pcg_solve"                                                  # (dfh_pcg_solve_update reports under both names)
+
+    def refused(rc, what=name):
+        _refused(lib, what, rc)
+        assert {k: bytes(v) for k, v in b.items()} == before                # nothing was written, the matrix's damping included
+
+    refused(_pcg_call(lib, update, b, 0, iters, ws_bytes))                  # no rows
+    refused(_pcg_call(lib, update, b, -3, iters, ws_bytes))
+    refused(_pcg_call(lib, update, b, n, 0, ws_bytes))                      # no iterations
+    refused(_pcg_call(lib, update, b, n, -1, ws_bytes))
+    for null in ("row_ptr", "col", "vals", "rhs", "x", "ws"):
+        refused(_pcg_call(lib, update, b, n, iters, ws_bytes, null=null))
+    if update:
+        refused(_pcg_call(lib, update, b, n, iters, ws_bytes, null="dq"), "dfh_pcg_solve_update")
+    refused(_pcg_call(lib, update, b, n, iters, ws_bytes - 1))              # a workspace one byte short
+    refused(_pcg_call(lib, update, b, n, iters + 1, ws_bytes))              # ... or sized for fewer iterations
+    refused(_pcg_call(lib, update, b, n, iters, 0))
+
+
+@on_own_thread
+def test_pcg_queries_refuse_bad_sizes(lib):
+    _refused(lib, "dfh_pcg_path", lib.dfh_pcg_path(0))
+    _refused(lib, "dfh_pcg_path", lib.dfh_pcg_path(-5))
+    assert lib.dfh_pcg_workspace_bytes(0, 10) == 0 and lib.dfh_pcg_workspace_bytes(-1, 10) == 0 and lib.dfh_pcg_workspace_bytes(4, -1) == 0
+    _refused(lib, "dfh_pcg_set_mode", lib.dfh_pcg_set_mode(1))
+    _refused(lib, "dfh_pcg_set_mode", lib.dfh_pcg_set_mode(3))

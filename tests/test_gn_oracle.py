@@ -212,3 +212,34 @@ def test_block_sparse_assembly_and_truncated_pcg(golden):
     assert x7 @ bd < 0 and np.linalg.norm(Adamp @ x7 + bd) < np.linalg.norm(bd)
     sc, obj = G.huber_scale(np.array([0.1, -2.0, 0.5]), 0.5)
     assert np.allclose(sc ** 2, [1.0, 0.25, 1.0]) and abs(obj - (0.005 + 0.5 * 1.75 + 0.125)) < 1e-15
+
+
+def test_block_jacobi_inverse_is_the_inverse_with_the_kernels_pivot_rule():
+    """block_jacobi_inverse restates inv6 (csrc/dfh_solve.hip): the inverse on SPD blocks, and for blocks without full rank
+    whatever the rule "a pivot <= 0 becomes 1" gives -- where np.linalg.inv fails or returns garbage."""
+    rng = np.random.default_rng(5)
+    B = rng.standard_normal((200, 6, 9))
+    D = np.einsum('nik,njk->nij', B, B) + 1e-3 * np.eye(6)
+    Mi = G.block_jacobi_inverse(D)
+    ref = np.linalg.inv(D)
+    assert np.abs(Mi - ref).max(axis=(1, 2)).max() <= 1e-12 * np.abs(ref).max()
+    assert (np.abs(Mi - ref).max(axis=(1, 2)) <= 1e-12 * np.abs(ref).max(axis=(1, 2)) * np.linalg.cond(D)).all()
+    assert np.array_equal(Mi, np.transpose(Mi, (0, 2, 1)))
+    # well-conditioned blocks: 1e-12 of each block's own scale
+    Dw = D + 5.0 * np.eye(6)
+    Mw, refw = G.block_jacobi_inverse(Dw), np.linalg.inv(Dw)
+    assert (np.abs(Mw - refw).max(axis=(1, 2)) <= 1e-12 * np.abs(refw).max(axis=(1, 2))).all()
+    # a node without samples: every pivot is 0 -> the identity
+    assert np.array_equal(G.block_jacobi_inverse(np.zeros((3, 6, 6))), np.tile(np.eye(6), (3, 1, 1)))
+    # rank 3, exactly: D = L0 L0^T with a unit lower-trapezoidal integer L0 (6 x 3): the factorisation is exact, pivots 4..6 are
+    # exactly 0 and become 1, so the result is (L L^T)^-1 of L = [L0 | unit columns] -- finite, symmetric, positive definite
+    L0 = np.array([[1, 0, 0], [2, 1, 0], [-1, 3, 1], [0, -2, 2], [3, 1, -1], [1, 1, 1]], dtype=np.float64)
+    M3 = G.block_jacobi_inverse((L0 @ L0.T)[None])[0]
+    Lfull = np.eye(6); Lfull[:, :3] = L0
+    assert np.isfinite(M3).all() and np.array_equal(M3, M3.T) and np.linalg.eigvalsh(M3).min() > 0.0
+    assert np.abs(M3 - np.linalg.inv(Lfull @ Lfull.T)).max() <= 1e-12 * np.abs(M3).max()
+    # rank 3 with rounding (pivots 4..6 are +-1e-16: either side of the rule): still finite and symmetric, positive diagonal
+    B3 = rng.standard_normal((50, 6, 3))
+    Mr = G.block_jacobi_inverse(np.einsum('nik,njk->nij', B3, B3))
+    assert np.isfinite(Mr).all() and np.array_equal(Mr, np.transpose(Mr, (0, 2, 1)))
+    assert (Mr[:, np.arange(6), np.arange(6)] > 0.0).all()
