@@ -54,7 +54,7 @@ __device__ __forceinline__ D3 dqb_warp_normal_exact(const double *q, double nx, 
 __device__ __forceinline__ double round_f32(double v) { return (double)(float)v; }
 
 // normalised blend of a sample's k node DQs with its static weights (identity when the blend vanishes); returns |b|_8
-// (1 in the degenerate case).  Shared by the GN kernels of dfh_solve.hip and the volume association (dfh_associate_volume.hip).
+// (1 in the degenerate case).  Shared by the GN kernels of dfh_solve.hip / dfh_gn_global.hip and the volume association (dfh_associate_volume.hip).
 constexpr int kBlendKMax = 8;         // knn <= 8 (idx / w hold kBlendKMax entries)
 __device__ __forceinline__ double blend_static(const double *__restrict__ node_dq, const int *idx, const double *w, int k, double *bh) {
     double b[8] = {0, 0, 0, 0, 0, 0, 0, 0};

@@ -1609,7 +1609,7 @@ static int check_live(const char *what, const dfh_live *l) {
 }
 
 // k nearest nodes + blend weights of arbitrary points through the bricks' candidate lists (what sample_knn_kernel of
-// dfh_solve.hip computes, same expressions, same tie order: candidates are kept in node order and the insertion is
+// dfh_points.hip computes, same expressions, same tie order: candidates are kept in node order and the insertion is
 // stable).  A point outside the slab's lattice, or in a brick whose list overflowed, scans every node.
 template <int KS>
 __global__ __launch_bounds__(256) void sample_knn_bricks_kernel(const double *__restrict__ spos, int S,

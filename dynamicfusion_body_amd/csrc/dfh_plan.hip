@@ -21,7 +21,7 @@ namespace dfh {
 using SortCfg = rocprim::radix_sort_config<rocprim::default_config,
                                            rocprim::merge_sort_config<512, 512, DFH_SORT_BLOCK_ITEMS, 128, 256, 8>,
                                            rocprim::default_config>;
-constexpr int kPlanTile = kGnTile;      // == kTile of dfh_solve.hip: a row never spans two tiles
+constexpr int kPlanTile = kGnTile;      // == kTile of dfh_gn_rows.h: a row never spans two tiles
 constexpr int kPlanWaves = kPlanTile / 64;
 constexpr int kKMaxP = 8;
 

@@ -1,5 +1,5 @@
 """Host side of the warp-field solve: device buffers, the block-sparse pattern of J^T J and the
-Gauss-Newton / Levenberg-Marquardt loop around the HIP kernels of csrc/dfh_solve.hip.
+Gauss-Newton / Levenberg-Marquardt loop around the HIP kernels of csrc/dfh_solve.hip, dfh_pcg.hip and dfh_gn_global.hip.
 
 The reference's solve is scipy.optimize.least_squares on `computef` with finite-difference
 Jacobians (core/fusion.py:327-412); what is kept from it is the residual definition, the

@@ -264,7 +264,7 @@ def associate_depth(points_idx, K, Kinv, lw_cam, dm, scale, center, half):
     cworld = (ccam - t) @ np.linalg.inv(R).T
     cidx = (cworld - center) / scale + half
     # a non-finite correspondence (a depth of -inf: z = inf, z u = inf or NaN) is not a data row -- this project's own rule, the
-    # reference associates mesh to mesh; the device drops such a sample gated or not (csrc/dfh_solve.hip: associate_views)
+    # reference associates mesh to mesh; the device drops such a sample gated or not (csrc/dfh_gn_rows.h: associate_views)
     valid = valid & np.isfinite(cidx).all(axis=1)
     return np.where(valid[:, None], cidx, 0.0), valid
 
@@ -292,7 +292,7 @@ def associate_depth_views(points_idx, K, Kinv, lw_cams, dms, scale, center, half
 
 
 # ---------------------------------------------------------------- block-sparse assembly + truncated PCG
-# (what the HIP build ships: csrc/dfh_solve.hip gn_build_* + pcg_cg1_kernel).  Same algorithm as assemble_dense
+# (what the HIP build ships: csrc/dfh_solve.hip gn_build_* + csrc/dfh_pcg.hip pcg_cg1_kernel).  Same algorithm as assemble_dense
 # + a dense solve, but sized for BASELINE configs 3/4 (512 / 2 048 nodes, 1e5..1e6 samples) and with the SAME
 # truncated linear solve the device runs, so that the benched settings (10 PCG iterations) have a CPU value beside them.
 def _reduce_by_key(keys, vals):
@@ -349,7 +349,7 @@ def damp_blocks(N, keys, blocks, lm_abs, lm_rel):
 
 
 def block_jacobi_inverse(D):
-    """inv6 / inv6_row of csrc/dfh_solve.hip for (n, 6, 6) blocks: Cholesky D = L L^T with the kernel's rule for a
+    """inv6 / inv6_row of csrc/dfh_solve_math.h for (n, 6, 6) blocks: Cholesky D = L L^T with the kernel's rule for a
     rank-deficient block -- a pivot d <= 0 becomes 1 (the kernel: d > 0 ? sqrt(d) : 1) -- then L^-T L^-1.  Equal to
     the inverse on SPD blocks; the identity on an all-zero block; SPD on any PSD block (the preconditioner only has to be SPD).
     Every sum runs term by term in the kernel's order (and the column scaling is a product with 1 / pivot, as there), so that a
@@ -402,7 +402,7 @@ def _damped_system(N, keys, blocks, lm_abs, lm_rel):
 
 def pcg_textbook(N, keys, blocks, Jtr, iters, lm_abs=0.0, lm_rel=0.0, iterates=None):
     """x after `iters` iterations of the two-reduction preconditioned CG on the system of pcg_cg1 -- the recurrence of the
-    multi-launch path (pcg_init_kernel / pcg_spmv_kernel / pcg_update_xr_kernel, csrc/dfh_solve.hip): z = M^-1 r, p = z + beta p
+    multi-launch path (pcg_init_kernel / pcg_spmv_kernel / pcg_update_xr_kernel, csrc/dfh_pcg.hip): z = M^-1 r, p = z + beta p
     with beta = rz / rz_old (0 when rz_old == 0), alpha = rz / p.Ap (0 when p.Ap == 0), x += alpha p, r -= alpha A p.
     iterates: a list that receives x after every iteration (iterates[k - 1] is what `iters = k` returns)."""
     A, M = _damped_system(N, keys, blocks, lm_abs, lm_rel)
@@ -429,7 +429,7 @@ def pcg_textbook(N, keys, blocks, Jtr, iters, lm_abs=0.0, lm_rel=0.0, iterates=N
 def pcg_cg1(N, keys, blocks, Jtr, iters, lm_abs=0.0, lm_rel=0.0, iterates=None):
     """x after `iters` iterations of the single-reduction preconditioned CG of Chronopoulos & Gear on
     (A + lm_abs I + lm_rel diag A) x = -J^T r with the block-Jacobi preconditioner -- the recurrence of
-    pcg_cg1_kernel (csrc/dfh_solve.hip): u = M^-1 r, w = A u, gamma = r.u, delta = w.u, beta = gamma/gamma_old,
+    pcg_cg1_kernel (csrc/dfh_pcg.hip): u = M^-1 r, w = A u, gamma = r.u, delta = w.u, beta = gamma/gamma_old,
     alpha = gamma / (delta - beta gamma / alpha_old), p = u + beta p, s = w + beta s, t = v + beta t (v = M^-1 w),
     x += alpha p, r -= alpha s, u -= alpha t.  M^-1 is block_jacobi_inverse of the damped diagonal blocks (the kernel's
     pivot rule for rank-deficient blocks).  iterates: as in pcg_textbook."""
@@ -460,7 +460,7 @@ def pcg_cg1(N, keys, blocks, Jtr, iters, lm_abs=0.0, lm_rel=0.0, iterates=None):
 
 
 def global_step(dqs, blocks, Jtr, lm_rel):
-    """The rigid mode of the normal equations solved on its own (dfh_gn_global_step, csrc/dfh_solve.hip): all nodes share ONE
+    """The rigid mode of the normal equations solved on its own (dfh_gn_global_step, csrc/dfh_gn_global.hip): all nodes share ONE
     twist xi -- (sum of all 6x6 blocks, symmetrised, + lm_rel diag) xi = -(sum of all J^T r) -- applied to every node.
     Returns (new dqs, xi)."""
     A = blocks.sum(axis=0)

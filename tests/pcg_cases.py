@@ -194,7 +194,7 @@ def workgroups(N, wpb):
 
 
 def auto_wpb(N, n_cu):
-    """pcg_shape's choice (csrc/dfh_solve.hip): 8 waves while the grid fits one workgroup per CU, 16 beyond."""
+    """pcg_shape's choice (csrc/dfh_pcg.hip): 8 waves while the grid fits one workgroup per CU, 16 beyond."""
     return 8 if (N + 7) // 8 <= n_cu else 16
 
 

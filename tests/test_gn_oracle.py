@@ -215,7 +215,7 @@ def test_block_sparse_assembly_and_truncated_pcg(golden):
 
 
 def test_block_jacobi_inverse_is_the_inverse_with_the_kernels_pivot_rule():
-    """block_jacobi_inverse restates inv6 (csrc/dfh_solve.hip): the inverse on SPD blocks, and for blocks without full rank
+    """block_jacobi_inverse restates inv6 (csrc/dfh_solve_math.h): the inverse on SPD blocks, and for blocks without full rank
     whatever the rule "a pivot <= 0 becomes 1" gives -- where np.linalg.inv fails or returns garbage."""
     rng = np.random.default_rng(5)
     B = rng.standard_normal((200, 6, 9))

@@ -310,7 +310,7 @@ def test_multi_view_association_and_gn_loop_vs_oracle():
 
 def test_view_culling_per_tile_changes_nothing():
     """Config 5's data term: eight orbit views, 45 degrees apart.  The fused build drops, per 128-sample tile, the views none
-    of the tile's samples can be valid in (csrc/dfh_solve.hip: tile_view_mask -- the tile's box projects outside the image, or
+    of the tile's samples can be valid in (csrc/dfh_gn_rows.h: tile_view_mask -- the tile's box projects outside the image, or
     onto pixels whose valid depths lie further than the gate from the box's depth range) before projecting a sample into them.
     Asserted: corr / valid, the normal equations and the cost are bit for bit those of the build that tries every view
     (option gn_no_view_cull) and corr / valid those of the stand-alone association kernel; five of the eight views win somewhere (the three behind the back wall see the wall, not the sphere)."""

@@ -1,4 +1,4 @@
-"""GPU parity of the warp-field solve (csrc/dfh_solve.hip through the C ABI).
+"""GPU parity of the warp-field solve (csrc/dfh_points.hip, dfh_solve.hip, dfh_pcg.hip and dfh_gn_global.hip through the C ABI).
 
   * residual evaluators vs the REFERENCE's outputs (golden g5): <= 1e-12 (fp64, same operations;
     exp() of the blend weights is the only last-ulp difference);
