@@ -83,6 +83,7 @@ _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
 _volume_p = ctypes.POINTER(Volume)
+_term_p = ctypes.POINTER(VolumeTerm)
 STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams, "dfh_slab": Slab,
            "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes,
            "dfh_gn_volume_term": VolumeTerm}
@@ -120,9 +121,11 @@ _SIGNATURES = {
     "dfh_gn_views_bytes": (ctypes.c_size_t, [_int, _int, _int, _int]),
     "dfh_gn_pack_views": (_int, [_vp, _int, ctypes.POINTER(ctypes.c_void_p), _int, _int, _int, _c_double_p, _vp]),
     "dfh_gn_associate": (_int, [_problem_p, _frame_p, _vp]),
-    "dfh_gn_associate_volume": (_int, [_problem_p, ctypes.POINTER(VolumeTerm), _vp]),
+    "dfh_gn_associate_volume": (_int, [_problem_p, _term_p, _vp]),
     "dfh_gn_build": (_int, [_problem_p, _frame_p, _vp]),
+    "dfh_gn_build_volume": (_int, [_problem_p, _term_p, _vp]),
     "dfh_gn_solve": (_int, [_problem_p, _frame_p, ctypes.POINTER(SolveParams), _vp]),
+    "dfh_gn_solve_volume": (_int, [_problem_p, _term_p, ctypes.POINTER(SolveParams), _vp]),
     "dfh_gn_pack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "dfh_gn_unpack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "dfh_gn_sort_workspace_bytes": (ctypes.c_size_t, [_int]),
@@ -143,6 +146,7 @@ _SIGNATURES = {
     "dfh_relax_twists": (_int, [_vp, _int, _dbl, _vp]),
     "dfh_gn_global_sampled_bytes": (ctypes.c_size_t, [_int, _int]),
     "dfh_gn_global_sampled": (_int, [_problem_p, _frame_p, _int, _dbl, _int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dfh_gn_global_sampled_volume": (_int, [_problem_p, _term_p, _int, _dbl, _int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dfh_gn_global_apply": (_int, [_vp, _dbl, _int, _vp, _vp, _vp]),
     "dfh_gn_global_step_bytes": (ctypes.c_size_t, []),
     "dfh_gn_global_step": (_int, [_vp, _int, _vp, _int, _dbl, _vp, _vp, _vp, ctypes.c_size_t, _vp]),

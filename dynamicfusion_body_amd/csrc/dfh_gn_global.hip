@@ -3,9 +3,11 @@
 // (dfh_gn_global_sampled; its rows are associated and differentiated by dfh_gn_rows.h exactly as in the build), the twist
 // decay between frames (dfh_relax_twists), and the packing of the symmetric system for the exchange between ranks.
 // Restated in oracle/gn_np.py (global_step, global_step_sampled, relax_twists).
+#include "dfh_assoc_volume.h"
 #include "dfh_gn_rows.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace dfh {
 
@@ -115,11 +117,14 @@ constexpr int kGlobalGrid = 1536;                   // workgroups of the rows ke
 // accumulates X^T X with v_mfma_f64_16x16x4 (16 steps of four samples per tile; A_g and g_g are its entries (i <= j < 6) and
 // (i, 6)); the accumulator is four doubles per lane where 27 running sums per thread made the kernel a 256-VGPR one: one wave
 // per SIMD, a tile's whole chain of dependent loads exposed -- 65 us for config 3's 762 tiles, 131 us for config 5's 5.2 k.
-template <int K, typename DepthT>
+// VOLUME: the samples are associated against a live TSDF volume of DepthT (one trilinear cell, dfh_assoc_volume.h) instead of
+// the frame's views; the kernel's last argument is what its association reads.
+template <int K, typename DepthT, bool VOLUME = false>
 __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(3, 8))) void gn_global_rows_kernel(const double *__restrict__ spos, const double *__restrict__ snrm,
                                                               const int *__restrict__ nbr, const double *__restrict__ wts,
                                                               const double *__restrict__ node_dq, const BuildParams p, int stride, long n_sub,
-                                                              double *__restrict__ tile_part, const AssocArgs aa) {
+                                                              double *__restrict__ tile_part,
+                                                              const std::conditional_t<VOLUME, VolAssocArgs, AssocArgs> aa) {
     __shared__ double sPart[kTileWaves][kGlobalVals];
     __shared__ double sX[kTile * 8];
     typedef double d4 __attribute__((ext_vector_type(4)));
@@ -146,7 +151,9 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(3, 8))) v
             const D3 x1 = dqb_warp_exact(bh, pfx, pfy, pfz);
             const D3 xp = dqb_warp_exact(p.lw.q, round_f32(x1.x), round_f32(x1.y), round_f32(x1.z));
             double c[3];
-            const bool ok = associate_views<DepthT>(aa.ap, aa.views, aa.n_views, xp, c);
+            bool ok;                                                              // (a lane with s >= S is not here: it touches no map, no volume)
+            if constexpr (VOLUME) ok = associate_volume_cell<DepthT>(static_cast<const DepthT *>(aa.live), aa.vp, xp, c);
+            else ok = associate_views<DepthT>(aa.ap, aa.views, aa.n_views, xp, c);
             if (ok) {
                 double Jrow[6 * K];
                 double r = data_row_from(node_dq, idx, w, K, p.lw.q, bh, nb, pfx, pfy, pfz, xp, snrm[3 * (size_t)s], snrm[3 * (size_t)s + 1],
@@ -357,20 +364,16 @@ int dfh_gn_global_apply(const double *sums29, double lm_rel, int n_nodes, double
     return DFH_OK;
 }
 
-int dfh_gn_global_sampled(const dfh_gn_problem *problem, const dfh_gn_frame *frame, int stride, double lm_rel, int n_steps,
-                          double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream) {
+// The body of dfh_gn_global_sampled / dfh_gn_global_sampled_volume.  views / vol: the association's arguments (one of them),
+// f64: the maps' / the volume's type.  The problem and the frame or term are checked by the caller.
+static int gn_global_sampled_impl(const char *what, const dfh_gn_problem &q, const dfh::AssocArgs *views, const dfh::VolAssocArgs *vol, bool f64,
+                                  int stride, double lm_rel, int n_steps, double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes,
+                                  void *stream) {
     using namespace dfh;
-    DFH_REQUIRE(n_steps >= 0 && n_steps <= 100 && stride >= 1, "dfh_gn_global_sampled: %d steps, stride %d", n_steps, stride);
-    if (n_steps == 0) return DFH_OK;
-    int rc = check_problem("dfh_gn_global_sampled", problem, false);
-    if (rc == DFH_OK) rc = check_frame("dfh_gn_global_sampled", frame, false);
-    if (rc != DFH_OK) return rc;
-    const dfh_gn_problem &q = *problem;
     const int n_samples = q.n_samples, knn = q.knn, n_nodes = q.n_nodes;
-    DFH_REQUIRE(scratch && lm_rel >= 0.0, "dfh_gn_global_sampled: bad arguments");
-    DFH_REQUIRE(scratch_bytes >= dfh_gn_global_sampled_bytes(n_samples, stride), "dfh_gn_global_sampled: scratch too small");
-    DFH_REQUIRE(!sums_out || n_steps == 1, "dfh_gn_global_sampled: sums_out (the caller reduces over ranks and applies) takes one step per call");
-    const AssocArgs aa = assoc_args(q, *frame, false);
+    DFH_REQUIRE(scratch && lm_rel >= 0.0, "%s: bad arguments", what);
+    DFH_REQUIRE(scratch_bytes >= dfh_gn_global_sampled_bytes(n_samples, stride), "%s: scratch too small", what);
+    DFH_REQUIRE(!sums_out || n_steps == 1, "%s: sums_out (the caller reduces over ranks and applies) takes one step per call", what);
     BuildParams bp;
     for (int i = 0; i < 8; ++i) bp.lw.q[i] = q.lw_dq[i];
     bp.S = n_samples; bp.k = knn; bp.N = n_nodes; bp.huber = q.huber_delta;
@@ -380,29 +383,59 @@ int dfh_gn_global_sampled(const dfh_gn_problem *problem, const dfh_gn_frame *fra
     double *tile_part = static_cast<double *>(scratch);
     double *sums = sums_out ? sums_out : tile_part + (size_t)kGlobalVals * kGlobalGrid;
     hipStream_t st = (hipStream_t)stream;
-    const bool f64 = frame->depth_dtype == DFH_F64;
     for (int g = 0; g < n_steps; ++g) {
         if (n_wg > 0) {
+#define DFH_GLOBAL_ROWS_T(KK, T)                                                                                                   \
+    if (vol)                                                                                                                       \
+        hipLaunchKernelGGL((gn_global_rows_kernel<KK, T, true>), dim3((unsigned)n_wg), dim3(kTile), 0, st, q.sample_pos, q.sample_nrm,  \
+                           q.nbr, q.weights, (const double *)q.node_dq, bp, stride, n_sub, tile_part, *vol);                         \
+    else                                                                                                                           \
+        hipLaunchKernelGGL((gn_global_rows_kernel<KK, T>), dim3((unsigned)n_wg), dim3(kTile), 0, st, q.sample_pos, q.sample_nrm,        \
+                           q.nbr, q.weights, (const double *)q.node_dq, bp, stride, n_sub, tile_part, *views)
 #define DFH_GLOBAL_ROWS(KK)                                                                                                        \
     case KK:                                                                                                                       \
-        if (f64)                                                                                                                   \
-            hipLaunchKernelGGL((gn_global_rows_kernel<KK, double>), dim3((unsigned)n_wg), dim3(kTile), 0, st, q.sample_pos, q.sample_nrm, \
-                               q.nbr, q.weights, (const double *)q.node_dq, bp, stride, n_sub, tile_part, aa);                            \
-        else                                                                                                                       \
-            hipLaunchKernelGGL((gn_global_rows_kernel<KK, float>), dim3((unsigned)n_wg), dim3(kTile), 0, st, q.sample_pos, q.sample_nrm, \
-                               q.nbr, q.weights, (const double *)q.node_dq, bp, stride, n_sub, tile_part, aa);                            \
+        if (f64) { DFH_GLOBAL_ROWS_T(KK, double); } else { DFH_GLOBAL_ROWS_T(KK, float); }                                         \
         break
             switch (knn) {
                 DFH_GLOBAL_ROWS(1); DFH_GLOBAL_ROWS(2); DFH_GLOBAL_ROWS(3); DFH_GLOBAL_ROWS(4);
                 DFH_GLOBAL_ROWS(5); DFH_GLOBAL_ROWS(6); DFH_GLOBAL_ROWS(7); DFH_GLOBAL_ROWS(8);
             }
 #undef DFH_GLOBAL_ROWS
+#undef DFH_GLOBAL_ROWS_T
         }
         if (sums_out) hipLaunchKernelGGL(gn_global_finish_kernel<false>, dim3(1), dim3(1024), 0, st, (const double *)tile_part, n_wg, sums, lm_rel, n_nodes, q.node_dq, xi_out);
         else hipLaunchKernelGGL(gn_global_finish_kernel<true>, dim3(1), dim3(1024), 0, st, (const double *)tile_part, n_wg, sums, lm_rel, n_nodes, q.node_dq, xi_out);
     }
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;
+}
+
+int dfh_gn_global_sampled(const dfh_gn_problem *problem, const dfh_gn_frame *frame, int stride, double lm_rel, int n_steps,
+                          double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream) {
+    using namespace dfh;
+    const char *what = "dfh_gn_global_sampled";
+    DFH_REQUIRE(n_steps >= 0 && n_steps <= 100 && stride >= 1, "%s: %d steps, stride %d", what, n_steps, stride);
+    if (n_steps == 0) return DFH_OK;
+    int rc = check_problem(what, problem, false);
+    if (rc == DFH_OK) rc = check_frame(what, frame, false);
+    if (rc != DFH_OK) return rc;
+    const AssocArgs aa = assoc_args(*problem, *frame, false);
+    return gn_global_sampled_impl(what, *problem, &aa, nullptr, frame->depth_dtype == DFH_F64, stride, lm_rel, n_steps, xi_out, sums_out,
+                                  scratch, scratch_bytes, stream);
+}
+
+int dfh_gn_global_sampled_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, int stride, double lm_rel, int n_steps,
+                                 double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream) {
+    using namespace dfh;
+    const char *what = "dfh_gn_global_sampled_volume";
+    DFH_REQUIRE(n_steps >= 0 && n_steps <= 100 && stride >= 1, "%s: %d steps, stride %d", what, n_steps, stride);
+    if (n_steps == 0) return DFH_OK;
+    int rc = check_problem(what, problem, false);
+    if (rc == DFH_OK) rc = check_volume_term(what, term, false);
+    if (rc != DFH_OK) return rc;
+    const VolAssocArgs va = vol_assoc_args(*problem, *term);
+    return gn_global_sampled_impl(what, *problem, nullptr, &va, term->live.dtype == DFH_F64, stride, lm_rel, n_steps, xi_out, sums_out,
+                                  scratch, scratch_bytes, stream);
 }
 
 int dfh_relax_twists(double *node_dq, int n_nodes, double factor, void *stream) {

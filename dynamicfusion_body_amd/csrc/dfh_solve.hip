@@ -10,6 +10,7 @@
 //
 // Everything is fp64: per GN iteration the work is ~1 kflop/sample over ~1e5..1e6 samples, far from any roofline that
 // would justify fp32, and fp64 keeps the residual bit-comparable with the CPU path.
+#include "dfh_assoc_volume.h"
 #include "dfh_gn_rows.h"
 #include "dfh_pcg.h"
 
@@ -75,10 +76,16 @@ __device__ void gn_reg_pairs(int block, const int *__restrict__ node_nbr, int N,
                              const int *__restrict__ row_ptr, const int *__restrict__ col, double *__restrict__ vals,
                              double *__restrict__ rhs, double *__restrict__ cost_count, double *__restrict__ partial_reg);
 
-// ASSOC: the projective association (associate_kernel's arithmetic, same bits) runs inside this kernel -- every sample of the
-// tile is warped once, associated against the frame's views, its correspondence and validity are written to corr / valid (for the
-// callers that read them) and the valid ones go straight on to their Jacobian rows: one launch and one blend + warp per
-// sample less per GN iteration.
+// MODE != AssocMode::None: the association runs inside this kernel -- every sample of the tile is warped once, associated, its
+// correspondence and validity are written to corr / valid (for the callers that read them) and the valid ones go straight on to
+// their Jacobian rows: one launch and one blend + warp per sample less per GN iteration.  Views: the projective association
+// against the frame's views (associate_kernel's arithmetic, same bits).  Volume: one trilinear cell of a live TSDF volume
+// (associate_volume_kernel's arithmetic, same bits: dfh_assoc_volume.h) -- no views, so no tile box and no view mask.
+// The kernel's last argument is what its mode reads: the views' arguments (also for None, which reads nothing: its kernarg
+// segment is what it was), or the volume's.
+enum class AssocMode { None, Views, Volume };
+template <AssocMode MODE> struct AssocArgsOf { typedef AssocArgs type; };
+template <> struct AssocArgsOf<AssocMode::Volume> { typedef VolAssocArgs type; };
 #ifdef DFH_BUILD_TRACE   // experiment builds only: wall-clock stamps of every tile's phases
 __device__ unsigned long long g_build_trace[8192][8];
 #define BT_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_build_trace[blockIdx.x][k] = wall_clock64(); } while (0)
@@ -86,7 +93,7 @@ __device__ unsigned long long g_build_trace[8192][8];
 #define BT_STAMP(k) do {} while (0)
 #endif
 
-template <int K, bool PLANNED, bool ASSOC>
+template <int K, bool PLANNED, AssocMode MODE>
 __global__ __launch_bounds__(kTile) void gn_build_data_kernel(const double *__restrict__ spos, const double *__restrict__ snrm,
                                                              const int *__restrict__ nbr, const double *__restrict__ wts,
                                                              double *__restrict__ corr,
@@ -96,7 +103,8 @@ __global__ __launch_bounds__(kTile) void gn_build_data_kernel(const double *__re
                                                              double *__restrict__ vals, double *__restrict__ rhs,
                                                              double *__restrict__ cost_count, const int *__restrict__ run_id,
                                                              double *__restrict__ partial, double *__restrict__ tile_cost,
-                                                             const RegTail rt, const AssocArgs aa) {
+                                                             const RegTail rt, const typename AssocArgsOf<MODE>::type aa) {
+    constexpr bool ASSOC = MODE != AssocMode::None;
     if (PLANNED && rt.zero_ptr && (int)blockIdx.x >= rt.first_zero_wg) {     // (workgroup-uniform) clearing that rides along
         const unsigned long long i0 = (unsigned long long)((int)blockIdx.x - rt.first_zero_wg) * kZeroPerWg + 4ull * threadIdx.x;
 #pragma unroll
@@ -142,34 +150,39 @@ __global__ __launch_bounds__(kTile) void gn_build_data_kernel(const double *__re
         const D3 x1 = dqb_warp_exact(a_bh, a_pf[0], a_pf[1], a_pf[2]);
         a_xp = dqb_warp_exact(p.lw.q, round_f32(x1.x), round_f32(x1.y), round_f32(x1.z));
     }
-    unsigned view_mask = ~0u;
-    if (ASSOC && aa.views && aa.cull) {                                        // (workgroup-uniform)
-        // the tile's warped samples' box -> the views any of them can be valid in
-        __shared__ double sBox[kTileWaves][6];
-        __shared__ unsigned sMask;
-        const bool in = tid < tile_n;
-        double bx[6] = {in ? a_xp.x : __builtin_huge_val(), in ? -a_xp.x : __builtin_huge_val(), in ? a_xp.y : __builtin_huge_val(),
-                        in ? -a_xp.y : __builtin_huge_val(), in ? a_xp.z : __builtin_huge_val(), in ? -a_xp.z : __builtin_huge_val()};
+    if constexpr (MODE == AssocMode::Views) {
+        unsigned view_mask = ~0u;
+        if (aa.views && aa.cull) {                                            // (workgroup-uniform)
+            // the tile's warped samples' box -> the views any of them can be valid in
+            __shared__ double sBox[kTileWaves][6];
+            __shared__ unsigned sMask;
+            const bool in = tid < tile_n;
+            double bx[6] = {in ? a_xp.x : __builtin_huge_val(), in ? -a_xp.x : __builtin_huge_val(), in ? a_xp.y : __builtin_huge_val(),
+                            in ? -a_xp.y : __builtin_huge_val(), in ? a_xp.z : __builtin_huge_val(), in ? -a_xp.z : __builtin_huge_val()};
 #pragma unroll
-        for (int o = 32; o > 0; o >>= 1)
+            for (int o = 32; o > 0; o >>= 1)
 #pragma unroll
-            for (int c6 = 0; c6 < 6; ++c6) bx[c6] = fmin(bx[c6], __shfl_xor(bx[c6], o, 64));
-        if ((tid & 63) == 0)
+                for (int c6 = 0; c6 < 6; ++c6) bx[c6] = fmin(bx[c6], __shfl_xor(bx[c6], o, 64));
+            if ((tid & 63) == 0)
 #pragma unroll
-            for (int c6 = 0; c6 < 6; ++c6) sBox[tid >> 6][c6] = bx[c6];
-        __syncthreads();
-        double box[6];
+                for (int c6 = 0; c6 < 6; ++c6) sBox[tid >> 6][c6] = bx[c6];
+            __syncthreads();
+            double box[6];
 #pragma unroll
-        for (int c6 = 0; c6 < 6; ++c6) {
-            double m = sBox[0][c6];
+            for (int c6 = 0; c6 < 6; ++c6) {
+                double m = sBox[0][c6];
 #pragma unroll
-            for (int w_ = 1; w_ < kTileWaves; ++w_) m = fmin(m, sBox[w_][c6]);
-            box[c6] = (c6 & 1) ? -m : m;                                       // (maxima were carried negated)
+                for (int w_ = 1; w_ < kTileWaves; ++w_) m = fmin(m, sBox[w_][c6]);
+                box[c6] = (c6 & 1) ? -m : m;                                       // (maxima were carried negated)
+            }
+            view_mask = tile_view_mask(aa.ap, aa.views, aa.n_views, box, &sMask);
         }
-        view_mask = tile_view_mask(aa.ap, aa.views, aa.n_views, box, &sMask);
+        if (tid < tile_n)
+            a_ok = associate_views<float>(aa.ap, aa.views, aa.n_views, a_xp, a_c, view_mask);
+    } else if constexpr (MODE == AssocMode::Volume) {
+        // (lanes beyond the ragged last tile hold no sample: they issue no live-volume load)
+        if (tid < tile_n) a_ok = associate_volume_cell<float>(static_cast<const float *>(aa.live), aa.vp, a_xp, a_c);
     }
-    if (ASSOC && tid < tile_n)
-        a_ok = associate_views<float>(aa.ap, aa.views, aa.n_views, a_xp, a_c, view_mask);
     // corr / valid are outputs only: stored after the last global load of the kernel (stored here, every later s_waitcnt for a
     // load also waited for these stores' acknowledgements)
     auto store_assoc = [&]() {
@@ -1000,11 +1013,19 @@ int dfh_gn_pack_views(void *out, int n_views, const void *const *depth, int dept
     return DFH_OK;
 }
 
-// assoc: the association fused into the data-row kernel (the caller checked that there is a plan); zero_ptr / zero_count:
-// doubles the launch's last workgroups clear (*zeroed says whether they did).  The problem is checked by the caller.
-static int gn_build_impl(const dfh_gn_problem &q, const dfh::AssocArgs *assoc, void *stream, double *zero_ptr = nullptr,
+// The association fused into the data-row kernel (the caller checked that there is a plan): against the frame's views, against
+// a live volume, or (both null) none.
+struct BuildAssoc {
+    const dfh::AssocArgs *views;
+    const dfh::VolAssocArgs *vol;
+};
+
+// zero_ptr / zero_count: doubles the launch's last workgroups clear (*zeroed says whether they did).  The problem is checked
+// by the caller.
+static int gn_build_impl(const dfh_gn_problem &q, const BuildAssoc &ba, void *stream, double *zero_ptr = nullptr,
                          size_t zero_count = 0, bool *zeroed = nullptr) {
     using namespace dfh;
+    const AssocArgs *assoc = ba.views;
     if (zeroed) *zeroed = false;
     const int knn = q.knn, n_samples = q.n_samples, n_nodes = q.n_nodes, n_blocks = q.n_blocks, n_rows = q.n_rows;
     double *vals = q.vals, *rhs = q.rhs, *cost_count = q.cost_count, *partial = q.partial, *partial_reg = q.partial_reg;
@@ -1046,14 +1067,17 @@ static int gn_build_impl(const dfh_gn_problem &q, const dfh::AssocArgs *assoc, v
         const AssocArgs aa = assoc ? *assoc : AssocArgs{};
 #define DFH_BUILD(KK)                                                                                               \
     case KK:                                                                                                        \
-        if (assoc)                                                                                                  \
-            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, true>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
+        if (ba.vol)                                                                                                 \
+            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, AssocMode::Volume>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
+                               q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, *ba.vol); \
+        else if (assoc)                                                                                             \
+            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, AssocMode::Views>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
                                q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, aa); \
         else if (planned)                                                                                           \
-            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, false>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
+            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, AssocMode::None>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
                                q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, aa); \
         else                                                                                                        \
-            hipLaunchKernelGGL((gn_build_data_kernel<KK, false, false>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
+            hipLaunchKernelGGL((gn_build_data_kernel<KK, false, AssocMode::None>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
                                q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, aa); \
         break
         switch (knn) {
@@ -1107,10 +1131,28 @@ int dfh_gn_build(const dfh_gn_problem *problem, const dfh_gn_frame *frame, void 
     int rc = check_problem("dfh_gn_build", problem, true);
     if (rc == DFH_OK && frame) rc = check_frame("dfh_gn_build", frame, true);
     if (rc != DFH_OK) return rc;
-    if (!frame) return gn_build_impl(*problem, nullptr, stream);
+    if (!frame) return gn_build_impl(*problem, BuildAssoc{nullptr, nullptr}, stream);
     DFH_REQUIRE(problem->blk_ptr, "dfh_gn_build: association inside the build needs a plan");
     const AssocArgs aa = assoc_args(*problem, *frame, true);
-    return gn_build_impl(*problem, &aa, stream);
+    return gn_build_impl(*problem, BuildAssoc{&aa, nullptr}, stream);
+}
+
+// the checks the fused volume entry points share; *va <- the data-row kernel's arguments
+static int check_fused_volume(const char *what, const dfh_gn_problem *problem, const dfh_gn_volume_term *term, dfh::VolAssocArgs *va) {
+    using namespace dfh;
+    int rc = check_problem(what, problem, true);
+    if (rc == DFH_OK) rc = check_volume_term(what, term, true);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(problem->blk_ptr, "%s: null blk_ptr (the fused association needs a plan)", what);
+    *va = vol_assoc_args(*problem, *term);
+    return DFH_OK;
+}
+
+int dfh_gn_build_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, void *stream) {
+    dfh::VolAssocArgs va;
+    const int rc = check_fused_volume("dfh_gn_build_volume", problem, term, &va);
+    if (rc != DFH_OK) return rc;
+    return gn_build_impl(*problem, BuildAssoc{nullptr, &va}, stream);
 }
 
 size_t dfh_gn_partial_doubles(int knn) {
@@ -1130,22 +1172,18 @@ int dfh_debug_gather_trace(unsigned long long *out) {
 }
 #endif
 
-int dfh_gn_solve(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_solve_params *params, void *stream) {
+// The body of dfh_gn_solve / dfh_gn_solve_volume: the problem, its plan and the association's arguments are checked by the caller.
+static int gn_solve_impl(const char *what, const dfh_gn_problem &q, const BuildAssoc &ba, const dfh_gn_solve_params *params, void *stream) {
     using namespace dfh;
-    int rc = check_problem("dfh_gn_solve", problem, true);
-    if (rc == DFH_OK) rc = check_frame("dfh_gn_solve", frame, true);
-    if (rc != DFH_OK) return rc;
-    const dfh_gn_problem &q = *problem;
-    DFH_REQUIRE(q.blk_ptr, "dfh_gn_solve: null blk_ptr (the fused association needs a plan)");
-    DFH_REQUIRE(params, "dfh_gn_solve: null params");
+    DFH_REQUIRE(params, "%s: null params", what);
     const dfh_gn_solve_params &sp = *params;
-    DFH_REQUIRE(sp.n_iters >= 0 && sp.n_iters <= 1000, "dfh_gn_solve: %d iterations", sp.n_iters);
-    DFH_REQUIRE(sp.n_global >= 0 && sp.n_global <= 100, "dfh_gn_solve: %d rigid-mode steps", sp.n_global);
-    DFH_REQUIRE(sp.pcg_iters >= 1 && sp.x_out && sp.pcg_workspace, "dfh_gn_solve: bad solve arguments");
-    DFH_REQUIRE(sp.pcg_workspace_bytes >= dfh_pcg_workspace_bytes(q.n_nodes, sp.pcg_iters), "dfh_gn_solve: solve workspace too small");
-    const AssocArgs aa = assoc_args(q, *frame, true);
+    DFH_REQUIRE(sp.n_iters >= 0 && sp.n_iters <= 1000, "%s: %d iterations", what, sp.n_iters);
+    DFH_REQUIRE(sp.n_global >= 0 && sp.n_global <= 100, "%s: %d rigid-mode steps", what, sp.n_global);
+    DFH_REQUIRE(sp.pcg_iters >= 1 && sp.x_out && sp.pcg_workspace, "%s: bad solve arguments", what);
+    DFH_REQUIRE(sp.pcg_workspace_bytes >= dfh_pcg_workspace_bytes(q.n_nodes, sp.pcg_iters), "%s: solve workspace too small", what);
+    int rc;
     for (int g = 0; g < sp.n_global; ++g) {
-        rc = gn_build_impl(q, &aa, stream);
+        rc = gn_build_impl(q, ba, stream);
         if (rc != DFH_OK) return rc;
         rc = dfh_gn_global_step(q.vals, q.n_blocks, q.rhs, q.n_nodes, sp.global_lm, q.node_dq, sp.global_xi_out, sp.global_scratch,
                                 sp.global_scratch_bytes, stream);
@@ -1157,13 +1195,30 @@ int dfh_gn_solve(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const
     pcg_zero_range(sp.pcg_workspace, q.n_nodes, sp.pcg_iters, &zbegin, &zcount);
     for (int it = 0; it < sp.n_iters; ++it) {
         bool zeroed = false;
-        rc = gn_build_impl(q, &aa, stream, on(opt().gn_iter_own_clear) ? nullptr : zbegin, zcount, &zeroed);
+        rc = gn_build_impl(q, ba, stream, on(opt().gn_iter_own_clear) ? nullptr : zbegin, zcount, &zeroed);
         if (rc != DFH_OK) return rc;
         rc = pcg_solve_impl(q.row_ptr, q.col, q.vals, q.rhs, q.n_nodes, sp.pcg_iters, sp.lm_abs, sp.lm_rel, sp.x_out, sp.pcg_workspace,
                             sp.pcg_workspace_bytes, q.node_dq, sp.step, stream, zeroed);
         if (rc != DFH_OK) return rc;
     }
     return DFH_OK;
+}
+
+int dfh_gn_solve(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_solve_params *params, void *stream) {
+    using namespace dfh;
+    int rc = check_problem("dfh_gn_solve", problem, true);
+    if (rc == DFH_OK) rc = check_frame("dfh_gn_solve", frame, true);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(problem->blk_ptr, "dfh_gn_solve: null blk_ptr (the fused association needs a plan)");
+    const AssocArgs aa = assoc_args(*problem, *frame, true);
+    return gn_solve_impl("dfh_gn_solve", *problem, BuildAssoc{&aa, nullptr}, params, stream);
+}
+
+int dfh_gn_solve_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, const dfh_gn_solve_params *params, void *stream) {
+    dfh::VolAssocArgs va;
+    const int rc = check_fused_volume("dfh_gn_solve_volume", problem, term, &va);
+    if (rc != DFH_OK) return rc;
+    return gn_solve_impl("dfh_gn_solve_volume", *problem, BuildAssoc{nullptr, &va}, params, stream);
 }
 
 }  // extern "C"

@@ -115,15 +115,22 @@ class FrameSolver:
 
     def gn_iteration_volume(self, live, band, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.0, n_iters=1, min_grad=0.5,
                             value_to_vox=1.0):
-        """gn_iteration with the volume data term: associate against the live TSDF volume (WarpSolver.associate_volume) -> build
-        (+ all-reduce) -> PCG -> twist update, n_iters times; asynchronous."""
+        """gn_iteration with the volume data term: associate against the live TSDF volume inside the build
+        (WarpSolver.build_volume; + all-reduce) -> PCG -> twist update, n_iters times, in one library call on one GPU
+        (WarpSolver.iterate_volume); asynchronous."""
         self.solver.iterate_volume(live, self.lw, rw, band, max_dist, huber, lm_abs, lm_rel, n_iters=n_iters, n_global=0,
                                    min_grad=min_grad, value_to_vox=value_to_vox)
 
-    def global_iteration_volume(self, live, band, rw=5.0, max_dist=2.0, huber=0.0, lm_rel=0.1, n_iters=1, min_grad=0.5, value_to_vox=1.0):
-        """The rigid mode alone with the volume data term, from the built normal equations (associate against the volume ->
-        build (+ all-reduce) -> WarpSolver.global_step), n_iters times; asynchronous.  (There is no sampled rigid-mode step for
-        volumes.)"""
+    def global_iteration_volume(self, live, band, rw=5.0, max_dist=2.0, huber=0.0, lm_rel=0.1, n_iters=1, min_grad=0.5, value_to_vox=1.0,
+                                built=True, stride=1):
+        """The rigid mode alone with the volume data term, n_iters times; asynchronous.  built=True (the default): from the built
+        normal equations, regulariser included (associate against the volume inside the build (+ all-reduce) ->
+        WarpSolver.global_step).  built=False: straight from the samples of every `stride`-th tile
+        (WarpSolver.global_sampled_volume: data rows only, no build, no gather)."""
+        if not built:
+            self.solver.global_sampled_volume(live, self.lw, band, max_dist, huber, lm_rel, n_steps=n_iters, stride=stride,
+                                              min_grad=min_grad, value_to_vox=value_to_vox)
+            return
         self.solver.iterate_volume(live, self.lw, rw, band, max_dist, huber, n_iters=0, n_global=n_iters, global_lm=lm_rel,
                                    min_grad=min_grad, value_to_vox=value_to_vox)
 
@@ -292,12 +299,16 @@ class SlabFrame:
 
     def step(self, depth, lw_cam, gn_iters=10, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.5, stage_ms=None,
              update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None,
-             data_term="depth"):
+             data_term="depth", global_built=None):
         """data_term: "depth" = projective association against the depth maps (one projection and one pixel per sample and
         view; the live sweep overlaps the whole solve); "volume" = association against the live TSDF volume the frame fuses from
         all views anyway (FrameSolver.gn_iteration_volume: one trilinear cell per sample whatever the number of views, band =
-        the truncation distance; the live sweep is joined -- and, on several ranks, all-gathered -- BEFORE the solve, the rigid-mode
-        steps come from the built system, and data_views / global_stride do not apply).
+        the truncation distance; the live sweep is joined -- and, on several ranks, all-gathered -- BEFORE the solve, and data_views
+        does not apply).
+        global_built: where the rigid-mode steps come from.  None keeps each term's choice: straight from the samples of every
+        `global_stride`-th tile for "depth" (FrameSolver.global_iteration), from the built system for "volume", where
+        global_stride then does not apply.  data_term="volume", global_built=False: from the samples, against the volume
+        (FrameSolver.global_iteration_volume(built=False)), and global_stride applies.  For "depth" the argument is not read.
         Defaults (regulariser weight, LM damping, association gate and Huber threshold in voxels, the per-frame decay of the warp
         field `relax` = 0.8) are the ones under which the loop follows a +-0.6 voxel oscillation of the bench scene with a BOUNDED
         warp field: max node translation 0.85 voxel at frame 400, 1.01 at frame 1 200, sample count constant (tools/soak.py;
@@ -370,7 +381,9 @@ class SlabFrame:
             # strict, so the cells that touch a voxel no view updated drop out
             band = float(torch.tensor(self.tvox, dtype=self.live.dtype))
             if ng > 0:
-                self.fs.global_iteration_volume(live_full, band, rw=rw, max_dist=max_dist, huber=huber, lm_rel=global_lm, n_iters=ng)
+                sampled = global_built is not None and not global_built
+                self.fs.global_iteration_volume(live_full, band, rw=rw, max_dist=max_dist, huber=huber, lm_rel=global_lm, n_iters=ng,
+                                                built=not sampled, stride=self.GLOBAL_STRIDE if global_stride is None else int(global_stride))
             self.fs.gn_iteration_volume(live_full, band, rw=rw, lm_abs=lm_abs, lm_rel=lm_rel, max_dist=max_dist, huber=huber,
                                         n_iters=gn_iters)
         elif ng > 0:

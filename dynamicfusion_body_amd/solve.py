@@ -664,6 +664,13 @@ class WarpSolver:
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
         _lib.check(self.lib.dfh_gn_associate(self._problem(lw_dq), frame, current_stream_ptr()), "dfh_gn_associate")
 
+    def _volume_term(self, live, band, max_dist, min_grad, value_to_vox):
+        """The live volume and the term's settings as a dfh_gn_volume_term."""
+        t = self._term
+        t.live.data, t.live.dtype, t.live.res = live.data_ptr(), dtype_code(live), _lib.iarr(live.shape)
+        t.value_to_vox, t.band, t.max_dist, t.min_grad = float(value_to_vox), float(band), float(max_dist), float(min_grad)
+        return t
+
     def associate_volume(self, live, lw_dq, band, max_dist=0.0, min_grad=0.5, value_to_vox=1.0):
         """Association of the warped samples against a live TSDF VOLUME (dfh_gn_associate_volume): one trilinear cell per
         sample, one Newton step along the interpolant's gradient onto its zero level set -- whatever the number of views
@@ -672,25 +679,52 @@ class WarpSolver:
         +-band voxels (band = the truncation distance drops the cells a fresh sweep never touched), its gradient is at
         least min_grad, and -- max_dist > 0 -- the Newton point lies within max_dist voxels.  Writes corr / valid."""
         _check_live(live)
-        t = self._term
-        t.live.data, t.live.dtype, t.live.res = live.data_ptr(), dtype_code(live), _lib.iarr(live.shape)
-        t.value_to_vox, t.band, t.max_dist, t.min_grad = float(value_to_vox), float(band), float(max_dist), float(min_grad)
+        t = self._volume_term(live, band, max_dist, min_grad, value_to_vox)
         _lib.check(self.lib.dfh_gn_associate_volume(self._problem(lw_dq), t, current_stream_ptr()), "dfh_gn_associate_volume")
+
+    def build_volume(self, live, lw_dq, rw, band, max_dist=0.0, huber=0.0, min_grad=0.5, value_to_vox=1.0):
+        """associate_volume + build in one launch sequence (dfh_gn_build_volume): same corr / valid, same system, bit for bit;
+        float32 live volumes and the planned build only (otherwise the two calls are made)."""
+        _check_live(live)
+        if self._pattern is None:
+            self._build_pattern()
+        if (live.dtype != torch.float32 or self.S == 0 or _lib.opt_on("py_gn_atomic") or _lib.opt_on("py_gn_no_fused_assoc")):
+            self.associate_volume(live, lw_dq, band, max_dist, min_grad, value_to_vox)
+            return self.build(lw_dq, rw, huber)
+        reg_here = (not self.distributed) or _dist.world()[0] == 0
+        t = self._volume_term(live, band, max_dist, min_grad, value_to_vox)
+        _lib.check(self.lib.dfh_gn_build_volume(self._problem(lw_dq, rw, huber, reg=reg_here), t, current_stream_ptr()), "dfh_gn_build_volume")
+        self._allreduce_system()
 
     def iterate_volume(self, live, lw_dq, rw, band, max_dist=0.0, huber=0.0, lm_abs=0.0, lm_rel=0.0, n_iters=1, n_global=0,
                        global_lm=0.1, min_grad=0.5, value_to_vox=1.0):
-        """The loop of iterate_associated with the volume data term: n_global x [associate_volume -> build -> global_step],
-        then n_iters x [associate_volume -> build -> solve_update]; asynchronous.  The association is a launch of its own in
-        front of the unchanged build (which all-reduces: the sharded multi-rank solve works as it does for depth maps)."""
+        """The loop of iterate_associated with the volume data term: n_global x [build_volume -> global_step], then n_iters x
+        [build_volume -> solve_update]; asynchronous.  On one GPU with a float32 live volume they are ONE call,
+        dfh_gn_solve_volume (the same bits as the separate calls); the options of iterate_associated select the older sequences:
+        py_gn_no_fused_assoc (associate_volume -> build, two launches), py_gn_no_fused_iter (one call per build and per solve),
+        py_gn_iter_per_call (one dfh_gn_solve_volume call per iteration).  Several ranks: build_volume all-reduces, the sharded
+        solve works as it does for depth maps."""
         _check_live(live)
-        for _ in range(int(n_global)):
-            self.associate_volume(live, lw_dq, band, max_dist, min_grad, value_to_vox)
-            self.build(lw_dq, rw, huber)
-            self.global_step(global_lm)
-        for _ in range(int(n_iters)):
-            self.associate_volume(live, lw_dq, band, max_dist, min_grad, value_to_vox)
-            self.build(lw_dq, rw, huber)
-            self.solve_update(lm_abs, lm_rel)
+        if self._pattern is None:
+            self._build_pattern()
+        one_call = (live.dtype == torch.float32 and self.S > 0 and not _lib.opt_on("py_gn_atomic") and
+                    not _lib.opt_on("py_gn_no_fused_assoc") and not _lib.opt_on("py_gn_no_fused_iter") and
+                    not (self.distributed and (_dist.world()[1] > 1 or self.force_collective)))
+        per_call = one_call and _lib.opt_on("py_gn_iter_per_call")
+        if not one_call or per_call:
+            for _ in range(int(n_global)):
+                self.build_volume(live, lw_dq, rw, band, max_dist, huber, min_grad, value_to_vox)
+                self.global_step(global_lm)
+            if not one_call:
+                for _ in range(int(n_iters)):
+                    self.build_volume(live, lw_dq, rw, band, max_dist, huber, min_grad, value_to_vox)
+                    self.solve_update(lm_abs, lm_rel)
+                return
+        sp = self._solve_params(lm_abs, lm_rel, n_iters, n_global, global_lm, per_call)
+        t = self._volume_term(live, band, max_dist, min_grad, value_to_vox)
+        prob = self._problem(lw_dq, rw, huber)
+        for _ in range(int(n_iters) if per_call else 1):
+            _lib.check(self.lib.dfh_gn_solve_volume(prob, t, sp, current_stream_ptr()), "dfh_gn_solve_volume")
 
     # -- iteration ---------------------------------------------------------------------------
     def build(self, lw_dq, rw, huber=0.0):
@@ -743,6 +777,13 @@ class WarpSolver:
                     self.solve_update(lm_abs, lm_rel)
                 return
             frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        sp = self._solve_params(lm_abs, lm_rel, n_iters, n_global, global_lm, per_call)
+        prob = self._problem(lw_dq, rw, huber)
+        for _ in range(int(n_iters) if per_call else 1):
+            _lib.check(self.lib.dfh_gn_solve(prob, frame, sp, current_stream_ptr()), "dfh_gn_solve")
+
+    def _solve_params(self, lm_abs, lm_rel, n_iters, n_global, global_lm, per_call):
+        """One dfh_gn_solve / dfh_gn_solve_volume call's schedule (per_call: one node iteration, the rigid-mode steps were taken)."""
         sp = self._sp
         sp.pcg_iters, sp.lm_abs, sp.lm_rel, sp.step = self.pcg_iters, float(lm_abs), float(lm_rel), 1.0
         sp.x_out, sp.pcg_workspace, sp.pcg_workspace_bytes = self.dx.data_ptr(), self.pcg_ws.data_ptr(), self.pcg_ws.numel() * 8
@@ -754,9 +795,7 @@ class WarpSolver:
                 self.global_xi = torch.zeros(8, dtype=torch.float64, device="cuda")
             sp.global_xi_out, sp.global_scratch = self.global_xi.data_ptr(), self._global_ws.data_ptr()
             sp.global_scratch_bytes = self._global_ws.numel() * 8
-        prob = self._problem(lw_dq, rw, huber)
-        for _ in range(int(n_iters) if per_call else 1):
-            _lib.check(self.lib.dfh_gn_solve(prob, frame, sp, current_stream_ptr()), "dfh_gn_solve")
+        return sp
 
     def _allreduce_system(self):
         """Sum of the normal equations over ranks, in place: the upper block triangle + J^T r + {cost, count} in one collective
@@ -793,6 +832,19 @@ class WarpSolver:
         one view or lists.  Samples sharded over ranks: the 29 sums are all-reduced, every rank applies the same twist.
         Asynchronous; self.global_xi holds the last step's twist | objective | valid count."""
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        self._global_sampled(self.lib.dfh_gn_global_sampled, "dfh_gn_global_sampled", frame, lw_dq, huber, lm_rel, n_steps, stride)
+
+    def global_sampled_volume(self, live, lw_dq, band, max_dist=0.0, huber=0.0, lm_rel=0.1, n_steps=1, stride=1, min_grad=0.5,
+                              value_to_vox=1.0):
+        """global_sampled with the volume data term (dfh_gn_global_sampled_volume): the samples of every `stride`-th tile are
+        associated against the live TSDF volume (float32 or float64) as associate_volume associates them.  The same
+        all-reduce of the 29 sums where the samples are sharded; self.global_xi as there."""
+        _check_live(live)
+        t = self._volume_term(live, band, max_dist, min_grad, value_to_vox)
+        self._global_sampled(self.lib.dfh_gn_global_sampled_volume, "dfh_gn_global_sampled_volume", t, lw_dq, huber, lm_rel, n_steps, stride)
+
+    def _global_sampled(self, call, name, against, lw_dq, huber, lm_rel, n_steps, stride):
+        """The sampled rigid-mode steps through `call` (the depth or the volume entry point; against: its frame or term)."""
         if getattr(self, "global_xi", None) is None or self.global_xi.numel() < 8:
             self.global_xi = torch.zeros(8, dtype=torch.float64, device="cuda")
         nbytes = self.lib.dfh_gn_global_sampled_bytes(self.S, int(stride))
@@ -802,14 +854,12 @@ class WarpSolver:
         prob = self._problem(lw_dq, huber=huber)
         ws = (self._gs_ws.data_ptr(), self._gs_ws.numel() * 8, current_stream_ptr())
         if not sharded:
-            _lib.check(self.lib.dfh_gn_global_sampled(prob, frame, int(stride), float(lm_rel), int(n_steps), self.global_xi.data_ptr(), 0, *ws),
-                       "dfh_gn_global_sampled")
+            _lib.check(call(prob, against, int(stride), float(lm_rel), int(n_steps), self.global_xi.data_ptr(), 0, *ws), name)
             return
         if getattr(self, "_gs_sums", None) is None:
             self._gs_sums = torch.zeros(32, dtype=torch.float64, device="cuda")
         for _ in range(int(n_steps)):
-            _lib.check(self.lib.dfh_gn_global_sampled(prob, frame, int(stride), float(lm_rel), 1, 0, self._gs_sums.data_ptr(), *ws),
-                       "dfh_gn_global_sampled")
+            _lib.check(call(prob, against, int(stride), float(lm_rel), 1, 0, self._gs_sums.data_ptr(), *ws), name)
             _dist.allreduce_system(self._gs_sums, force=self.force_collective)
             _lib.check(self.lib.dfh_gn_global_apply(self._gs_sums.data_ptr(), float(lm_rel), self.N, self.node_dq.data_ptr(),
                                                     self.global_xi.data_ptr(), current_stream_ptr()), "dfh_gn_global_apply")

@@ -401,6 +401,12 @@ int dfh_gn_associate_volume(const dfh_gn_problem *problem, const dfh_gn_volume_t
  * the data-row kernel -- every sample is warped once, associated as by dfh_gn_associate (corr / valid receive the same values,
  * bit for bit) and the valid ones go straight on to their Jacobian rows; it needs the data plan and DFH_F32 maps. */
 int dfh_gn_build(const dfh_gn_problem *problem, const dfh_gn_frame *frame, void *stream);
+/* dfh_gn_build with a frame, for volumes: the cell evaluation of dfh_gn_associate_volume (steps 1-7 above, the same operations)
+ * runs inside the data-row kernel.  corr / valid and vals / rhs / cost_count are, bit for bit, those of dfh_gn_associate_volume
+ * followed by dfh_gn_build(problem, NULL).  It needs the data plan (blk_ptr != NULL) and a DFH_F32 live volume (DFH_F64 volumes
+ * keep the two calls, as DFH_F64 depth maps do).  DFH_E_BADARG (before any HIP call): what dfh_gn_build and
+ * dfh_gn_associate_volume refuse, a problem without a plan, a DFH_F64 volume. */
+int dfh_gn_build_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, void *stream);
 size_t dfh_gn_partial_doubles(int knn);
 
 /* Samples per tile of the planned build (a scratch row = a run of equal node tuples inside one tile; callers size tile_off,
@@ -450,6 +456,12 @@ int dfh_pcg_solve_update(const int *row_ptr, const int *col, double *vals, const
  * needs its data plan.  Multi-GPU solves keep the separate calls (the all-reduce goes between build and solve).  Reference: the
  * body of least_squares' iteration for Fusion.computef, core/fusion.py:356-389. */
 int dfh_gn_solve(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_solve_params *params, void *stream);
+/* dfh_gn_solve with the volume data term: the same schedule (params->n_global x [dfh_gn_build_volume -> dfh_gn_global_step], then
+ * params->n_iters x [dfh_gn_build_volume with the solve workspace's clearing riding in its data-row launch -> the PCG and twist
+ * update of dfh_pcg_solve_update]), the same bits as the separate calls (also as dfh_gn_associate_volume -> dfh_gn_build(problem,
+ * NULL) -> dfh_gn_global_step / dfh_pcg_solve_update).  term: a DFH_F32 live volume; the problem needs its data plan.  Refuses what
+ * dfh_gn_build_volume and dfh_gn_solve refuse. */
+int dfh_gn_solve_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, const dfh_gn_solve_params *params, void *stream);
 
 /* Multi-GPU solve: what travels in the per-iteration all-reduce.  `system` = {J^T J blocks (n_blocks x 36) | J^T r (6 n_nodes) |
  * cost, count} as the builds write it; J^T J is symmetric, so only the blocks with col >= row are packed (then J^T r and
@@ -513,6 +525,12 @@ int dfh_relax_twists(double *node_dq, int n_nodes, double factor, void *stream);
 size_t dfh_gn_global_sampled_bytes(int n_samples, int stride);
 int dfh_gn_global_sampled(const dfh_gn_problem *problem, const dfh_gn_frame *frame, int stride, double lm_rel, int n_steps,
                           double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream);
+/* dfh_gn_global_sampled with the volume data term: the samples of every `stride`-th tile are associated by the cell evaluation of
+ * dfh_gn_associate_volume (a DFH_F32 or DFH_F64 live volume, knn 1..8) instead of against the views' table; everything else -- the
+ * rows, the sums and their order, scratch, xi_out, sums_out with n_steps = 1 followed by dfh_gn_global_apply -- is that call's
+ * contract.  A sample beyond n_samples touches no voxel.  n_steps == 0: DFH_OK, nothing is checked further or launched. */
+int dfh_gn_global_sampled_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, int stride, double lm_rel, int n_steps,
+                                 double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream);
 int dfh_gn_global_apply(const double *sums29, double lm_rel, int n_nodes, double *node_dq, double *xi_out, void *stream);
 size_t dfh_gn_global_step_bytes(void);
 int dfh_gn_global_step(const double *vals, int n_blocks, const double *rhs, int n_nodes, double lm_rel, double *node_dq, double *xi_out,
