@@ -103,6 +103,8 @@ _SIGNATURES = {
     "dfh_dqb_workspace_bytes": (ctypes.c_size_t, [_slab_p]),
     "dfh_dqb_workspace_bytes_cached": (ctypes.c_size_t, [_slab_p, _int, _int, _int]),
     "dfh_fuse_volume_dqb": (_int, [_volume_p, ctypes.POINTER(Live), ctypes.POINTER(Nodes), _c_double_p, _dbl, _dbl, _vp, ctypes.c_size_t, _int, _vp]),
+    "dfh_integrate_depth_dqb": (_int, [_volume_p, ctypes.POINTER(DepthViews), ctypes.POINTER(Nodes), _c_double_p, _dbl, _dbl, _int, _vp,
+                                      ctypes.c_size_t, _int, _vp]),
     "dfh_residual_rigid": (_int, [_vp, _vp, _vp, _int, _c_double_p, _vp, _vp]),
     "dfh_gn_build_rigid": (_int, [_vp, _vp, _vp, _vp, _int, _c_double_p, _vp, _vp]),
     "dfh_residual_data": (_int, [_vp, _vp, _vp, _vp, _int, _int, _vp, _vp, _vp, _int, _c_double_p, _vp, _vp]),

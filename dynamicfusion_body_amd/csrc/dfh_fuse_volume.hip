@@ -6,7 +6,7 @@
 // reference's trilinear scheme and blend.  The warp / sampler arithmetic is the exact fp64
 // restatement in dfh_dq.h; the blend is evaluated in fp64 with IEEE division and rounded
 // once to the volume dtype.
-#include "dfh_dq.h"
+#include "dfh_dqb_front.h"
 
 #include <algorithm>
 #include <cmath>
@@ -247,50 +247,14 @@ static int launch_rigid(void *tsdf, void *tsdf_w, const void *live, RigidParams 
 // ------------------------------------------------------------------------------------------
 // K3: node search + DQ blending
 // ------------------------------------------------------------------------------------------
-constexpr int kBX = 4, kBY = 4, kBZ = 16;      // brick = one 256-thread block, z fastest (64-B rows)
-constexpr int kCap = 256;                       // candidate nodes kept per brick (<= 256: one per thread when staged)
-constexpr int kKMax = 8;                        // knn <= 8
+// (the brick shape kBX x kBY x kBZ, kCap, kKMax, DqbParams, topk_insert and select_k live in dfh_dqb_front.h, shared with
+// dfh_integrate_warped.hip)
 // half diagonal of the voxel-centre span of a brick
 #define DFH_BRICK_RADIUS 7.7942286340599480     /* sqrt(1.5^2 + 1.5^2 + 7.5^2) */
 // head-room for off-lattice points (dfh_sample_knn_bricks): a point p belongs to the brick of its nearest voxel centre
 // v, |p - v| <= sqrt(3)/2, so D_k(p) <= D_k(v) + sqrt(3)/2 and a node among p's k nearest is within
 // D_k(p) + sqrt(3)/2 of v, hence of the brick's box
 #define DFH_SAMPLE_MARGIN 1.7320508075688774
-
-struct DqbParams {
-    DQ lw;
-    double tdist, wmax;
-    int X, Y, Z;
-    int LX, LY, LZ;
-    int x0, nx;
-    int N, k;
-    int nbx, nby, nbz;      // bricks per axis (over the slab)
-};
-
-// sorted (ascending, stable) insertion into a KS-slot list held in registers
-template <int KS>
-__device__ __forceinline__ void topk_insert(double (&bd)[KS], int (&bi)[KS], double d2, int idx) {
-    bool ins = false;                       // once inserted, everything below shifts down: equal distances keep their
-#pragma unroll
-    for (int i = 0; i < KS; ++i) {          // arrival order (a stable sort, KD-tree-like: ties go to the lower node index)
-        const bool lt = ins || d2 < bd[i];
-        ins = lt;
-        const double td = bd[i];
-        const int ti = bi[i];
-        bd[i] = lt ? d2 : td;
-        bi[i] = lt ? idx : ti;
-        d2 = lt ? td : d2;
-        idx = lt ? ti : idx;
-    }
-}
-
-template <int KS>
-__device__ __forceinline__ double select_k(const double (&bd)[KS], int k) {
-    double r = bd[0];
-#pragma unroll
-    for (int i = 1; i < KS; ++i) r = (k - 1 == i) ? bd[i] : r;
-    return r;
-}
 
 // Per brick: the nodes that can be among the k nearest of ANY voxel centre p of the brick.
 // With c the brick centre and r its radius, D_k(p) <= d_k(c) + r for every p in the brick, so a
@@ -333,87 +297,7 @@ __global__ __launch_bounds__(256) void dqb_candidates_kernel(const double *__res
     c[0] = cnt <= kCap ? cnt : -1;
 }
 
-// k nearest nodes of `pos` (ascending distance, ties by node index = stable argsort of the
-// squared distances; what KDTree.query(pos, k+1)[1][:-1] yields, core/fusion.py:175-176).
-// All 256 threads of the block must call this (LDS staging + barriers).
-template <int KS>
-__device__ __forceinline__ void block_knn(const double *__restrict__ node_pos, const int *__restrict__ c, int N,
-                                          double px, double py, double pz, bool active,
-                                          double (&bd)[KS], int (&bi)[KS]) {
-    __shared__ double spos[kCap * 3];
-    __shared__ int sidx[kCap];
-    const int cnt = c[0];
-    const int total = cnt >= 0 ? cnt : N;
-#pragma unroll
-    for (int i = 0; i < KS; ++i) { bd[i] = __builtin_huge_val(); bi[i] = -1; }
-    for (int base = 0; base < total; base += kCap) {
-        const int n = min(kCap, total - base);
-        if ((int)threadIdx.x < n) {
-            const int gi = cnt >= 0 ? c[1 + base + threadIdx.x] : base + (int)threadIdx.x;
-            sidx[threadIdx.x] = gi;
-            spos[3 * threadIdx.x + 0] = node_pos[3 * gi + 0];
-            spos[3 * threadIdx.x + 1] = node_pos[3 * gi + 1];
-            spos[3 * threadIdx.x + 2] = node_pos[3 * gi + 2];
-        }
-        __syncthreads();
-        if (active) {
-            for (int i = 0; i < n; ++i) {
-                const double dx = px - spos[3 * i], dy = py - spos[3 * i + 1], dz = pz - spos[3 * i + 2];
-                const double d2 = (dx * dx + dy * dy) + dz * dz;
-                if (d2 < bd[KS - 1]) topk_insert<KS>(bd, bi, d2, sidx[i]);
-            }
-        }
-        __syncthreads();
-    }
-}
-
-// Fusion.dq_blend + warp (core/fusion.py:502-551) for one point whose k nearest nodes are
-// (bd, bi).  Returns the point warped by the blended DQ and then by m_lw (x1 is re-rounded to
-// float32 inside the second dqb_warp, core/util.py:69); *wi_out = mean node distance (:180-183).
-template <int KS>
-__device__ __forceinline__ void dqb_weights(const double *__restrict__ node_w, const double (&bd)[KS], const int (&bi)[KS], int k,
-                                            double (&wg)[KS], double &wi) {
-    wi = 0.0;
-#pragma unroll
-    for (int j = 0; j < KS; ++j) {
-        wg[j] = 0.0;
-        if (j < k) {
-            const double dist = sqrt(bd[j]);
-            const double t = dist / (2.0 * node_w[bi[j]]);
-            wg[j] = exp(-1.0 * (t * t));                                 // :537
-            wi = wi + dist / (double)k;                                  // mean node distance (:180-183)
-        }
-    }
-}
-
-template <int KS>
-__device__ __forceinline__ D3 dqb_blend_warp(const double *__restrict__ node_dq, const double (&wg)[KS], const int (&bi)[KS], int k,
-                                             const double *lw, double px, double py, double pz) {
-    double b[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#pragma unroll
-    for (int j = 0; j < KS; ++j) {
-        if (j < k) {
-            const int gi = bi[j];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) b[c] = b[c] + wg[j] * node_dq[8 * gi + c];   // :538
-        }
-    }
-    // 8-norm (:551), pairwise like numpy's reduction of 8 contiguous values
-    const double n2 = ((b[0] * b[0] + b[1] * b[1]) + (b[2] * b[2] + b[3] * b[3])) +
-                      ((b[4] * b[4] + b[5] * b[5]) + (b[6] * b[6] + b[7] * b[7]));
-    const double n = sqrt(n2);
-    if (n == 0.0) {                                                       // :544-549
-        b[0] = 1.0;
-#pragma unroll
-        for (int c = 1; c < 8; ++c) b[c] = 0.0;
-    } else {
-        const double inv = 1.0 / n;                  // one division; each component within 1 ulp of b/n
-#pragma unroll
-        for (int c = 0; c < 8; ++c) b[c] = b[c] * inv;
-    }
-    const D3 x1 = dqb_warp_exact(b, px, py, pz);                          // :510
-    return dqb_warp_exact(lw, round_f32(x1.x), round_f32(x1.y), round_f32(x1.z));   // :512
-}
+// (block_knn, dqb_weights, dqb_blend_warp: dfh_dqb_front.h)
 
 // MODE 0: search the brick's candidates; 1: search and store per voxel the k indices (and, with a weight cache, the
 // k blend weights and the integration weight wi); 2: load the stored indices; 3: load indices and weights.
@@ -1577,28 +1461,18 @@ static int launch_dqb(void *tsdf, void *tsdf_w, const void *live, const double *
     return DFH_OK;
 }
 
-// The grid, live-grid and slab fields of a K2 / K3 parameter block (live_res == nullptr: calls that sample no live volume).
-template <typename Params>
-static void set_grid(Params &p, const dfh_slab &sl, const int *live_res) {
-    p.X = sl.res[0]; p.Y = sl.res[1]; p.Z = sl.res[2];
-    if (live_res) { p.LX = live_res[0]; p.LY = live_res[1]; p.LZ = live_res[2]; }
-    p.x0 = sl.x0; p.nx = sl.x1 - sl.x0;
-}
+// (set_grid, dqb_params, cand_bytes: dfh_dqb_front.h)
 
-// ... and K3's node counts and bricks per axis on top (everything but lw, tdist and wmax)
-static DqbParams dqb_params(const dfh_slab &sl, const int *live_res, int n_nodes, int knn) {
-    DqbParams p = {};
-    set_grid(p, sl, live_res);
-    p.N = n_nodes; p.k = knn;
-    p.nbx = (p.nx + kBX - 1) / kBX;
-    p.nby = (p.Y + kBY - 1) / kBY;
-    p.nbz = (p.Z + kBZ - 1) / kBZ;
-    return p;
-}
+// Which of K3's two paths wrote a level-2 workspace's weight region: workspace -> 1 (fast entries) / 2 (fp64 weights).
+static std::mutex &dqb_format_mutex() { static std::mutex mu; return mu; }
+static std::unordered_map<const void *, int> &dqb_format_map() { static std::unordered_map<const void *, int> format; return format; }
 
-static size_t cand_bytes(const dfh_slab &sl) {
-    const DqbParams p = dqb_params(sl, nullptr, 0, 0);
-    return (((size_t)p.nbx * p.nby * p.nbz * (kCap + 1) * sizeof(int)) + 15) & ~(size_t)15;
+// A call that rewrites a workspace's stored indices without writing its weight region (dfh_integrate_depth_dqb with
+// rebuild_candidates) drops the record: stored weights are then not known to belong to the stored indices, and the next
+// dfh_fuse_volume_dqb call without a rebuild recomputes them (mode 2) instead of trusting what an earlier graph left there.
+void dqb_forget_weights(const void *workspace) {
+    std::lock_guard<std::mutex> lock(dqb_format_mutex());
+    dqb_format_map().erase(workspace);
 }
 
 static int check_live(const char *what, const dfh_live *l) {
@@ -1773,8 +1647,8 @@ extern "C" int dfh_fuse_volume_dqb(const dfh_volume *vol, const dfh_live *live_v
     // indices serve both; the weights are then recomputed, mode 2)
     const bool fast = vol_dtype == DFH_F32 && knn == 4 && !on(opt().k3_exact);
     if (has_w) {
-        static std::mutex mu;
-        static std::unordered_map<const void *, int> format;           // workspace -> 1 (fast entries) / 2 (fp64 weights)
+        std::mutex &mu = dqb_format_mutex();
+        std::unordered_map<const void *, int> &format = dqb_format_map();
         std::lock_guard<std::mutex> lock(mu);
         if (mode == 1) {
             if (format.size() > 4096) format.clear();

@@ -133,6 +133,46 @@ class Fusion:
                                 np.asarray(self._lw, dtype=np.float64), self._tdist, wmax,
                                 workspace=self._workspace, rebuild_candidates=rebuild)
 
+    def updateTSDF_depths(self, depths, lws, wmax=100.0, weight="node_distance", scale=1.0, center=np.zeros(3)):
+        """The canonical update straight from the frame's depth maps (K1w, dfh_integrate_depth_dqb): every canonical voxel is
+        warped through the DQB warp field and `_lw` as in updateTSDF, projected into each map as in fuseDepths, and the
+        projective signed distance is averaged in -- DynamicFusion's surface fusion, without the live volume updateTSDF
+        resamples.  Needs the intrinsics of InitializeCanonicalSpace(..., K=K); depth maps follow fuseDepths' dtype rule
+        (float32 on the device unless a float64 map is not float32-exact: then every map travels as float64).
+        weight: "node_distance" = updateTSDF's running average (core/fusion.py:180-190), "unit" = fuseDepths'."""
+        if getattr(self, '_K', None) is None:
+            raise ValueError('updateTSDF_depths needs the intrinsics: call InitializeCanonicalSpace(..., K=K) first')
+        depths, lws = list(depths), list(lws)
+        if len(depths) != len(lws):
+            raise ValueError('length of camera matrix array must equal that of depth maps')
+        if weight not in kernels.WARPED_WEIGHTS:
+            raise ValueError("weight must be one of %s, not %r" % (sorted(kernels.WARPED_WEIGHTS), weight))
+        lws = [np.asarray(m, dtype=np.float64) for m in lws]
+        for m in lws:
+            if m.shape != (3, 4):
+                raise ValueError('lw must be a 3x4 camera extrinsic')
+        for d in depths:
+            if (d.dim() if _is_tensor(d) else np.asarray(d).ndim) != 2:
+                raise ValueError('depth map must be 2-D')
+            if tuple(d.shape) != tuple(depths[0].shape):
+                raise ValueError('all depth maps of one call must have the same shape')
+
+        def exact32(d):
+            return (d.dtype == torch.float32) if _is_tensor(d) else f32_exact(np.asarray(d))
+        ddt = torch.float32 if all(exact32(d) for d in depths) else torch.float64
+        ds = [to_device(d if _is_tensor(d) else np.asarray(d), dtype=ddt) for d in depths]
+        self._ensure_volumes()
+        pos, dq, w, _ = self.node_arrays()
+        res = tuple(self._T.shape)
+        key = (res, pos.tobytes(), w.tobytes(), self._knn)          # shared with updateTSDF: one workspace serves both
+        rebuild = key != self._workspace_key
+        if rebuild:
+            self._workspace = kernels.dqb_workspace(res, knn=self._knn, n_nodes=len(pos))
+            self._workspace_key = key
+        kernels.integrate_depth_dqb(self._T, self._Wt, ds, self._K, self._Kinv, lws, scale, center, self._tdist, pos, dq, w,
+                                    self._knn, np.asarray(self._lw, dtype=np.float64), wmax=wmax, weight=weight,
+                                    tsdf_res=res[0], workspace=self._workspace, rebuild_candidates=rebuild)
+
     # ------------------------------------------------------------------ A5 (single-point helpers)
     def _gather_nodes(self, locations, dqs):
         pos, dq, w, _ = self.node_arrays()

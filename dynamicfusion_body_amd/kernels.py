@@ -296,3 +296,52 @@ def fuse_volume_dqb(T, Wt, live, node_pos, node_dq, node_w, knn, lw_dq, tdist, w
                                  workspace.numel() * 4, 1 if rebuild_candidates else 0, current_stream_ptr())
     _lib.check(rc, "dfh_fuse_volume_dqb")
     return T, Wt
+
+
+WARPED_WEIGHTS = {"unit": 0, "node_distance": 1}                              # include/dfusion_hip.h: DFH_WARPED_W_*
+
+
+def integrate_depth_dqb(T, Wt, depths, K, Kinv, lws, scale, center, tdist, node_pos, node_dq, node_w, knn, lw_dq, wmax=100.0,
+                        weight="unit", tsdf_res=None, res=None, x_range=None, workspace=None, rebuild_candidates=True):
+    """K1w = depth maps fused into the canonical volume through the warp field (dfh_integrate_depth_dqb): every canonical voxel
+    is warped by fuse_volume_dqb's chain (Fusion.warp, reference core/fusion.py:502-551), projected into each map by
+    integrate_depth's chain (core/fusion_dm.py:191-203) and the signed distance averaged in -- no live volume.
+    depths: list of (H, W) CUDA tensors of one shape and dtype, lws: their 3x4 extrinsics; more than 16 views are taken 16 at a
+    time.  weight: "unit" = integrate_depth's running average, "node_distance" = fuse_volume_dqb's (the mean node distance wi).
+    `workspace` is a dqb_workspace, shared with fuse_volume_dqb; pass rebuild_candidates=False while the node positions, knn and
+    slab are unchanged."""
+    depths, lws = list(depths), list(lws)
+    if len(depths) != len(lws):
+        raise ValueError('length of camera matrix array must equal that of depth maps')        # core/fusion_dm.py:96-97
+    if weight not in WARPED_WEIGHTS:
+        raise ValueError("weight must be one of %s, not %r" % (sorted(WARPED_WEIGHTS), weight))
+    for d in depths:                                   # (what needs no device is checked before one is asked for)
+        if not (isinstance(d, torch.Tensor) and d.dim() == 2):
+            raise ValueError("depth must be a contiguous 2-D CUDA tensor")
+        if d.shape != depths[0].shape or d.dtype != depths[0].dtype:
+            raise ValueError("all depth maps of one call must have the same shape and dtype")
+    require_gpu()
+    lib = _lib.load()
+    vol, tsdf_res = _volume(T, Wt, res, x_range, tsdf_res)
+    P, Q, Wn = _node_tensors(node_pos, node_dq, node_w)
+    for d in depths:
+        _check_depth(d)
+    if vol.slab.x1 == vol.slab.x0 or not depths:
+        return T, Wt
+    if workspace is None:
+        workspace = dqb_workspace(vol.slab.res, (vol.slab.x0, vol.slab.x1))
+        rebuild_candidates = True
+    H, W = depths[0].shape
+    nodes = _lib.Nodes(P.data_ptr(), Q.data_ptr(), Wn.data_ptr(), int(P.shape[0]), int(knn))
+    for i in range(0, len(depths), 16):
+        dd, ll = depths[i:i + 16], lws[i:i + 16]
+        n = len(dd)
+        ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dd])
+        lw = _lib.darr(np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in ll]), 12 * n)
+        views = _lib.DepthViews(n, ptrs, dtype_code(dd[0]), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), lw, float(scale),
+                                _lib.darr(np.asarray(center, dtype=np.float64), 3), tsdf_res)
+        rc = lib.dfh_integrate_depth_dqb(vol, views, nodes, _lib.darr(lw_dq, 8), float(tdist), float(wmax), WARPED_WEIGHTS[weight],
+                                         workspace.data_ptr(), workspace.numel() * 4, 1 if (rebuild_candidates and i == 0) else 0,
+                                         current_stream_ptr())
+        _lib.check(rc, "dfh_integrate_depth_dqb")
+    return T, Wt

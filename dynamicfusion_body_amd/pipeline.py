@@ -299,8 +299,16 @@ class SlabFrame:
 
     def step(self, depth, lw_cam, gn_iters=10, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.5, stage_ms=None,
              update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None,
-             data_term="depth", global_built=None):
-        """data_term: "depth" = projective association against the depth maps (one projection and one pixel per sample and
+             data_term="depth", global_built=None, update="volume", update_weight="node_distance"):
+        """update: how the canonical slab takes the frame in.  "volume" = the reference's two stages: the live volume fused from
+        the depth maps (K1) is resampled through the warp field (K3, kernels.fuse_volume_dqb; the warp gathers across slab faces,
+        so several ranks all-gather the live volume).  "depth" = DynamicFusion's surface fusion (K1w,
+        kernels.integrate_depth_dqb): every canonical voxel of this rank's slab is warped into the live frame, projected into the
+        frame's depth maps and the projective signed distance averaged in with `update_weight` ("node_distance": K3's weights,
+        so the canonical weights keep their meaning when a loop switches routes; "unit": K1's).  It reads no live volume: with
+        data_term="depth" the frame then launches no live sweep and no all-gather and `self.live` is not written; with
+        data_term="volume" the live volume is still swept (and gathered) for the solve only.
+        data_term: "depth" = projective association against the depth maps (one projection and one pixel per sample and
         view; the live sweep overlaps the whole solve); "volume" = association against the live TSDF volume the frame fuses from
         all views anyway (FrameSolver.gn_iteration_volume: one trilinear cell per sample whatever the number of views, band =
         the truncation distance; the live sweep is joined -- and, on several ranks, all-gathered -- BEFORE the solve, and data_views
@@ -322,6 +330,11 @@ class SlabFrame:
         first launches, ahead of the sample refresh's."""
         if data_term not in ("depth", "volume"):
             raise ValueError("data_term must be 'depth' or 'volume'")
+        if update not in ("depth", "volume"):
+            raise ValueError("update must be 'depth' or 'volume'")
+        if update == "depth" and update_weight not in kernels.WARPED_WEIGHTS:
+            raise ValueError("update_weight must be one of %s" % sorted(kernels.WARPED_WEIGHTS))
+        need_live = update == "volume" or data_term == "volume"       # (update="depth" fuses the maps themselves)
         import time as _t
         t0 = [_t.perf_counter()]
 
@@ -354,7 +367,9 @@ class SlabFrame:
         # plan's launches AND the whole solve (bound by latency, ten waves per CU), and the streams join in front of the TSDF
         # update (round 4; rounds 2-3 joined before the first GN iteration).  With stage timing the order is sequential.
         joined = True
-        if stage_ms is None and not _lib.opt_on("py_no_side_stream"):
+        if not need_live:
+            pass
+        elif stage_ms is None and not _lib.opt_on("py_no_side_stream"):
             if self._side is None:
                 self._side = torch.cuda.Stream()
             main = torch.cuda.current_stream()
@@ -396,12 +411,18 @@ class SlabFrame:
         mark("solve")
         if not joined:
             torch.cuda.current_stream().wait_stream(self._side)
-        if live_full is None:
+        if live_full is None and update == "volume":
             live_full = self.D.allgather_planes(self.live, R) if self.ws > 1 else self.live
         mark("allgather")
         sv = self.fs.solver
-        kernels.fuse_volume_dqb(self.T, self.Wt, live_full, sv.node_pos, sv.node_dq, sv.node_w, self.knn, self.ident_lw, self.tvox,
-                                res=(R, R, R), x_range=(self.a, self.b), workspace=self.ws_dqb, rebuild_candidates=self._first)
+        if update == "volume":
+            kernels.fuse_volume_dqb(self.T, self.Wt, live_full, sv.node_pos, sv.node_dq, sv.node_w, self.knn, self.ident_lw, self.tvox,
+                                    res=(R, R, R), x_range=(self.a, self.b), workspace=self.ws_dqb, rebuild_candidates=self._first)
+        else:
+            kernels.integrate_depth_dqb(self.T, self.Wt, depth_list, self.K, self.Kinv, lw_list, self.scale, self.center,
+                                        self.tdist_world, sv.node_pos, sv.node_dq, sv.node_w, self.knn, self.ident_lw,
+                                        weight=update_weight, tsdf_res=R, res=(R, R, R), x_range=(self.a, self.b),
+                                        workspace=self.ws_dqb, rebuild_candidates=self._first)
         self._first = False
         # the warp field decays towards the identity once the TSDF update has used it (solve.relax_twists: every node's rotation
         # vector and translation scaled by `relax`).  Fusion.updateTSDF writes most of the motion into the canonical volume every

@@ -167,6 +167,45 @@ size_t dfh_dqb_workspace_bytes_cached(const dfh_slab *slab, int knn, int n_nodes
 int dfh_fuse_volume_dqb(const dfh_volume *vol, const dfh_live *live, const dfh_nodes *nodes, const double lw_dq[8], double tdist,
                         double wmax, void *workspace, size_t workspace_bytes, int rebuild_candidates, void *stream);
 
+/* K1w  depth maps -> canonical volume through the warp field: DynamicFusion's surface fusion.  No reference counterpart as one
+ * function: it composes Fusion.warp (core/fusion.py:502-551, as A4-A6 evaluate it) with FusionDM.fuseDepths' projection
+ * (core/fusion_dm.py:191-203, as A1 evaluates it), so that the canonical update needs neither a live volume nor a second
+ * trilinear resampling.  Everything is fp64 without contraction, for both volume dtypes.
+ * For every canonical voxel i=(x,y,z), x in [x0,x1):
+ *   loc, the Gaussian weights, b^, wi = sum_j |v_j - i| / knn and
+ *   q   = dqb_warp(lw_dq, float32(dqb_warp(b^, i)))                are those of A4-A6: same neighbour order and tie rule, same
+ *                                                                  8-norm, the identity blend when |b|_8 == 0
+ * and then for every view 0 .. n_views-1 in turn, A1's chain with the index i replaced by q:
+ *   pos  = scale*(q - tsdf_res/2) + center
+ *   lpos = lw*[pos,1];  (u,v) = (K*lpos)_{0,1}/(K*lpos)_2, skipped if (K*lpos)_2 == 0
+ *   visible iff 0<=u<W-1 and 0<=v<H-1
+ *   z = -depth[rint(v)][rint(u)] (round-half-even), valid iff z>0; a z*u or z*v that is not finite updates nothing
+ *   sd = (Kinv*(z*[u,v,1]))_2 - lpos_2;  update iff sd > -tdist    (tdist in the depth maps' units, as for A1)
+ *   weight_mode DFH_WARPED_W_UNIT (A1's rule):
+ *     T <- (scale*T*w + min(tdist,sd)) / (scale*(1+w));  w <- min(1+w, wmax)
+ *   weight_mode DFH_WARPED_W_NODE_DISTANCE (A4-A6's rule, core/fusion.py:180-190: canonical weights keep their meaning when a
+ *   frame loop switches between this call and dfh_fuse_volume_dqb):
+ *     wt = w, or wi if w == 0;  T <- (T*wt + (min(tdist,sd)/scale)*wi) / (wi + wt);  w <- min(wi + wt, wmax)
+ *   T and w are rounded to the volume's dtype after every view: n_views views in one call equal n_views one-view calls bit for
+ *   bit, while the voxel is read once and written once (and only if a view updated it).
+ * With every node DQ and lw_dq the identity (or every node DQ zero) q == i exactly, and DFH_WARPED_W_UNIT on float64 volumes
+ * gives dfh_integrate_depth's bits.
+ * workspace: the buffer of dfh_fuse_volume_dqb (dfh_dqb_workspace_bytes[_cached]); one buffer can serve both entry points.
+ * rebuild_candidates != 0 builds the per-brick candidate lists, searches, and stores every voxel's knn node indices when the
+ * buffer has room for them (level >= 1); rebuild_candidates == 0 loads stored indices when the buffer has them (clamped to
+ * n_nodes - 1: a stale buffer cannot fault) and otherwise searches the existing lists.  The blend weights are always
+ * recomputed from the node positions; the weight region of a level-2 buffer is never read or written.  Storing indices drops
+ * the library's note of which dfh_fuse_volume_dqb path last wrote that region, so a later dfh_fuse_volume_dqb call without a
+ * rebuild recomputes its weights from the stored indices (same bits) until its own next rebuild.
+ * DFH_E_BADARG before any HIP call for: a bad volume or slab; null views, nodes, lw_dq or node arrays; n_views outside 0..16; a
+ * null depth pointer; H or W < 2; a depth dtype other than DFH_F32 / DFH_F64; scale == 0; knn outside 1..8; n_nodes < knn; an
+ * unknown weight_mode; a workspace smaller than dfh_dqb_workspace_bytes().  An empty slab or n_views == 0: DFH_OK, no launch. */
+#define DFH_WARPED_W_UNIT 0
+#define DFH_WARPED_W_NODE_DISTANCE 1
+int dfh_integrate_depth_dqb(const dfh_volume *vol, const dfh_depth_views *views, const dfh_nodes *nodes,
+                            const double lw_dq[8], double tdist, double wmax, int weight_mode,
+                            void *workspace, size_t workspace_bytes, int rebuild_candidates, void *stream);
+
 /* ---- warp-field solve ------------------------------------------------------------------------------
  * All arrays device fp64 unless noted; point / normal / node arrays are row-major (n x 3, n x 8).
  *
