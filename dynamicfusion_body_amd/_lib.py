@@ -114,6 +114,9 @@ _SIGNATURES = {
     "dfh_nearest_points": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp]),
     "dfh_graph_unsupported": (_int, [_vp, _int, _vp, _int, _vp, _vp, _int, _vp, _vp]),
     "dfh_dq_blend_points": (_int, [_vp, _int, _vp, _int, _vp, _vp, _vp, _int, _vp, _vp]),
+    "dfh_radius_sample_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long]),
+    "dfh_radius_sample": (_int, [_vp, ctypes.c_long, _dbl, _vp, ctypes.c_long, ctypes.POINTER(ctypes.c_long), _c_int_p, _vp,
+                                 ctypes.c_size_t, _vp]),
     "dfh_sample_knn": (_int, [_vp, _int, _vp, _vp, _int, _int, _vp, _vp, _vp]),
     "dfh_dqb_skip_layout": (_int, [_slab_p, _c_int_p, _int, _int, ctypes.POINTER(ctypes.c_size_t)]),
     "dfh_dqb_build_candidates": (_int, [_slab_p, _vp, _int, _int, _vp, ctypes.c_size_t, _vp]),

@@ -122,8 +122,16 @@ def collective_device(device=None):
 def gather_rows(rows, device=None):
     """Concatenation over ranks, in rank order, of per-rank (n_r, C) float64 numpy arrays (n_r differs from rank to rank):
     every rank gets the same (sum n_r, C) array.  Sizes, padded buffers and outputs all live on ONE device chosen once
-    (`collective_device`), so the same code runs over RCCL and over gloo."""
+    (`collective_device`), so the same code runs over RCCL and over gloo.  A torch tensor (any device) is gathered as a
+    tensor and comes back on its own device: over RCCL the rows of a CUDA tensor never visit the host."""
     import numpy as np
+    if isinstance(rows, torch.Tensor):
+        if rows.dim() != 2:
+            raise ValueError("gather_rows expects a 2-D array, got shape %s" % (tuple(rows.shape),))
+        _, ws = world()
+        if ws == 1:
+            return rows
+        return allgather_ragged(rows.to(collective_device(device)).contiguous()).to(rows.device)
     rows = np.ascontiguousarray(rows, dtype=np.float64)
     if rows.ndim != 2:
         raise ValueError("gather_rows expects a 2-D array, got shape %s" % (rows.shape,))

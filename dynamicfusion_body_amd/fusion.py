@@ -24,6 +24,8 @@ def _is_tensor(a):
 
 
 class Fusion:
+    graph_sampler = "host"       # where construct_graph / update_graph run the radius subsampling (graph.SAMPLERS); set on an instance
+
     def __init__(self, tsdf, trunc_distance, subsample_rate=5.0, knn=4, marching_cubes_step_size=3, verbose=False,
                  use_cnn=False, write_warpfield=True, volume_dtype=np.float32):
         if not _is_tensor(tsdf) and (type(tsdf) is not np.ndarray or tsdf.ndim != 3):
@@ -585,10 +587,12 @@ class Fusion:
 
     def construct_graph(self):
         """Reference core/fusion.py:101-123 (needs `_vertices` and `_radius`).  The vertex -> node table is computed on the
-        device (dfh_sample_knn); `_kdtree` is a graph.NodeIndex (device look-ups) in place of the reference's KD-tree."""
+        device (dfh_sample_knn); `_kdtree` is a graph.NodeIndex (device look-ups) in place of the reference's KD-tree.
+        `graph_sampler` = "device": the radius subsampling runs on the device as well (same nodes)."""
+        _graph._check_sampler(self.graph_sampler)
         if self._vertices is None or getattr(self, '_radius', None) is None:
             raise ValueError('construct_graph needs _vertices and _radius')
-        vidx, pos, dq, w, lookup = _graph.construct_graph_device(self._vertices, self._radius, self._knn)
+        vidx, pos, dq, w, lookup = _graph.construct_graph_device(self._vertices, self._radius, self._knn, sampler=self.graph_sampler)
         self._nodes = [(vidx[i], pos[i], dq[i].copy(), w[i]) for i in range(len(pos))]
         self._kdtree = _graph.NodeIndex(pos)
         self._neighbor_look_up = lookup.cpu().numpy().astype(np.int64)
@@ -600,12 +604,13 @@ class Fusion:
     def update_graph(self, refresh_surface=True):
         """Reference core/fusion.py:201-239: refresh the surface, re-anchor the nodes, insert nodes
         for unsupported vertices, rebuild the lookup, drop the live-frame data, write the warp field.
-        The O(vertices x nodes) steps run on the device (graph.update_graph_device)."""
+        The O(vertices x nodes) steps run on the device (graph.update_graph_device), the subsampling where `graph_sampler` says."""
+        _graph._check_sampler(self.graph_sampler)
         if refresh_surface:
             self.marching_cubes()
         pos, dq, w, _ = self.node_arrays()
         vidx, P2, Q2, W2, lookup, n_new = _graph.update_graph_device(pos, dq, w, np.asarray(self._vertices, dtype=np.float64),
-                                                                    self._radius, self._knn)
+                                                                    self._radius, self._knn, sampler=self.graph_sampler)
         vidx, P2, Q2 = vidx.cpu().numpy(), P2.cpu().numpy(), Q2.cpu().numpy()
         old = self._nodes
         N = len(old)
@@ -637,6 +642,8 @@ def _lend_nonrigid_methods():
                  "computeSparsity", "construct_graph", "_dq_blend_kdtree", "update_graph", "live_frame_mesh", "render_live_frame"):
         if name not in FusionDM.__dict__:
             setattr(FusionDM, name, Fusion.__dict__[name])
+    if "graph_sampler" not in FusionDM.__dict__:
+        FusionDM.graph_sampler = Fusion.graph_sampler
 
 
 _lend_nonrigid_methods()

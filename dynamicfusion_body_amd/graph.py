@@ -4,7 +4,8 @@ construction (core/fusion.py:101-123) and the per-frame graph update (core/fusio
 Device path (`construct_graph_device`, `update_graph_device`; what Fusion and pipeline.SlabFrame use): every
 O(vertices x nodes) step is a HIP kernel behind the C ABI -- anchor vertices (dfh_nearest_points), the vertex -> node
 table (dfh_sample_knn), the unsupported-vertex test (dfh_graph_unsupported), the new nodes' DQs (dfh_dq_blend_points).
-Only the greedy radius subsampling stays on the host: it is sequential by definition and runs on the unsupported set only.
+The greedy radius subsampling runs on the host by default (`uniform_sample`, the reference's loop) and, with
+sampler="device", as parallel rounds on the device (`uniform_sample_device`, dfh_radius_sample): the same indices either way.
 The reference's own loops (numpy + a KD-tree, statement for statement) live in oracle/graph_np.py as the checker of this
 path; nothing here builds a KD-tree: the `_kdtree` attribute the reference's callers touch is a `NodeIndex`, whose
 query() runs on the device."""
@@ -37,6 +38,43 @@ def _dev64(a):
     import torch
     t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
     return t.to(device="cuda", dtype=torch.float64).contiguous()
+
+
+SAMPLERS = ("host", "device")
+
+
+def _check_sampler(sampler):
+    if sampler not in SAMPLERS:
+        raise ValueError("sampler must be 'host' or 'device', got %r" % (sampler,))
+
+
+def uniform_sample_device(points, radius):
+    """`uniform_sample` on the device (dfh_radius_sample): the same points in the same order, index for index.
+    points: (n,3) numpy or torch, any float dtype, contiguous or not (converted to fp64 as `_dev64` does).
+    Returns (samples (m,3) CUDA fp64 -- rows of the converted input --, idx (m,) CUDA int32, ascending).  Coordinates that are
+    not finite raise ValueError (the host loop never terminates on them).  Synchronises the current stream."""
+    import ctypes
+    import torch
+    from . import _lib
+    from .device import current_stream_ptr, require_gpu
+    require_gpu()
+    lib = _lib.load()
+    P = _dev64(points)
+    if P.dim() == 1 and P.numel() == 0:
+        P = P.reshape(0, 3)
+    if P.dim() != 2 or P.shape[1] != 3:
+        raise ValueError("uniform_sample_device needs (n,3) points")
+    n = int(P.shape[0])
+    if n and not bool(torch.isfinite(P).all()):
+        raise ValueError("uniform_sample_device: coordinates must be finite")
+    nbytes = lib.dfh_radius_sample_workspace_bytes(n)
+    ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device="cuda")
+    idx = torch.empty(n, dtype=torch.int32, device="cuda")
+    count, rounds = ctypes.c_long(0), ctypes.c_int(0)
+    _lib.check(lib.dfh_radius_sample(P.data_ptr(), n, float(radius), idx.data_ptr(), n, ctypes.byref(count), ctypes.byref(rounds),
+                                     ws.data_ptr(), ws.numel() * 8, current_stream_ptr()), "dfh_radius_sample")
+    idx = idx[:count.value]
+    return P[idx.long()], idx
 
 
 def nearest_points(query, cloud):
@@ -114,23 +152,34 @@ class NodeIndex:
         return (d[0], idx[0]) if single else (d, idx)
 
 
-def construct_graph_device(vertices, radius, knn):
+def construct_graph_device(vertices, radius, knn, sampler="host"):
     """construct_graph with the vertex -> node table computed on the device.  Returns (node_vidx (N,) int64 numpy,
-    node_pos (N,3) numpy, node_dq (N,8) float32 numpy, node_w (N,) numpy, lookup (V,knn) CUDA int32)."""
+    node_pos (N,3) numpy, node_dq (N,8) float32 numpy, node_w (N,) numpy, lookup (V,knn) CUDA int32).
+    sampler="device": the radius subsampling runs on the device too (the vertices are uploaded once and no vertex comes
+    back; only the nodes do, for the returned arrays)."""
+    _check_sampler(sampler)
     from .solve import sample_knn
-    nodes_v, nodes_idx = uniform_sample(vertices, radius)
+    if sampler == "device":
+        vertices = _dev64(vertices)
+        nodes_d, idx_d = uniform_sample_device(vertices, radius)
+        nodes_v, nodes_idx = nodes_d.cpu().numpy(), idx_d.cpu().numpy()
+    else:
+        nodes_v, nodes_idx = uniform_sample(vertices, radius)
     N = len(nodes_v)
     node_w = np.full(N, 2.0 * radius)
     lookup, _ = sample_knn(vertices, nodes_v, node_w, min(knn, N))
     return np.asarray(nodes_idx, dtype=np.int64), np.asarray(nodes_v, dtype=np.float64), np.tile(NEW_NODE_DQ, (N, 1)), node_w, lookup
 
 
-def update_graph_device(node_pos, node_dq, node_w, vertices, radius, knn, gather_unsupported=None):
+def update_graph_device(node_pos, node_dq, node_w, vertices, radius, knn, gather_unsupported=None, sampler="host"):
     """update_graph (reference core/fusion.py:203-233) on device arrays.
     node_pos (N,3), node_dq (N,8), node_w (N,): the OLD graph (numpy or CUDA); vertices (V,3): the refreshed surface.
     Returns (node_vidx (N+n,) CUDA int32, node_pos, node_dq, node_w (CUDA fp64, old nodes first), lookup (V,knn) CUDA
     int32 against the new graph, n_new).  gather_unsupported: optional callable mapping this rank's unsupported
-    vertices (numpy (u,3)) to the concatenation over all ranks (so that every rank inserts the same nodes)."""
+    vertices (numpy (u,3)) to the concatenation over all ranks (so that every rank inserts the same nodes).
+    sampler="device": the unsupported set stays on the device -- gather_unsupported receives and returns CUDA tensors, and
+    the subsampling is uniform_sample_device; the same nodes as with "host"."""
+    _check_sampler(sampler)
     import torch
     from .solve import sample_knn
     V = _dev64(vertices)
@@ -143,11 +192,11 @@ def update_graph_device(node_pos, node_dq, node_w, vertices, radius, knn, gather
     nbr_old, _ = sample_knn(V, P, Wn, k)
     flag = unsupported_vertices(V, nbr_old, P, Wn)
     uns_idx = torch.nonzero(flag).reshape(-1)
-    uns = V[uns_idx].cpu().numpy()
+    uns = V[uns_idx] if sampler == "device" else V[uns_idx].cpu().numpy()
     if gather_unsupported is not None:
         uns = gather_unsupported(uns)
-    # :221 greedy radius subsampling of the unsupported set (sequential by definition: host)
-    new_v, new_i = uniform_sample(uns, radius)
+    # :221 greedy radius subsampling of the unsupported set
+    new_v, new_i = uniform_sample_device(uns, radius) if sampler == "device" else uniform_sample(uns, radius)
     n_new = len(new_v)
     Wnew = torch.full((N + n_new,), 2.0 * float(radius), dtype=torch.float64, device="cuda")       # :212, :225: every node's weight
     if n_new:
@@ -162,6 +211,10 @@ def update_graph_device(node_pos, node_dq, node_w, vertices, radius, knn, gather
         vidx_old = nearest_points(P, V)
     else:
         vidx_old = torch.zeros(N, dtype=torch.int32, device="cuda")
-    vidx = torch.cat([vidx_old, torch.from_numpy(np.asarray(new_i, dtype=np.int32)).cuda()]) if n_new else vidx_old
+    if n_new:
+        new_i = new_i if isinstance(new_i, torch.Tensor) else torch.from_numpy(np.asarray(new_i, dtype=np.int32)).cuda()
+        vidx = torch.cat([vidx_old, new_i])
+    else:
+        vidx = vidx_old
     lookup, _ = sample_knn(V, P2, Wnew, min(int(knn), N + n_new))          # :229-233
     return vidx, P2, Q2, Wnew, lookup, n_new

@@ -147,11 +147,14 @@ class SlabFrame:
     axis-0 slabs: live depth -> this rank's live slab (K1, no exchange) -> all-gather of the live volume ->
     GN iterations (samples of this slab; one all-reduce of the normal equations per iteration) -> canonical
     slab <- live volume through the warp field (K3) -> this slab's samples for the next frame.
-    With one rank it is the single-GPU frame."""
+    With one rank it is the single-GPU frame.
+    The deformation graph comes from outside (node_pos, node_w) or, with node_pos = node_w = None, from the loop's own
+    volume: integrate() the initial views, then construct_graph(radius)."""
 
     RELAX = 0.8          # default of step(relax=...): see there
     GLOBAL_ITERS = 2     # default of step(global_iters=...): rigid-mode steps in front of the node iterations
     GLOBAL_STRIDE = 4    # ... each fitted to every 4th 128-sample tile (step(global_stride=...))
+    has_graph = False    # set by the constructor (node_pos given) or by construct_graph()
 
     def __init__(self, K, scale, center, res, tdist_vox, node_pos, node_w, knn=4, pcg_iters=10, band=4.0, volume_dtype=torch.float32,
                  distributed=True, solve_mode="auto"):
@@ -183,19 +186,31 @@ class SlabFrame:
         # (replicated / undecided: the solver itself runs no collective; a decision for "sharded" switches it on)
         self.fs = FrameSolver(K, scale, center, R / 2, knn=knn, pcg_iters=pcg_iters,
                               distributed=self.distributed and self.ws > 1 and solve_mode == "sharded")
-        N = len(node_pos)
-        ident = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0, 0]), (N, 1))
-        self.fs.set_graph(node_pos, ident, node_w)
-        self.ws_dqb = kernels.dqb_workspace((R, R, R), (self.a, self.b), knn=knn, n_nodes=N)
+        if (node_pos is None) != (node_w is None):
+            raise ValueError("node_pos and node_w come together (both None: construct_graph() builds the graph)")
         self.ws_views = None                     # the multi-view dfh_integrate_depth's scratch (parameters + depth pyramids): sized on first use
         self._side = None                        # side stream of step(): the live-volume sweep beside the plan build
         self.updated = None                      # event recorded by step() right after the TSDF update
+        self.ws_dqb = None
         self.knn_bricks = None
-        if self.b > self.a:
-            kernels.dqb_build_candidates(self.ws_dqb, (R, R, R), node_pos, knn, (self.a, self.b))
-            self.knn_bricks = ((R, R, R), (self.a, self.b), self.ws_dqb)       # the samples' node search uses the same lists
         self._first = True
         self.ident_lw = np.array([1.0, 0, 0, 0, 0, 0, 0, 0])
+        self.has_graph = node_pos is not None    # False: everything that depends on the graph waits for construct_graph()
+        if self.has_graph:
+            N = len(node_pos)
+            ident = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0, 0]), (N, 1))
+            self.fs.set_graph(node_pos, ident, node_w)
+            self._graph_workspaces(node_pos, N)
+
+    def _graph_workspaces(self, node_pos, N):
+        """K3's workspace and the per-brick candidate lists for a graph of N nodes (the samples' node search uses the same lists)."""
+        R = self.R
+        self.ws_dqb = kernels.dqb_workspace((R, R, R), (self.a, self.b), knn=self.knn, n_nodes=N)
+        self.knn_bricks = None
+        if self.b > self.a:
+            kernels.dqb_build_candidates(self.ws_dqb, (R, R, R), node_pos, self.knn, (self.a, self.b))
+            self.knn_bricks = ((R, R, R), (self.a, self.b), self.ws_dqb)
+        self._first = True                               # K3 stores its per-voxel neighbourhoods again on the next call
 
     def integrate(self, depth, lw_cam):
         """Fuse a depth map into this rank's canonical slab (initial frames)."""
@@ -203,19 +218,72 @@ class SlabFrame:
         kernels.integrate_depth(self.T, self.Wt, depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.tdist_world,
                                 tsdf_res=R, res=(R, R, R), x_range=(self.a, self.b))
 
-    def refresh_samples(self):
-        """Samples of this slab.  Normals are central differences of T, also across the slab faces: the
-        neighbours' face planes come as a halo whose weight is 0 (they feed gradients, never samples), so the
-        union over ranks is exactly the whole-grid sample set."""
-        if self.ws == 1:
-            return self.fs.set_canonical(self.T, self.Wt, band=self.band, x0=self.a, knn_bricks=self.knn_bricks)
+    def _slab_with_halo(self):
+        """This rank's slab with its neighbours' face planes at weight 0 (see refresh_samples) -> (T, Wt, first global plane)."""
         lo, hi = self.D.halo_planes(self.T, self.R)
         Tp, Wp, x0 = [self.T], [self.Wt], self.a
         if lo is not None:
             Tp.insert(0, lo[None]); Wp.insert(0, torch.zeros_like(lo)[None]); x0 -= 1
         if hi is not None:
             Tp.append(hi[None]); Wp.append(torch.zeros_like(hi)[None])
-        Tp, Wp = torch.cat(Tp).contiguous(), torch.cat(Wp).contiguous()
+        return torch.cat(Tp).contiguous(), torch.cat(Wp).contiguous(), x0
+
+    def band_samples(self):
+        """The band samples of this rank's slab (positions in global index space, unit normals; CUDA fp64, voxel order): the
+        bare extraction of refresh_samples(), which needs no graph."""
+        if self.ws == 1:
+            return extract_surface_samples(self.T, self.Wt, self.band, x0=self.a)
+        Tp, Wp, x0 = self._slab_with_halo()
+        return extract_surface_samples(Tp, Wp, self.band, x0=x0)
+
+    @staticmethod
+    def _canonical_order(pts):
+        """Rows of a (n,3) tensor sorted by x, then y, then z -- np.lexsort((z, y, x)) as three stable sorts on the tensor's device."""
+        o = torch.sort(pts[:, 2], stable=True).indices
+        o = o[torch.sort(pts[o, 1], stable=True).indices]
+        o = o[torch.sort(pts[o, 0], stable=True).indices]
+        return pts[o]
+
+    def construct_graph(self, radius, sampler="device"):
+        """The deformation graph from the loop's own canonical volume (after the initial integrate() calls): the band samples of
+        all slabs, ordered canonically by position (so the graph does not depend on the slab partition), radius-subsampled
+        (graph.uniform_sample_device, or graph.uniform_sample with sampler="host": the same nodes) into nodes with identity
+        DQs and weight 2 * radius (core/fusion.py:116); the solver's graph, K3's workspace and candidate lists and the samples
+        are then set up as update_graph() does after an insertion.  Returns the node count."""
+        from . import graph as _graph
+        _graph._check_sampler(sampler)
+        radius = float(radius)
+        if not (np.isfinite(radius) and radius > 0):
+            raise ValueError("construct_graph needs a finite radius > 0")
+        pts, _ = self.band_samples()
+        if self.ws > 1:
+            pts = self.D.gather_rows(pts)
+        pts = self._canonical_order(pts)
+        if sampler == "device":
+            nodes, _ = _graph.uniform_sample_device(pts, radius)
+        else:
+            nodes, _ = _graph.uniform_sample(pts.cpu().numpy(), radius)
+            nodes = _graph._dev64(np.asarray(nodes, dtype=np.float64).reshape(-1, 3))
+        N = int(nodes.shape[0])
+        if N < self.knn:
+            raise ValueError("construct_graph: %d band samples gave %d nodes, fewer than knn = %d" % (pts.shape[0], N, self.knn))
+        ident = torch.zeros((N, 8), dtype=torch.float64, device="cuda")
+        ident[:, 0] = 1.0
+        self.fs.set_graph(nodes, ident, torch.full((N,), 2.0 * radius, dtype=torch.float64, device="cuda"))
+        self.has_graph = True
+        self._graph_workspaces(nodes, N)
+        self.refresh_samples()
+        return N
+
+    def refresh_samples(self):
+        """Samples of this slab.  Normals are central differences of T, also across the slab faces: the
+        neighbours' face planes come as a halo whose weight is 0 (they feed gradients, never samples), so the
+        union over ranks is exactly the whole-grid sample set."""
+        if not self.has_graph:
+            raise ValueError("no deformation graph yet: call construct_graph() first (band_samples() needs none)")
+        if self.ws == 1:
+            return self.fs.set_canonical(self.T, self.Wt, band=self.band, x0=self.a, knn_bricks=self.knn_bricks)
+        Tp, Wp, x0 = self._slab_with_halo()
         if self.solve_mode == "sharded":
             return self.fs.set_canonical(Tp, Wp, band=self.band, x0=x0, knn_bricks=self.knn_bricks)
         # replicated (or still to be decided): this slab's samples with their node tables, then all slabs' in rank order --
@@ -239,15 +307,20 @@ class SlabFrame:
                        weights=allp[:, 6:6 + k].contiguous())
         return int(allp.shape[0])
 
-    def update_graph(self, radius=None):
+    def update_graph(self, radius=None, sampler="host"):
         """Deformation-graph maintenance after a TSDF update (reference Fusion.update_graph, core/fusion.py:201-239) on the
         device path, with this loop's surface points -- the band samples of the canonical slab -- in the role of the mesh
         vertices: samples no node supports (min over their knn nodes of |node - p| / w >= 1) are radius-subsampled into new
         nodes whose DQs are the blend of the old graph at their positions; the solver's graph, K3's stored neighbourhoods
         and candidate lists and the samples' node table are rebuilt when nodes were inserted.  Every rank inserts the same
         nodes (the unsupported points are gathered in rank order before the greedy subsampling).  Returns the number of
-        inserted nodes.  radius defaults to half the nodes' weight (w = 2 radius, core/fusion.py:116)."""
+        inserted nodes.  radius defaults to half the nodes' weight (w = 2 radius, core/fusion.py:116).
+        sampler="device": the unsupported points stay on the device -- gathered over ranks as tensors, ordered by three stable
+        sorts, subsampled by graph.uniform_sample_device; the same nodes as with "host"."""
         from . import graph as _graph
+        _graph._check_sampler(sampler)
+        if not self.has_graph:
+            raise ValueError("no deformation graph yet: call construct_graph() first")
         sv = self.fs.solver
         if radius is None:
             radius = 0.5 * float(sv.node_w[0])
@@ -264,19 +337,18 @@ class SlabFrame:
             if len(uns) == 0:
                 return uns
             return uns[np.lexsort((uns[:, 2], uns[:, 1], uns[:, 0]))]
+
+        def canon_device(uns):
+            if gather is not None:
+                uns = self.D.gather_rows(uns)
+            return self._canonical_order(uns)
         vidx, P2, Q2, W2, lookup, n_new = _graph.update_graph_device(sv.node_pos, sv.node_dq, sv.node_w, pts, radius, self.knn,
-                                                                    gather_unsupported=canon)
+                                                                    gather_unsupported=canon_device if sampler == "device" else canon,
+                                                                    sampler=sampler)
         if n_new == 0:
             return 0
         self.fs.set_graph(P2, Q2, W2)                    # resets the block pattern; node-node table of the regulariser rebuilt
-        N = int(P2.shape[0])
-        R = self.R
-        self.ws_dqb = kernels.dqb_workspace((R, R, R), (self.a, self.b), knn=self.knn, n_nodes=N)
-        self.knn_bricks = None
-        if self.b > self.a:
-            kernels.dqb_build_candidates(self.ws_dqb, (R, R, R), P2, self.knn, (self.a, self.b))
-            self.knn_bricks = ((R, R, R), (self.a, self.b), self.ws_dqb)
-        self._first = True                               # K3 stores its per-voxel neighbourhoods again on the next call
+        self._graph_workspaces(P2, int(P2.shape[0]))
         self.refresh_samples()
         return n_new
 
@@ -299,7 +371,7 @@ class SlabFrame:
 
     def step(self, depth, lw_cam, gn_iters=10, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.5, stage_ms=None,
              update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None,
-             data_term="depth", global_built=None, update="volume", update_weight="node_distance"):
+             data_term="depth", global_built=None, update="volume", update_weight="node_distance", graph_sampler="host"):
         """update: how the canonical slab takes the frame in.  "volume" = the reference's two stages: the live volume fused from
         the depth maps (K1) is resampled through the warp field (K3, kernels.fuse_volume_dqb; the warp gathers across slab faces,
         so several ranks all-gather the live volume).  "depth" = DynamicFusion's surface fusion (K1w,
@@ -327,13 +399,18 @@ class SlabFrame:
         time (ms) is added under its name (for breakdowns only: the syncs cost throughput).
         on_updated: optional callable, called once the launches of this frame's TSDF update are queued and `self.updated` is
         recorded -- the place where a consumer of the updated canonical slab (mesh extraction on another stream) queues its
-        first launches, ahead of the sample refresh's."""
+        first launches, ahead of the sample refresh's.
+        graph_sampler: update_graph()'s `sampler` for update_graph=True."""
+        if graph_sampler not in ("host", "device"):              # (graph.SAMPLERS; read by update_graph=True only)
+            raise ValueError("graph_sampler must be 'host' or 'device', got %r" % (graph_sampler,))
         if data_term not in ("depth", "volume"):
             raise ValueError("data_term must be 'depth' or 'volume'")
         if update not in ("depth", "volume"):
             raise ValueError("update must be 'depth' or 'volume'")
         if update == "depth" and update_weight not in kernels.WARPED_WEIGHTS:
             raise ValueError("update_weight must be one of %s" % sorted(kernels.WARPED_WEIGHTS))
+        if not self.has_graph:
+            raise ValueError("no deformation graph yet: call construct_graph() first")
         need_live = update == "volume" or data_term == "volume"       # (update="depth" fuses the maps themselves)
         import time as _t
         t0 = [_t.perf_counter()]
@@ -441,7 +518,7 @@ class SlabFrame:
         mark("samples")
         self.fs.solver.check_status(completed_only=True)   # the sample count's read-back has synchronised: a timed-out PCG raises here
         if update_graph:
-            if self.update_graph():
+            if self.update_graph(sampler=graph_sampler):
                 n = self.fs.solver.S
             mark("graph")
         return n

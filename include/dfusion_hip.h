@@ -17,7 +17,8 @@
  *  - a volume's `dtype` / `depth_dtype`: DFH_F32 or DFH_F64. fp32 volumes are the product
  *    layout (16 B/voxel read-modify-write); fp64 volumes reproduce the reference's float64
  *    arrays bit for bit and exist for parity checking.
- *  - Calls are asynchronous on `stream` (a hipStream_t; NULL = default stream).
+ *  - Calls are asynchronous on `stream` (a hipStream_t; NULL = default stream); dfh_radius_sample, which drives its rounds
+ *    from the host, is the exception and says so.
  *  - Return value: 0 on success, <0 on error (DFH_E_*); dfh_last_error() describes the
  *    last failure on the calling thread.  Nothing throws across the ABI.
  */
@@ -41,6 +42,7 @@ extern "C" {
 #define DFH_E_HIP (-2)
 #define DFH_E_UNSUPPORTED (-3)
 #define DFH_E_TIMEOUT (-4)
+#define DFH_E_INTERNAL (-5)
 
 /* ABI version of the loaded library (== DFH_ABI_VERSION of the header it was built from). */
 int dfh_version(void);
@@ -283,7 +285,7 @@ int dfh_sample_knn_bricks(const double *sample_pos, int n_samples, const double 
 
 /* ---- deformation-graph maintenance: the device side of Fusion.update_graph / construct_graph ---------------------
  * (core/fusion.py:101-123, 201-239; the greedy radius subsampling of the unsupported vertices, core/util.py:27-47, is
- * sequential by definition and stays with the caller).
+ * dfh_radius_sample below).
  * dfh_nearest_points: idx_out[q] = nearest cloud point of query q (KDTree(cloud).query(q), :209-212 -- a node's anchor
  *   vertex; ties go to the lower index), d2_out (may be NULL) its squared distance.  A query that is not finite (no cloud
  *   point at a finite squared distance): idx_out = -1, d2_out = +inf.
@@ -296,6 +298,29 @@ int dfh_graph_unsupported(const double *verts, int n_verts, const int *nbr, int 
                           int n_nodes, unsigned char *flag_out, void *stream);
 int dfh_dq_blend_points(const double *points, int n_points, const int *nbr, int knn, const double *node_dq, const double *node_pos,
                         const double *node_w, int n_nodes, double *dq_out, void *stream);
+
+/* Greedy radius subsampling (core/util.py:27-47: take the first remaining candidate, drop every candidate closer than `radius`
+ * to it, repeat) of n_points fp64 points p_0 .. p_{n-1} (n_points x 3).  The selected set A is
+ *      i in A  <=>  no j < i with j in A and dist(p_i, p_j) < radius,
+ * the lexicographically first maximal independent set of the "closer than radius" graph, built in parallel rounds over a uniform
+ * cell table; it is the host loop's result index for index.  dist is computed operation by operation in fp64 with no
+ * contraction: d = p_i - p_j per component, s = (d0 d0 + d1 d1) + d2 d2, dist = sqrt(s) correctly rounded, and the comparison is
+ * strict: a point at distance exactly `radius` from a selected point is kept, duplicates of a selected point are dropped.
+ * idx_out (device, `capacity` int32): the min(count, capacity) lowest selected indices in ascending order, which is the order the
+ * host loop returns them in.  count_out, rounds_out: HOST pointers (rounds_out may be NULL): |A|, and the number of rounds run.
+ * workspace: dfh_radius_sample_workspace_bytes(n_points) bytes of device memory, 8-byte aligned; the size is a function of
+ * n_points only (the cell table is capped and the cells grow to fit the bounding box: a far outlier costs rounds, never memory).
+ * UNLIKE the other entry points this call does not only enqueue: it queues its rounds on `stream` a few at a time, synchronises
+ * `stream` in between to read how many points are still undecided, and has written count_out when it returns.  It cannot be
+ * captured into a graph.  At most n_points rounds run (every round decides at least the lowest undecided index); a round that
+ * decides nothing returns DFH_E_INTERNAL.
+ * n_points == 0: DFH_OK with count 0 before any launch.  DFH_E_BADARG before any HIP call: n_points < 0 or >= 2^31; radius not
+ * finite or <= 0; capacity < 0; null count_out; with n_points > 0 a null points, idx_out or workspace, or a workspace that is
+ * too small.  Coordinates that are not finite are the caller's error (the host loop never terminates on them); the call still
+ * terminates and touches no memory outside its arguments. */
+size_t dfh_radius_sample_workspace_bytes(long n_points);
+int dfh_radius_sample(const double *points, long n_points, double radius, int *idx_out, long capacity, long *count_out,
+                      int *rounds_out, void *workspace, size_t workspace_bytes, void *stream);
 
 /* out[i] = in[order[i]] for the four per-sample arrays at once (samples are sorted by node tuple before the build:
  * few runs per tile of dfh_gn_tile_samples() samples).  order: n_samples int64 indices, a permutation. */
