@@ -169,6 +169,11 @@ _SIGNATURES = {
                                  _dbl, _dbl, _vp, ctypes.c_size_t, _vp]),
     "dfh_render_resolve": (_int, [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _int, _c_double_p, _c_double_p, _int, _int, _dbl,
                                   _c_double_p, _dbl, _dbl, _vp, ctypes.c_size_t, _vp, _vp, _vp, _vp]),
+    "dfh_render_samples_workspace_bytes": (ctypes.c_size_t, [_int, _int, _int, _int]),
+    "dfh_render_samples_count": (_int, [_int, _int, _int, ctypes.c_long, _int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp]),
+    "dfh_render_samples_emit": (_int, [_vp, _vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _int, _c_double_p, _c_double_p, _int, _int, _dbl,
+                                       _c_double_p, _dbl, _dbl, _int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp, _vp,
+                                       ctypes.c_long, _vp]),
 }
 
 _lib = None

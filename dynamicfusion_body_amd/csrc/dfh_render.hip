@@ -12,6 +12,7 @@
 //                         million)
 //   render_resolve_kernel one lane per pixel: the key -> depth (-z, the reference's storage convention) and face id; the
 //                         normal is re-interpolated from the winning face (same arithmetic as the raster pass)
+//   samples_*_kernel     the visible-surface samples (dfh_render_samples_*): see below, behind the resolve pass
 // Everything that decides coverage and depth runs in fp64 with -ffp-contract=off, so the numpy restatement with the same
 // operation order gives the same bits.
 #include "dfh_common.h"
@@ -251,6 +252,243 @@ static int render_params(const char *who, int nv, const double *K, const double 
     return DFH_OK;
 }
 
+// ---- visible-surface samples: the rendered model as the warp solve's sample set (dfh_render_samples_*) ---------------------
+// Every `stride`-th pixel of every `stride`-th row (the "lattice", enumerated view-major, then y, then x) whose key is not
+// empty yields one sample: attributes of the CANONICAL mesh interpolated perspective-correctly at the pixel with the winning
+// face's weights.  Work decomposition (ordered, no atomics -- the pattern of dfh_extract.hip):
+//   samples_count_kernel     a workgroup counts the non-empty keys of its kSamplesPix lattice pixels
+//   samples_scan_kernel      a workgroup scans kSamplesChunk of those counts from zero and leaves the chunk's total
+//   samples_scan_top_kernel  ONE workgroup scans the chunk totals (64-bit) and stores the count (one plain store)
+//   samples_compact_kernel   pass A: the count pass's walk again; every sample learns its rank, the subsample rule picks its
+//                            slot, and the kept samples' pixel indices go out -- pixel_out is both a result and pass B's list
+//   samples_emit_kernel      pass B: one lane per KEPT sample over that dense list (full waves where a fifth of the image is
+//                            covered): key -> face, set-up and weights as in the resolve pass, nine vertex gathers, two rows out
+constexpr int kSamplesPix = 1024;     // lattice pixels per workgroup of the count / compact passes (256 lanes x 4)
+constexpr int kSamplesChunk = 1024;   // counts per workgroup of the scan (256 lanes x 4): a chunk's total is < 2^20, an int
+
+struct SampleLattice {
+    int stride, Hs, Ws, H, W;         // Hs = ceil(H / stride) rows of Ws = ceil(W / stride) lattice pixels per view
+    long nl;                          // lattice pixels of all views
+};
+
+// pixel index (view * H + y) * W + x of lattice pixel L < nl
+__device__ __forceinline__ long lattice_pixel(const SampleLattice &q, long L) {
+    if (q.stride == 1) return L;
+    long row, view;
+    int xs, ys;
+    if (q.nl < (1L << 32)) {          // (32-bit divisions where the images allow them)
+        const unsigned r = (unsigned)L / (unsigned)q.Ws, v = r / (unsigned)q.Hs;
+        xs = (int)((unsigned)L - r * (unsigned)q.Ws);
+        ys = (int)(r - v * (unsigned)q.Hs);
+        view = v;
+    } else {
+        row = L / q.Ws;
+        xs = (int)(L - row * q.Ws);
+        view = row / q.Hs;
+        ys = (int)(row - view * q.Hs);
+    }
+    return (view * q.H + (long)ys * q.stride) * q.W + (long)xs * q.stride;
+}
+
+__global__ __launch_bounds__(kRenderBlock) void samples_count_kernel(const unsigned long long *__restrict__ keys, SampleLattice q,
+                                                                     int *__restrict__ block_cnt) {
+    __shared__ int red[4];
+    // lane t takes lattice pixels t, t + 256, t + 512, t + 768 of the workgroup's 1 024: consecutive lanes, consecutive keys
+    const long L0 = (long)blockIdx.x * kSamplesPix + threadIdx.x;
+    int c = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long L = L0 + j * kRenderBlock;
+        if (L < q.nl && keys[lattice_pixel(q, L)] != kRenderEmpty) ++c;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o, 64);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) block_cnt[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// block_off[b] = samples of the workgroups of b's chunk in front of b; chunk_tot[chunk] = samples of the chunk
+__global__ __launch_bounds__(kRenderBlock) void samples_scan_kernel(const int *__restrict__ block_cnt, int nblocks, int *__restrict__ block_off,
+                                                                    long *__restrict__ chunk_tot) {
+    __shared__ int wtot[4];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const long base = (long)blockIdx.x * kSamplesChunk + 4 * (long)t;
+    int v[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) v[j] = base + j < nblocks ? block_cnt[base + j] : 0;
+    const int sum = (v[0] + v[1]) + (v[2] + v[3]);
+    int x = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) wtot[wv] = x;
+    __syncthreads();
+    int off = 0, all = 0;
+#pragma unroll
+    for (int w_ = 0; w_ < 4; ++w_) {
+        const int n = wtot[w_];
+        off += w_ < wv ? n : 0;
+        all += n;
+    }
+    const int ex = off + x - sum;
+    const int o4[4] = {ex, ex + v[0], ex + v[0] + v[1], ex + v[0] + v[1] + v[2]};
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+        if (base + j < nblocks) block_off[base + j] = o4[j];
+    if (t == 0) chunk_tot[blockIdx.x] = (long)all;
+}
+
+// chunk_base[c] = samples in front of chunk c, chunk_base[nchunks] = *total_out = all of them (256 chunks a round, in order)
+__global__ __launch_bounds__(kRenderBlock) void samples_scan_top_kernel(const long *__restrict__ chunk_tot, int nchunks, long *__restrict__ chunk_base,
+                                                                        long *__restrict__ total_out) {
+    __shared__ long wtot[4];
+    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    long carry = 0;
+    for (int first = 0; first < nchunks; first += kRenderBlock) {
+        const int i = first + t;
+        const long v = i < nchunks ? chunk_tot[i] : 0;
+        long x = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wtot[wv] = x;
+        __syncthreads();
+        long off = 0, all = 0;
+#pragma unroll
+        for (int w_ = 0; w_ < 4; ++w_) {
+            const long n = wtot[w_];
+            off += w_ < wv ? n : 0;
+            all += n;
+        }
+        if (i < nchunks) chunk_base[i] = carry + off + x - v;
+        carry += all;
+        __syncthreads();                                 // wtot is rewritten by the next round
+    }
+    if (t == 0) {
+        chunk_base[nchunks] = carry;
+        *total_out = carry;
+    }
+}
+
+__global__ __launch_bounds__(kRenderBlock) void samples_compact_kernel(const unsigned long long *__restrict__ keys, SampleLattice q,
+                                                                       const int *__restrict__ block_cnt, const int *__restrict__ block_off,
+                                                                       const long *__restrict__ chunk_base, int nchunks, long capacity,
+                                                                       long *__restrict__ pixel_out) {
+    __shared__ int wave_cnt[4][4];                       // [round j][wave]: samples of lattice pixels j * 256 + 64 * wave .. + 63
+    if (block_cnt[blockIdx.x] == 0) return;              // nothing covered here: do not re-read the keys
+    const long L0 = (long)blockIdx.x * kSamplesPix + threadIdx.x;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    long pix[4];
+    bool ok[4];
+    int before[4];                                       // samples of lower lanes of this wave in round j
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long L = L0 + j * kRenderBlock;
+        pix[j] = L < q.nl ? lattice_pixel(q, L) : 0;
+        ok[j] = L < q.nl && keys[pix[j]] != kRenderEmpty;
+        const unsigned long long m = __ballot(ok[j]);
+        before[j] = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_cnt[j][wv] = __popcll(m);
+    }
+    __syncthreads();
+    long at = chunk_base[blockIdx.x / kSamplesChunk] + (long)block_off[blockIdx.x];
+    const long total = chunk_base[nchunks];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        long mine = at + before[j];
+        for (int w_ = 0; w_ < 4; ++w_) {
+            if (w_ < wv) mine += wave_cnt[j][w_];
+            at += wave_cnt[j][w_];                       // after the loop: start of round j + 1
+        }
+        // capacity < total: dfh_surface_emit's EVEN subsample -- sample i goes to slot floor(i * capacity / total) and is kept
+        // iff it is the first one of its slot (every slot gets exactly one)
+        long dst = mine;
+        bool keep = ok[j];
+        if (capacity < total) {
+            dst = (long)(((__int128)mine * capacity) / total);
+            keep = keep && (mine == 0 || (long)(((__int128)(mine - 1) * capacity) / total) != dst);
+        }
+        if (keep) pixel_out[dst] = pix[j];               // (dst < min(total, capacity): mine < total)
+    }
+}
+
+__global__ __launch_bounds__(kRenderBlock) void samples_emit_kernel(const double *__restrict__ verts, const double *__restrict__ canon_pos,
+                                                                    const double *__restrict__ canon_nrm, const int *__restrict__ faces,
+                                                                    RenderParams p, const unsigned long long *__restrict__ keys,
+                                                                    const long *__restrict__ chunk_base, int nchunks, long capacity,
+                                                                    const long *__restrict__ pixel, double *__restrict__ pos_out,
+                                                                    double *__restrict__ nrm_out) {
+    const long i = (long)blockIdx.x * kRenderBlock + threadIdx.x;
+    const long total = chunk_base[nchunks];
+    if (i >= (capacity < total ? capacity : total)) return;
+    const long hw = (long)p.H * p.W, pi = pixel[i];
+    const long f = (long)(unsigned)(keys[pi] & 0xFFFFFFFFull);
+    const int view = (int)(pi / hw);
+    const long rem = pi - (long)view * hw;
+    const int y = (int)(rem / p.W), x = (int)(rem - (long)y * p.W);
+    Tri t;
+    double l[3];
+    double o[3] = {0.0, 0.0, 0.0}, n[3] = {0.0, 0.0, 0.0};
+    // (always true with the raster call's mesh and views: this face wrote the key; another mesh gets zeros, not a wild read)
+    if (f < p.nfaces && render_setup(p, p.view[view], verts, faces, f, t) && render_bary(t, x, y, l)) {
+        const double a0 = l[0] / t.z[0], a1 = l[1] / t.z[1], a2 = l[2] / t.z[2];
+        const double s = (a0 + a1) + a2;
+        const double b0 = a0 / s, b1 = a1 / s, b2 = a2 / s;
+        const size_t i0 = 3 * (size_t)faces[3 * f], i1 = 3 * (size_t)faces[3 * f + 1], i2 = 3 * (size_t)faces[3 * f + 2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) o[c] = (b0 * canon_pos[i0 + c] + b1 * canon_pos[i1 + c]) + b2 * canon_pos[i2 + c];
+        if (nrm_out) {
+            double m[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] = (b0 * canon_nrm[i0 + c] + b1 * canon_nrm[i1 + c]) + b2 * canon_nrm[i2 + c];
+            const double len = sqrt((m[0] * m[0] + m[1] * m[1]) + m[2] * m[2]);
+            if (len > 0.0 && isfinite(len)) { n[0] = m[0] / len; n[1] = m[1] / len; n[2] = m[2] / len; }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) pos_out[3 * i + c] = o[c];
+    if (nrm_out) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) nrm_out[3 * i + c] = n[c];
+    }
+}
+
+struct SamplesWorkspace {
+    int *block_cnt, *block_off;
+    long *chunk_tot, *chunk_base;
+    long nblocks, nchunks;
+    size_t bytes;
+};
+
+static bool samples_lattice(int nv, int H, int W, int stride, SampleLattice &q) {
+    if (!(nv >= 1 && nv <= kRenderMaxViews && H >= 1 && W >= 1 && stride >= 1 && (long)nv * H * W < (1L << 38))) return false;
+    q.stride = stride; q.H = H; q.W = W;
+    q.Hs = (H - 1) / stride + 1;
+    q.Ws = (W - 1) / stride + 1;
+    q.nl = (long)nv * q.Hs * q.Ws;
+    return true;
+}
+
+static SamplesWorkspace samples_workspace(const SampleLattice &q, void *base) {
+    SamplesWorkspace w;
+    w.nblocks = (q.nl + kSamplesPix - 1) / kSamplesPix;                  // < 2^28
+    w.nchunks = (w.nblocks + kSamplesChunk - 1) / kSamplesChunk;
+    size_t off = 0;
+    char *b = static_cast<char *>(base);
+    auto take = [&](size_t n) { char *r = b ? b + off : nullptr; off += (n + 15) & ~(size_t)15; return r; };
+    w.block_cnt = reinterpret_cast<int *>(take((size_t)w.nblocks * sizeof(int)));
+    w.block_off = reinterpret_cast<int *>(take((size_t)w.nblocks * sizeof(int)));
+    w.chunk_tot = reinterpret_cast<long *>(take((size_t)w.nchunks * sizeof(long)));
+    w.chunk_base = reinterpret_cast<long *>(take((size_t)(w.nchunks + 1) * sizeof(long)));
+    w.bytes = off;
+    return w;
+}
+
 }  // namespace dfh
 
 extern "C" {
@@ -306,6 +544,69 @@ int dfh_render_resolve(const double *verts, const double *normals, long n_verts,
     const long npix = (long)n_views * H * W;
     hipLaunchKernelGGL(render_resolve_kernel, dim3((unsigned)((npix + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0,
                        (hipStream_t)stream, verts, normals, faces, p, w.keys, depth_out, face_out, normal_out);
+    DFH_HIP_CHECK(hipGetLastError());
+    return DFH_OK;
+}
+
+size_t dfh_render_samples_workspace_bytes(int n_views, int H, int W, int stride) {
+    using namespace dfh;
+    SampleLattice q;
+    if (!samples_lattice(n_views, H, W, stride, q)) return 0;
+    return samples_workspace(q, nullptr).bytes;
+}
+
+int dfh_render_samples_count(int n_views, int H, int W, long n_faces, int stride, const void *workspace, size_t workspace_bytes,
+                             void *scan_workspace, size_t scan_workspace_bytes, long *total_out, void *stream) {
+    using namespace dfh;
+    SampleLattice q;
+    DFH_REQUIRE(render_sizes_ok(n_views, H, W, n_faces), "dfh_render_samples_count: bad sizes (views %d in [1, %d], H %d, W %d, faces %ld)",
+                n_views, kRenderMaxViews, H, W, n_faces);
+    DFH_REQUIRE(stride >= 1 && samples_lattice(n_views, H, W, stride, q), "dfh_render_samples_count: stride %d must be >= 1", stride);
+    DFH_REQUIRE(workspace && scan_workspace && total_out, "dfh_render_samples_count: null pointer");
+    DFH_REQUIRE(workspace_bytes >= dfh_render_workspace_bytes(n_views, H, W, n_faces), "dfh_render_samples_count: workspace too small");
+    DFH_REQUIRE(scan_workspace_bytes >= dfh_render_samples_workspace_bytes(n_views, H, W, stride),
+                "dfh_render_samples_count: scan workspace too small");
+    const RenderWorkspace w = render_workspace(n_views, H, W, n_faces, const_cast<void *>(workspace));
+    const SamplesWorkspace sw = samples_workspace(q, scan_workspace);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(samples_count_kernel, dim3((unsigned)sw.nblocks), dim3(kRenderBlock), 0, s, w.keys, q, sw.block_cnt);
+    hipLaunchKernelGGL(samples_scan_kernel, dim3((unsigned)sw.nchunks), dim3(kRenderBlock), 0, s, (const int *)sw.block_cnt, (int)sw.nblocks,
+                       sw.block_off, sw.chunk_tot);
+    hipLaunchKernelGGL(samples_scan_top_kernel, dim3(1), dim3(kRenderBlock), 0, s, (const long *)sw.chunk_tot, (int)sw.nchunks, sw.chunk_base,
+                       total_out);
+    DFH_HIP_CHECK(hipGetLastError());
+    return DFH_OK;
+}
+
+int dfh_render_samples_emit(const double *verts, const double *canon_pos, const double *canon_nrm, long n_verts, const int *faces,
+                            long n_faces, int n_views, const double *K, const double *lw, int H, int W, double scale, const double center[3],
+                            double half, double znear, int stride, const void *workspace, size_t workspace_bytes,
+                            const void *scan_workspace, size_t scan_workspace_bytes, double *pos_out, double *nrm_out, long *pixel_out,
+                            long capacity, void *stream) {
+    using namespace dfh;
+    RenderParams p;
+    SampleLattice q;
+    const int rc = render_params("dfh_render_samples_emit", n_views, K, lw, H, W, n_verts, n_faces, scale, center, half, znear, p);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(stride >= 1 && samples_lattice(n_views, H, W, stride, q), "dfh_render_samples_emit: stride %d must be >= 1", stride);
+    DFH_REQUIRE(capacity >= 0, "dfh_render_samples_emit: capacity %ld < 0", capacity);
+    DFH_REQUIRE(workspace && scan_workspace, "dfh_render_samples_emit: null workspace");
+    DFH_REQUIRE(workspace_bytes >= dfh_render_workspace_bytes(n_views, H, W, n_faces), "dfh_render_samples_emit: workspace too small");
+    DFH_REQUIRE(scan_workspace_bytes >= dfh_render_samples_workspace_bytes(n_views, H, W, stride),
+                "dfh_render_samples_emit: scan workspace too small");
+    DFH_REQUIRE(n_faces == 0 || (faces && verts && canon_pos), "dfh_render_samples_emit: null mesh");
+    DFH_REQUIRE(canon_nrm || !nrm_out, "dfh_render_samples_emit: a normal output needs canon_nrm");
+    if (capacity == 0 || n_faces == 0) return DFH_OK;                 // (no faces: nothing is covered, no row is written)
+    DFH_REQUIRE(pos_out && pixel_out, "dfh_render_samples_emit: null output");
+    const RenderWorkspace w = render_workspace(n_views, H, W, n_faces, const_cast<void *>(workspace));
+    const SamplesWorkspace sw = samples_workspace(q, const_cast<void *>(scan_workspace));
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(samples_compact_kernel, dim3((unsigned)sw.nblocks), dim3(kRenderBlock), 0, s, (const unsigned long long *)w.keys, q,
+                       (const int *)sw.block_cnt, (const int *)sw.block_off, (const long *)sw.chunk_base, (int)sw.nchunks, capacity, pixel_out);
+    const long rows = capacity < q.nl ? capacity : q.nl;               // (the count stays on the device: lanes beyond it return)
+    hipLaunchKernelGGL(samples_emit_kernel, dim3((unsigned)((rows + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, verts,
+                       canon_pos, canon_nrm, faces, p, (const unsigned long long *)w.keys, (const long *)sw.chunk_base, (int)sw.nchunks,
+                       capacity, (const long *)pixel_out, pos_out, nrm_out);
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;
 }

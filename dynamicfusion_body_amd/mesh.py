@@ -157,6 +157,35 @@ class render_workspace:
         self.buf = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=device or "cuda")
 
 
+def _rows3(a, what, dev):
+    """(n,3) numpy array or tensor -> contiguous fp64 tensor on `dev`."""
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
+    t = t.to(device=dev, dtype=torch.float64).contiguous()
+    if t.dim() != 2 or t.shape[1] != 3:
+        raise ValueError("%s must be (n,3), got shape %s" % (what, tuple(t.shape)))
+    return t
+
+
+def _render_args(verts, faces, K, lws, H, W, scale, center, half, znear, workspace):
+    """What render and render_samples share: the arguments checked and on the device.  Returns (dev, V, F, mesh, views,
+    workspace) with mesh = (verts pointer, n_verts, faces pointer, n_faces) and views = (n_views, K, lw, H, W, scale, center, half,
+    znear, workspace pointer, workspace bytes) as the dfh_render_* calls take them."""
+    Kf, lwf, nv = _view_table(K, lws)
+    H, W = int(H), int(W)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    V = _rows3(verts, "verts", dev)
+    F = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(faces)))
+    F = F.to(device=dev, dtype=torch.int32).contiguous()
+    if F.dim() != 2 or F.shape[1] != 3:
+        raise ValueError("faces must be (n,3), got shape %s" % (tuple(F.shape),))
+    ctr = np.broadcast_to(np.asarray(center, dtype=np.float64), (3,))
+    if workspace is None:
+        workspace = render_workspace(nv, H, W, F.shape[0], dev)
+    views = (nv, _lib.darr(Kf, 9 * nv), _lib.darr(lwf, 12 * nv), H, W, float(scale), _lib.darr(ctr, 3), float(half), float(znear),
+             workspace.buf.data_ptr(), workspace.buf.numel() * 8)
+    return dev, V, F, (V.data_ptr(), V.shape[0], F.data_ptr(), F.shape[0]), views, workspace
+
+
 def render(verts, faces, normals, K, lws, H, W, scale=1.0, center=0.0, half=0.0, znear=1e-3, workspace=None, stages=None):
     """Rasterise one triangle mesh into V views (csrc/dfh_render.hip, semantics in include/dfusion_hip.h): vertices (N,3) in
     voxel-index space, world = scale * (p - half) + center (K1's voxel -> world map), `lws` one 3x4 world->camera matrix or a list
@@ -166,42 +195,63 @@ def render(verts, faces, normals, K, lws, H, W, scale=1.0, center=0.0, half=0.0,
     (for timing tools)."""
     require_gpu()
     lib = _lib.load()
-    Kf, lwf, nv = _view_table(K, lws)
-    H, W = int(H), int(W)
-    dev = torch.device("cuda", torch.cuda.current_device())
-
-    def f64(a, what):
-        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=np.float64)))
-        t = t.to(device=dev, dtype=torch.float64).contiguous()
-        if t.dim() != 2 or t.shape[1] != 3:
-            raise ValueError("%s must be (n,3), got shape %s" % (what, tuple(t.shape)))
-        return t
-    V = f64(verts, "verts")
-    Nn = None if normals is None else f64(normals, "normals")
+    dev, V, F, msh, views, workspace = _render_args(verts, faces, K, lws, H, W, scale, center, half, znear, workspace)
+    nv, H, W = views[0], views[3], views[4]
+    Nn = None if normals is None else _rows3(normals, "normals", dev)
     if Nn is not None and Nn.shape[0] != V.shape[0]:
         raise ValueError("normals and verts disagree in length")
-    F = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(faces)))
-    F = F.to(device=dev, dtype=torch.int32).contiguous()
-    if F.dim() != 2 or F.shape[1] != 3:
-        raise ValueError("faces must be (n,3), got shape %s" % (tuple(F.shape),))
-    ctr = np.broadcast_to(np.asarray(center, dtype=np.float64), (3,))
-    if workspace is None:
-        workspace = render_workspace(nv, H, W, F.shape[0], dev)
     depth = torch.empty((nv, H, W), dtype=torch.float32, device=dev)
     face = torch.empty((nv, H, W), dtype=torch.int32, device=dev)
     normal = None if Nn is None else torch.empty((nv, H, W, 3), dtype=torch.float32, device=dev)
-    Ka, La, Ca = _lib.darr(Kf, 9 * nv), _lib.darr(lwf, 12 * nv), _lib.darr(ctr, 3)
-    ws, nbytes = workspace.buf.data_ptr(), workspace.buf.numel() * 8
-    _lib.check(lib.dfh_render_raster(V.data_ptr(), V.shape[0], F.data_ptr(), F.shape[0], nv, Ka, La, H, W, float(scale), Ca, float(half),
-                                     float(znear), ws, nbytes, current_stream_ptr()), "dfh_render_raster")
+    _lib.check(lib.dfh_render_raster(*msh, *views, current_stream_ptr()), "dfh_render_raster")
     if stages is not None:
         stages("raster")
-    _lib.check(lib.dfh_render_resolve(V.data_ptr(), 0 if Nn is None else Nn.data_ptr(), V.shape[0], F.data_ptr(), F.shape[0], nv, Ka, La,
-                                      H, W, float(scale), Ca, float(half), float(znear), ws, nbytes, depth.data_ptr(), face.data_ptr(),
+    _lib.check(lib.dfh_render_resolve(V.data_ptr(), 0 if Nn is None else Nn.data_ptr(), *msh[1:], *views, depth.data_ptr(), face.data_ptr(),
                                       0 if normal is None else normal.data_ptr(), current_stream_ptr()), "dfh_render_resolve")
     if stages is not None:
         stages("resolve")
     return depth, normal, face
+
+
+def render_samples(verts, faces, canon_pos, canon_nrm, K, lws, H, W, scale=1.0, center=0.0, half=0.0, znear=1e-3, stride=1,
+                   max_samples=None, workspace=None):
+    """Visible-surface samples of one triangle mesh in V views (csrc/dfh_render.hip, semantics in include/dfusion_hip.h,
+    dfh_render_samples_*): the mesh `verts` / `faces` is rasterised as by `render` (same arguments), and every `stride`-th pixel
+    of every `stride`-th row that it covers yields one sample -- the per-vertex attributes `canon_pos` and `canon_nrm` ((N,3), the
+    canonical mesh where `verts` is its warped copy; canon_nrm may be None) interpolated perspective-correctly at the pixel with
+    the visible face's weights, the normal renormalised.  Samples come in view-major, then row, then column order.
+    max_samples < the number of covered lattice pixels keeps extract_surface_samples' even subsample, never a prefix.
+    Returns (pos (S,3) fp64, nrm (S,3) fp64 or None, pixel (S,) int64 = (view * H + y) * W + x) as CUDA tensors.  The raster pass,
+    the count, one 8-byte read-back of the count, the emit pass."""
+    require_gpu()
+    lib = _lib.load()
+    stride = int(stride)
+    if stride < 1:
+        raise ValueError("stride must be >= 1, got %d" % stride)
+    if max_samples is not None and int(max_samples) < 0:
+        raise ValueError("max_samples must be >= 0, got %d" % int(max_samples))
+    dev, V, F, msh, views, workspace = _render_args(verts, faces, K, lws, H, W, scale, center, half, znear, workspace)
+    nv, H, W = views[0], views[3], views[4]
+    P = _rows3(canon_pos, "canon_pos", dev)
+    Nn = None if canon_nrm is None else _rows3(canon_nrm, "canon_nrm", dev)
+    if P.shape[0] != V.shape[0] or (Nn is not None and Nn.shape[0] != V.shape[0]):
+        raise ValueError("canon_pos / canon_nrm and verts disagree in length")
+    _lib.check(lib.dfh_render_raster(*msh, *views, current_stream_ptr()), "dfh_render_raster")
+    sbytes = lib.dfh_render_samples_workspace_bytes(nv, H, W, stride)
+    scan_buf = torch.empty((sbytes + 7) // 8, dtype=torch.int64, device=dev)
+    scan = (scan_buf.data_ptr(), scan_buf.numel() * 8)
+    total = HostScalar(torch.int64)                    # (the last scan launch stores the count straight into pinned host memory)
+    _lib.check(lib.dfh_render_samples_count(nv, H, W, F.shape[0], stride, *views[-2:], *scan, total.ptr(), current_stream_ptr()),
+               "dfh_render_samples_count")
+    n = total.get()
+    cap = n if max_samples is None else min(n, int(max_samples))
+    pos = torch.empty((cap, 3), dtype=torch.float64, device=dev)
+    nrm = None if Nn is None else torch.empty((cap, 3), dtype=torch.float64, device=dev)
+    pixel = torch.empty((cap,), dtype=torch.int64, device=dev)
+    _lib.check(lib.dfh_render_samples_emit(V.data_ptr(), P.data_ptr(), 0 if Nn is None else Nn.data_ptr(), *msh[1:], *views[:-2], stride,
+                                           *views[-2:], *scan, pos.data_ptr(), 0 if nrm is None else nrm.data_ptr(), pixel.data_ptr(), cap,
+                                           current_stream_ptr()), "dfh_render_samples_emit")
+    return pos, nrm, pixel
 
 
 def depth_error(rendered, observed, gate):

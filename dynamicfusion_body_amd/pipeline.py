@@ -155,6 +155,8 @@ class SlabFrame:
     GLOBAL_ITERS = 2     # default of step(global_iters=...): rigid-mode steps in front of the node iterations
     GLOBAL_STRIDE = 4    # ... each fitted to every 4th 128-sample tile (step(global_stride=...))
     has_graph = False    # set by the constructor (node_pos given) or by construct_graph()
+    SAMPLE_SOURCES = ("band", "visible")
+    sample_source = "band"   # set_sample_source(): where refresh_samples() takes the solve's samples from
 
     def __init__(self, K, scale, center, res, tdist_vox, node_pos, node_w, knn=4, pcg_iters=10, band=4.0, volume_dtype=torch.float32,
                  distributed=True, solve_mode="auto"):
@@ -281,6 +283,12 @@ class SlabFrame:
         union over ranks is exactly the whole-grid sample set."""
         if not self.has_graph:
             raise ValueError("no deformation graph yet: call construct_graph() first (band_samples() needs none)")
+        if self.sample_source == "visible":
+            # the rendered model is the sample set (set_sample_source); none visible is a valid state: S = 0, the solve a no-op
+            pos, nrm, _ = self.visible_samples(self._src_lws, self._src_size[0], self._src_size[1], stride=self._src_stride,
+                                               max_samples=self._src_max)
+            self.fs.solver.set_samples(pos, nrm, knn_bricks=self.knn_bricks)
+            return int(pos.shape[0])
         if self.ws == 1:
             return self.fs.set_canonical(self.T, self.Wt, band=self.band, x0=self.a, knn_bricks=self.knn_bricks)
         Tp, Wp, x0 = self._slab_with_halo()
@@ -324,7 +332,10 @@ class SlabFrame:
         sv = self.fs.solver
         if radius is None:
             radius = 0.5 * float(sv.node_w[0])
-        pts = sv.spos if sv.S > 0 else torch.zeros((0, 3), dtype=torch.float64, device="cuda")
+        if self.sample_source == "band":
+            pts = sv.spos if sv.S > 0 else torch.zeros((0, 3), dtype=torch.float64, device="cuda")
+        else:                                            # the graph must not grow by what the cameras happen to see: the band
+            pts, _ = self.band_samples()                 # samples (construct_graph's points), which the solver does not hold now
         gather = None
         if self.ws > 1 and self.solve_mode == "sharded":         # (replicated: every rank already holds every sample)
             def gather(uns):                             # (ragged all-gather on one device: dist.gather_rows)
@@ -368,6 +379,52 @@ class SlabFrame:
             verts, normals = warp_points(verts, normals, self.ident_lw, nbr=nbr, node_dq=sv.node_dq, node_pos=sv.node_pos,
                                          node_w=sv.node_w)
         return _mesh.render(verts, faces, normals, self.K, lws, H, W, scale=self.scale, center=self.center, half=self.R / 2)
+
+    def visible_samples(self, lws, H, W, stride=1, max_samples=None):
+        """The visible-surface samples of the loop's current live model in the views `lws`: render_live's mesh, warp and
+        K / scale / center / half -- marching cubes of T at level 0, warped by the solver's node field, rasterised -- and, for every
+        `stride`-th covered pixel of every `stride`-th row, the UNWARPED vertices and normals interpolated at the pixel
+        (mesh.render_samples): the canonical point and normal of the surface a camera sees there, DynamicFusion's model-to-frame
+        sample.  Returns (pos (S,3), nrm (S,3), pixel (S,)), view-major in pixel order.  Single rank only, as render_live."""
+        if self.ws > 1:
+            raise ValueError("visible_samples renders one rank's whole grid; the %d-rank slab partition is not supported" % self.ws)
+        if not self.has_graph:
+            raise ValueError("no deformation graph yet: call construct_graph() first")
+        from . import mesh as _mesh
+        verts, faces, normals, _ = _mesh.marching_cubes(self.T, 0.0, 1)
+        sv = self.fs.solver
+        warped = verts
+        if verts.shape[0] > 0:
+            nbr, _ = sample_knn(verts, sv.node_pos, sv.node_w, self.knn)
+            warped, _ = warp_points(verts, normals, self.ident_lw, nbr=nbr, node_dq=sv.node_dq, node_pos=sv.node_pos,
+                                    node_w=sv.node_w)
+        return _mesh.render_samples(warped, faces, verts, normals, self.K, lws, H, W, scale=self.scale, center=self.center,
+                                    half=self.R / 2, stride=stride, max_samples=max_samples)
+
+    def set_sample_source(self, source, lws=None, size=None, stride=1, max_samples=None):
+        """Where refresh_samples() -- and so the end of every step() -- takes the solve's samples from.  "band" (the default):
+        every band voxel of the canonical slab (extract_surface_samples).  "visible": visible_samples(lws, size[0], size[1],
+        stride, max_samples), the model rendered into the views `lws` of size = (H, W); step() then replaces views and size by
+        each frame's own cameras and depth-map size, so the model as that frame updated and warped it is what the next frame's
+        solve sees.  With a graph in place the samples are refreshed at once.  Graph construction and growth keep using the band
+        samples whatever the source.  Single rank only for "visible"."""
+        if source not in self.SAMPLE_SOURCES:
+            raise ValueError("sample source must be one of %s, got %r" % (self.SAMPLE_SOURCES, source))
+        stride = int(stride)
+        if stride < 1:
+            raise ValueError("stride must be >= 1, got %d" % stride)
+        if source == "visible":
+            if lws is None or size is None:
+                raise ValueError("the visible sample source needs its views (lws) and their size (H, W)")
+            if self.ws > 1:
+                raise ValueError("the visible sample source renders one rank's whole grid; %d ranks are not supported" % self.ws)
+            H, W = (int(x) for x in size)
+            self._src_lws, self._src_size = lws, (H, W)
+        self._src_stride = stride
+        self._src_max = None if max_samples is None else int(max_samples)
+        self.sample_source = source
+        if self.has_graph:
+            self.refresh_samples()
 
     def step(self, depth, lw_cam, gn_iters=10, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.5, stage_ms=None,
              update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None,
@@ -514,6 +571,8 @@ class SlabFrame:
         if on_updated is not None:             # stream, e.g. mesh extraction, need not wait for the sample refresh below)
             on_updated()
         mark("tsdf_update")
+        if self.sample_source == "visible":              # this frame's cameras and map size: the prediction for the next frame
+            self._src_lws, self._src_size = lw_list, (int(depth.shape[0]), int(depth.shape[1]))
         n = self.refresh_samples()
         mark("samples")
         self.fs.solver.check_status(completed_only=True)   # the sample count's read-back has synchronised: a timed-out PCG raises here

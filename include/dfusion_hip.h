@@ -681,6 +681,44 @@ int dfh_render_resolve(const double *verts, const double *normals, long n_verts,
                        const double *K, const double *lw, int H, int W, double scale, const double center[3], double half, double znear,
                        const void *workspace, size_t workspace_bytes, float *depth_out, int *face_out, float *normal_out, void *stream);
 
+/* ---- visible-surface samples: the rendered model as the warp solve's sample set (no reference counterpart) --------------
+ * DynamicFusion's data term is model-to-frame: every pixel the rendered (warped) model covers gives one point-to-plane row,
+ * the CANONICAL point and normal of the surface visible there.  After dfh_render_raster (no resolve pass is needed: only the
+ * key buffer of `workspace` and the mesh are read) these calls turn the covered pixels into samples.  verts / faces / views /
+ * H / W / scale / center / half / znear are the raster call's; canon_pos and canon_nrm (n_verts x 3 fp64) are per-vertex
+ * attributes of the canonical mesh (the unwarped vertices and normals; any arrays will do).  Semantics (restated in numpy by
+ * tests/render_samples_np.py; everything in fp64, no fused multiply-add, operations in the order written):
+ *  - Lattice pixels: (view, y, x) with x % stride == 0 and y % stride == 0 (stride >= 1), enumerated view-major, then y,
+ *    then x.  A lattice pixel yields a sample iff its key is not the empty key; `total` is the number of such pixels.
+ *  - Weights: f = the low 32 bits of the key; lambda_i, z_i = the rasterizer's barycentric weights and vertex depths of
+ *    face f in that view at (x, y) (the set-up and edge values above); a_i = lambda_i / z_i; s = (a0 + a1) + a2;
+ *    b_i = a_i / s.
+ *  - pos[c] = (b0 P0[c] + b1 P1[c]) + b2 P2[c] with P_i the rows of canon_pos at the face's vertices.
+ *  - m[c] = (b0 N0[c] + b1 N1[c]) + b2 N2[c] likewise from canon_nrm; len = sqrt((m0 m0 + m1 m1) + m2 m2);
+ *    nrm = m / len if len > 0 and finite, else (0, 0, 0).  canon_nrm and nrm_out may both be NULL (nrm_out without canon_nrm:
+ *    DFH_E_BADARG).
+ *  - pixel (int64) = (view * H + y) * W + x.
+ *  - Samples come out in lattice order, deterministically (per-workgroup counts, an exclusive scan, ordered emission: no
+ *    atomics).  capacity < total: dfh_surface_emit's even subsample -- sample i is kept iff it is the first with slot
+ *    floor(i * capacity / total), and stored in that slot; never a prefix.  Rows at and beyond min(total, capacity) are not
+ *    written; nothing covered (or n_faces == 0): DFH_OK, count 0, no row written.
+ *   dfh_render_samples_count : fills `scan_workspace` (dfh_render_samples_workspace_bytes(n_views, H, W, stride) bytes; 0 for
+ *                              bad sizes) from the keys; *total_out = total by ONE plain store of the last launch (device or
+ *                              pinned host memory, like dfh_surface_count's)
+ *   dfh_render_samples_emit  : pos_out / nrm_out (capacity x 3 fp64) and pixel_out (capacity int64), after the count call
+ *                              with the same workspaces and stride.  pixel_out is written first and read back as the list of
+ *                              kept samples: one lane per kept sample computes the rows.
+ * Both only enqueue on `stream`.  DFH_E_BADARG before any HIP call: null required pointers, stride < 1, sizes the render
+ * calls refuse, capacity < 0, a workspace smaller than its size query. */
+size_t dfh_render_samples_workspace_bytes(int n_views, int H, int W, int stride);
+int dfh_render_samples_count(int n_views, int H, int W, long n_faces, int stride, const void *workspace, size_t workspace_bytes,
+                             void *scan_workspace, size_t scan_workspace_bytes, long *total_out, void *stream);
+int dfh_render_samples_emit(const double *verts, const double *canon_pos, const double *canon_nrm, long n_verts, const int *faces,
+                            long n_faces, int n_views, const double *K, const double *lw, int H, int W, double scale, const double center[3],
+                            double half, double znear, int stride, const void *workspace, size_t workspace_bytes,
+                            const void *scan_workspace, size_t scan_workspace_bytes, double *pos_out, double *nrm_out, long *pixel_out,
+                            long capacity, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
