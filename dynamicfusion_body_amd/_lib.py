@@ -79,6 +79,14 @@ class Nodes(ctypes.Structure):
     _fields_ = [("pos", _vp), ("dq", _vp), ("w", _vp), ("n_nodes", _int), ("knn", _int)]
 
 
+class DepthPrepParams(ctypes.Structure):
+    """dfh_depth_prep_params: the maps, camera, filter tables and thresholds of one dfh_depth_prep call (depth: a host array the
+    caller keeps alive; spatial, range_lut: device float32)."""
+    _fields_ = [("n_views", _int), ("depth", ctypes.POINTER(_vp)), ("depth_dtype", _int), ("H", _int), ("W", _int),
+                ("Kinv", _dbl * 9), ("radius", _int), ("spatial", _vp), ("range_lut", _vp), ("n_lut", _int),
+                ("range_scale", _dbl), ("max_jump", _dbl), ("min_cos", _dbl), ("mask", _int)]
+
+
 _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
@@ -86,7 +94,7 @@ _volume_p = ctypes.POINTER(Volume)
 _term_p = ctypes.POINTER(VolumeTerm)
 STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams, "dfh_slab": Slab,
            "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes,
-           "dfh_gn_volume_term": VolumeTerm}
+           "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -174,6 +182,8 @@ _SIGNATURES = {
     "dfh_render_samples_emit": (_int, [_vp, _vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _int, _c_double_p, _c_double_p, _int, _int, _dbl,
                                        _c_double_p, _dbl, _dbl, _int, _vp, ctypes.c_size_t, _vp, ctypes.c_size_t, _vp, _vp, _vp,
                                        ctypes.c_long, _vp]),
+    "dfh_depth_prep": (_int, [ctypes.POINTER(DepthPrepParams), _vp, _vp, _vp]),
+    "dfh_depth_prep_tile": (_int, [_c_int_p]),
 }
 
 _lib = None

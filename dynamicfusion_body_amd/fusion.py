@@ -25,6 +25,8 @@ def _is_tensor(a):
 
 class Fusion:
     graph_sampler = "host"       # where construct_graph / update_graph run the radius subsampling (graph.SAMPLERS); set on an instance
+    depth_prep = None            # a depth_prep.DepthPrep: the methods that sweep a LIST of depth maps (InitializeCanonicalSpace from
+                                 # maps, updateTSDF_depths) clean the list with it first; the single-map fuseDepths stays raw
 
     def __init__(self, tsdf, trunc_distance, subsample_rate=5.0, knn=4, marching_cubes_step_size=3, verbose=False,
                  use_cnn=False, write_warpfield=True, volume_dtype=np.float32):
@@ -158,6 +160,8 @@ class Fusion:
                 raise ValueError('depth map must be 2-D')
             if tuple(d.shape) != tuple(depths[0].shape):
                 raise ValueError('all depth maps of one call must have the same shape')
+        if self.depth_prep is not None and depths:
+            depths = self.depth_prep(depths, self._Kinv, want_normals=False)[0]
 
         def exact32(d):
             return (d.dtype == torch.float32) if _is_tensor(d) else f32_exact(np.asarray(d))
@@ -555,6 +559,8 @@ class Fusion:
             self._T = torch.empty((R, R, R), dtype=self._vol_dtype, device="cuda")
             self._Wt = torch.empty_like(self._T)
             self._tsdf_host = None
+            if self.depth_prep is not None and len(depths) > 0:
+                depths = self.depth_prep(depths, self._Kinv, want_normals=False)[0]
             # (the dtype rule of fuseDepths: float32 on the device unless a float64 map is not float32-exact -- then every map
             # travels as float64, so that no visibility mask can flip; integrate_depth_views wants one dtype per call)
             def exact32(d):

@@ -32,6 +32,8 @@ def _is_tensor(a):
 
 
 class FusionDM:
+    depth_prep = None            # a depth_prep.DepthPrep: compute_live_tsdf cleans its list of maps with it first; set on an instance
+
     def __init__(self, trunc_distance, K, tsdf_res=256, subsample_rate=5.0, knn=4, marching_cubes_step_size=3,
                  verbose=False, write_warpfield=True, volume_dtype=np.float32):
         # attribute set of the reference ctor, core/fusion_dm.py:57-81
@@ -351,6 +353,8 @@ class FusionDM:
         tensors instead of downloading them."""
         if len(depths) != len(lws):
             raise ValueError('length of camera matrix array Ks must equal that of depth maps')   # :96-97
+        if self.depth_prep is not None and len(depths) > 0:          # (the single-map fuseDepths stays raw: the reference's meaning)
+            depths = self.depth_prep(depths, self._Kinv, want_normals=False)[0]
         avg = np.array([-0.03, -0.43, -5.6], dtype='float32')       # :106-107
         std = 1.3
         if UseAutoAlignment:

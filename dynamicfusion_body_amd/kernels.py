@@ -345,3 +345,92 @@ def integrate_depth_dqb(T, Wt, depths, K, Kinv, lws, scale, center, tdist, node_
                                          current_stream_ptr())
         _lib.check(rc, "dfh_integrate_depth_dqb")
     return T, Wt
+
+
+def depth_prep_tile():
+    """(rows, columns) of the output tile a workgroup of the depth-preprocessing kernel owns (dfh_depth_prep_tile; no launch)."""
+    hw = (ctypes.c_int * 2)()
+    _lib.check(_lib.load().dfh_depth_prep_tile(hw), "dfh_depth_prep_tile")
+    return int(hw[0]), int(hw[1])
+
+
+def depth_prep_tables(radius, sigma_s, sigma_r, n_lut=1024, cut=3.0, device=None):
+    """The bilateral filter's tables for depth_prep: (spatial (2r+1, 2r+1) float32, range_lut (n_lut,) float32, range_scale), computed
+    in numpy float64 and rounded to float32 (the kernel multiplies table entries; it evaluates no exp):
+      spatial[dy][dx] = exp(-(dx^2 + dy^2) / (2 sigma_s^2))
+      range_scale     = float32(n_lut / (cut * sigma_r)^2)       a squared depth difference times it is the LUT index; differences
+                                                                 beyond cut * sigma_r fall off the table and do not count
+      range_lut[i]    = exp(-((i + 0.5) / range_scale) / (2 sigma_r^2))
+    sigma_s in pixels, sigma_r in the depth maps' units.  device: default the current GPU ("cpu" gives host tensors)."""
+    radius, n_lut = int(radius), int(n_lut)
+    if not 0 <= radius <= 8:
+        raise ValueError("radius must be 0..8, got %d" % radius)
+    if not 1 <= n_lut <= 4096:
+        raise ValueError("n_lut must be 1..4096, got %d" % n_lut)
+    if not (sigma_s > 0 and sigma_r > 0 and cut > 0):
+        raise ValueError("sigma_s, sigma_r and cut must be positive")
+    o = np.arange(-radius, radius + 1, dtype=np.float64)
+    spatial = np.exp(-(o[None, :] ** 2 + o[:, None] ** 2) / (2.0 * float(sigma_s) ** 2)).astype(np.float32)
+    range_scale = float(np.float32(n_lut / (float(cut) * float(sigma_r)) ** 2))
+    lut = np.exp(-((np.arange(n_lut, dtype=np.float64) + 0.5) / range_scale) / (2.0 * float(sigma_r) ** 2)).astype(np.float32)
+    if device is None:
+        require_gpu()
+        device = torch.device("cuda", torch.cuda.current_device())
+    return torch.from_numpy(spatial).to(device), torch.from_numpy(lut).to(device), range_scale
+
+
+def depth_prep(depths, Kinv, tables, max_jump, min_cos, mask=True, want_normals=True, out=None):
+    """K12 = the frame's depth maps filtered, given normals and masked in one launch (dfh_depth_prep; semantics in
+    include/dfusion_hip.h).  depths: list of at most 16 (H, W) CUDA tensors of one shape and dtype (float32 / float64), only read.
+    tables: depth_prep_tables(...) on the maps' device; the window radius is the spatial table's.  max_jump: largest depth step
+    between neighbours a normal is computed across; min_cos: smallest cosine between the normal and the viewing ray.
+    Returns (clean (V, H, W) float32, normals (V, H, W, 3) float32 or None): clean[v] is a depth map every other entry point
+    reads (negative depth, 0 = no measurement); with mask=True the pixels without a normal are 0 in it.
+    out=(clean, normals): write into these tensors instead of fresh ones (either may be None: that output is not produced).  The
+    kernel writes through raw pointers, so the tensors' version counters are bumped here: whatever keys a cache on
+    (data_ptr, _version), WarpSolver's packed views table for one, sees new content."""
+    depths = list(depths)
+    if not depths:
+        raise ValueError("depth_prep needs at least one depth map")
+    if len(depths) > 16:
+        raise ValueError("at most 16 depth maps per call, got %d" % len(depths))
+    for d in depths:
+        if not (isinstance(d, torch.Tensor) and d.dim() == 2):
+            raise ValueError("depth must be a contiguous 2-D CUDA tensor")
+        if d.shape != depths[0].shape or d.dtype != depths[0].dtype:
+            raise ValueError("all depth maps of one call must have the same shape and dtype")
+    spatial, range_lut, range_scale = tables
+    if spatial.dim() != 2 or spatial.shape[0] != spatial.shape[1] or spatial.shape[0] % 2 != 1:
+        raise ValueError("spatial table must be (2r+1, 2r+1), got %s" % (tuple(spatial.shape),))
+    side = int(spatial.shape[0])
+    for t in (spatial, range_lut):
+        if not (t.dtype == torch.float32 and t.is_contiguous()):
+            raise ValueError("filter tables must be contiguous float32 tensors")
+    require_gpu()
+    lib = _lib.load()
+    for d in depths:
+        _check_depth(d)
+    dev = depths[0].device
+    if spatial.device != dev or range_lut.device != dev:
+        raise ValueError("filter tables must live on the depth maps' device")
+    V = len(depths)
+    H, W = (int(n) for n in depths[0].shape)
+    if out is None:
+        clean = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+        normals = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev) if want_normals else None
+    else:
+        clean, normals = out
+        for t, shape in ((clean, (V, H, W)), (normals, (V, H, W, 3))):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and
+                                      t.is_contiguous() and tuple(t.shape) == shape):
+                raise ValueError("out tensor must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
+    ptrs = (ctypes.c_void_p * V)(*[d.data_ptr() for d in depths])
+    prm = _lib.DepthPrepParams(V, ptrs, dtype_code(depths[0]), H, W, _lib.darr(Kinv, 9), (side - 1) // 2, spatial.data_ptr(),
+                               range_lut.data_ptr(), int(range_lut.numel()), float(range_scale), float(max_jump), float(min_cos),
+                               1 if mask else 0)
+    rc = lib.dfh_depth_prep(prm, None if clean is None else clean.data_ptr(), None if normals is None else normals.data_ptr(),
+                            current_stream_ptr())
+    _lib.check(rc, "dfh_depth_prep")
+    if out is not None:
+        torch.autograd.graph.increment_version(tuple(t for t in (clean, normals) if t is not None))
+    return clean, normals

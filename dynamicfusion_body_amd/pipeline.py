@@ -159,8 +159,12 @@ class SlabFrame:
     sample_source = "band"   # set_sample_source(): where refresh_samples() takes the solve's samples from
 
     def __init__(self, K, scale, center, res, tdist_vox, node_pos, node_w, knn=4, pcg_iters=10, band=4.0, volume_dtype=torch.float32,
-                 distributed=True, solve_mode="auto"):
-        """solve_mode (several ranks): "sharded" = every rank builds the normal equations of its own slab's samples, one
+                 distributed=True, solve_mode="auto", depth_prep=None):
+        """depth_prep: a depth_prep.DepthPrep, or None.  step() then cleans the frame's depth maps once, before anything reads
+        them (the live sweep, the solve's association, an update="depth" fusion), and keeps the cleaned maps in
+        `self.clean_depth` (list of (H, W) float32 views) and the live normal maps in `self.live_normals` ((V, H, W, 3)) for the
+        caller; both are rewritten in place by the next step() with maps of the same number and size.
+        solve_mode (several ranks): "sharded" = every rank builds the normal equations of its own slab's samples, one
         all-reduce per GN iteration (BASELINE north star); "replicated" = the slabs' samples are all-gathered once per frame
         and every rank solves the whole system, no per-iteration collective (bit-identical warp fields on all ranks, and the
         single-GPU loop's bits WHEN both run the same PCG path -- _lib dfh_pcg_path: ranks that share one GPU, a rehearsal, take
@@ -190,6 +194,9 @@ class SlabFrame:
                               distributed=self.distributed and self.ws > 1 and solve_mode == "sharded")
         if (node_pos is None) != (node_w is None):
             raise ValueError("node_pos and node_w come together (both None: construct_graph() builds the graph)")
+        self.depth_prep = depth_prep
+        self.clean_depth = self.live_normals = None
+        self._prep_out = None                    # step()'s output buffers of depth_prep, reused from frame to frame
         self.ws_views = None                     # the multi-view dfh_integrate_depth's scratch (parameters + depth pyramids): sized on first use
         self._side = None                        # side stream of step(): the live-volume sweep beside the plan build
         self.updated = None                      # event recorded by step() right after the TSDF update
@@ -487,6 +494,15 @@ class SlabFrame:
         lw_list = list(lw_cam) if isinstance(depth, (list, tuple)) else [lw_cam]
         if len(depth_list) != len(lw_list):
             raise ValueError('length of camera matrix array must equal that of depth maps')
+        if self.depth_prep is not None:
+            shape = (len(depth_list),) + tuple(depth_list[0].shape)
+            if self._prep_out is None or tuple(self._prep_out[0].shape) != shape or self._prep_out[0].device != depth_list[0].device:
+                dev = depth_list[0].device
+                self._prep_out = (torch.empty(shape, dtype=torch.float32, device=dev),
+                                  torch.empty(shape + (3,), dtype=torch.float32, device=dev))
+            depth_list, self.live_normals = self.depth_prep(depth_list, self.Kinv, out=self._prep_out)
+            self.clean_depth = depth_list
+            mark("depth_prep")
         depth, lw_cam = depth_list[0], lw_list[0]
         nd = len(depth_list) if data_views is None else max(1, min(int(data_views), len(depth_list)))
         solve_depth, solve_lw = (depth_list[:nd], lw_list[:nd]) if nd > 1 else (depth, lw_cam)

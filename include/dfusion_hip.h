@@ -719,6 +719,60 @@ int dfh_render_samples_emit(const double *verts, const double *canon_pos, const 
                             const void *scan_workspace, size_t scan_workspace_bytes, double *pos_out, double *nrm_out, long *pixel_out,
                             long capacity, void *stream);
 
+/* ---- K12  depth preprocessing: bilateral filter, live normal map, flying-pixel mask ----------------------------------------
+ * The first stage of KinectFusion / DynamicFusion, which the reference does not have: every depth map of a frame is smoothed,
+ * back-projected, given a normal map and stripped of the pixels no surface normal can be computed for.  The cleaned maps keep
+ * the convention every other entry point reads (negative depth, 0 = no measurement).
+ * All arithmetic is float32 with ONE rounding per operation (no contraction, IEEE division and square root, subnormals kept),
+ * so that an element-wise float32 numpy restatement (tests/depth_prep_np.py) agrees bit for bit; that is why the range weight
+ * is a caller's table and not a device exp.
+ *
+ * Per view v, D = depth[v] (H x W, only read; a float64 value is rounded to nearest-even float32 at load).
+ *   valid(d)  <=>  d is finite and d < 0          (-0.0, 0, positive values, NaN, +-inf: "no measurement")
+ * Stage A, bilateral filter, r = radius, s = (float)range_scale; centre d = D[y][x]:
+ *   centre not valid            -> F = 0
+ *   r == 0                      -> F = d            (no table is read)
+ *   otherwise num = den = 0; for dy = -r..r (outer), dx = -r..r (inner), in that order, every tap e = D[y+dy][x+dx] that lies
+ *   inside the image and is valid:
+ *     delta = e - d;  q = (delta*delta)*s;  the tap counts iff q < (float)n_lut;  i = (int)q (truncation)
+ *     w = spatial[(dy+r)*(2r+1) + (dx+r)] * range_lut[i];  num = num + w*e;  den = den + w
+ *   F = num / den if den > 0, else 0.
+ * Stage B, vertex and normal: Kf = float32(Kinv), J = (float)max_jump, m2 = (float)min_cos * (float)min_cos; x, y are the
+ * float32 values of the pixel's integer indices:
+ *   rho_i(x, y) = (Kf[i][0]*x + Kf[i][1]*y) + Kf[i][2];   P_i = z*rho_i with z = -F
+ * Pixel (y, x) HAS A NORMAL iff valid(F[y][x]); its four neighbours (y, x+-1), (y+-1, x) lie inside the image, are valid in F
+ * and have |F_nb - F| <= J; and with a = P(y,x+1) - P(y,x-1), b = P(y+1,x) - P(y-1,x):
+ *   n0 = a1*b2 - a2*b1;  n1 = a2*b0 - a0*b2;  n2 = a0*b1 - a1*b0;  l2 = (n0*n0 + n1*n1) + n2*n2;  l2 > 0 and finite;
+ *   nh = n / sqrt(l2) (three divisions);  c = (nh0*P0 + nh1*P1) + nh2*P2 at the centre;  c > 0: nh = -nh, c = -c (the normal
+ *   faces the camera);  pp = (P0*P0 + P1*P1) + P2*P2;  kept iff c*c >= m2*pp.
+ * Outputs (device float32; either may be NULL, not both):
+ *   normals (n_views, H, W, 3): nh, or zeros where the pixel has no normal
+ *   clean   (n_views, H, W)   : F if mask == 0 or the pixel has a normal, else 0.  mask = 1 removes silhouette ("flying")
+ *                               pixels, isolated pixels, pixels seen at a grazing angle and the one-pixel image border.
+ * One launch for all views; the filtered map never goes through memory.  The outputs must not alias an input (the kernel reads
+ * halos that other workgroups write: in-place use is not supported).
+ * DFH_E_BADARG before any launch: a null params / depth array / depth[v]; n_views outside 1..16; a dtype other than DFH_F32 /
+ * DFH_F64; H or W < 2 or H*W >= 2^31; radius outside 0..8; spatial or range_lut NULL with radius > 0; n_lut outside 1..4096;
+ * range_scale not finite or <= 0; max_jump not finite or < 0; min_cos outside [0, 1]; mask not 0 or 1; both outputs NULL; an
+ * output equal to one of the input pointers.
+ * dfh_depth_prep_tile: the kernel's output tile (rows, columns) per workgroup, for tests that put image sizes on its edges. */
+typedef struct dfh_depth_prep_params {
+    int n_views;                  /* 1..16 */
+    const void *const *depth;     /* HOST array of n_views device pointers, H x W row-major */
+    int depth_dtype, H, W;        /* DFH_F32 | DFH_F64; H, W >= 2 */
+    double Kinv[9];
+    int radius;                   /* 0..8 */
+    const float *spatial;         /* DEVICE (2r+1)^2, NULL allowed iff radius == 0 */
+    const float *range_lut;       /* DEVICE n_lut,    NULL allowed iff radius == 0 */
+    int n_lut;                    /* 1..4096 */
+    double range_scale;           /* finite, > 0 */
+    double max_jump;              /* finite, >= 0 */
+    double min_cos;               /* 0..1 */
+    int mask;                     /* 0 | 1 */
+} dfh_depth_prep_params;
+int dfh_depth_prep(const dfh_depth_prep_params *p, float *clean, float *normals, void *stream);
+int dfh_depth_prep_tile(int tile_hw[2]);
+
 #ifdef __cplusplus
 }
 #endif
