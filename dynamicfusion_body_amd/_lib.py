@@ -87,14 +87,21 @@ class DepthPrepParams(ctypes.Structure):
                 ("range_scale", _dbl), ("max_jump", _dbl), ("min_cos", _dbl), ("mask", _int)]
 
 
+class NormalGate(ctypes.Structure):
+    """dfh_gn_normal_gate: the live normal maps ((V, H, W, 3) float32, device) and the smallest compatible cosine."""
+    _fields_ = [("normals", _vp), ("min_cos", _dbl)]
+
+
 _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
 _volume_p = ctypes.POINTER(Volume)
 _term_p = ctypes.POINTER(VolumeTerm)
+_gate_p = ctypes.POINTER(NormalGate)
 STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams, "dfh_slab": Slab,
            "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes,
-           "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams}
+           "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams,
+           "dfh_gn_normal_gate": NormalGate}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -139,6 +146,10 @@ _SIGNATURES = {
     "dfh_gn_build_volume": (_int, [_problem_p, _term_p, _vp]),
     "dfh_gn_solve": (_int, [_problem_p, _frame_p, ctypes.POINTER(SolveParams), _vp]),
     "dfh_gn_solve_volume": (_int, [_problem_p, _term_p, ctypes.POINTER(SolveParams), _vp]),
+    "dfh_gn_associate_gated": (_int, [_problem_p, _frame_p, _gate_p, _vp]),
+    "dfh_gn_build_gated": (_int, [_problem_p, _frame_p, _gate_p, _vp]),
+    "dfh_gn_solve_gated": (_int, [_problem_p, _frame_p, _gate_p, ctypes.POINTER(SolveParams), _vp]),
+    "dfh_gn_global_sampled_gated": (_int, [_problem_p, _frame_p, _gate_p, _int, _dbl, _int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dfh_gn_pack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "dfh_gn_unpack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "dfh_gn_sort_workspace_bytes": (ctypes.c_size_t, [_int]),

@@ -118,13 +118,16 @@ constexpr int kGlobalGrid = 1536;                   // workgroups of the rows ke
 // (i, 6)); the accumulator is four doubles per lane where 27 running sums per thread made the kernel a 256-VGPR one: one wave
 // per SIMD, a tile's whole chain of dependent loads exposed -- 65 us for config 3's 762 tiles, 131 us for config 5's 5.2 k.
 // VOLUME: the samples are associated against a live TSDF volume of DepthT (one trilinear cell, dfh_assoc_volume.h) instead of
-// the frame's views; the kernel's last argument is what its association reads.
-template <int K, typename DepthT, bool VOLUME = false>
+// the frame's views; the kernel's last argument is what its association reads.  GATED: the views through the normal gate
+// (associate_views<.., true>): the sample's warped normal is computed in front of the association, the gate's arguments travel in
+// this mode's own struct.
+template <int K, typename DepthT, bool VOLUME = false, bool GATED = false>
 __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(3, 8))) void gn_global_rows_kernel(const double *__restrict__ spos, const double *__restrict__ snrm,
                                                               const int *__restrict__ nbr, const double *__restrict__ wts,
                                                               const double *__restrict__ node_dq, const BuildParams p, int stride, long n_sub,
                                                               double *__restrict__ tile_part,
-                                                              const std::conditional_t<VOLUME, VolAssocArgs, AssocArgs> aa) {
+                                                              const std::conditional_t<VOLUME, VolAssocArgs, std::conditional_t<GATED, GatedAssocArgs, AssocArgs>> aa) {
+    static_assert(!(VOLUME && GATED), "the normal gate is the depth term's");
     __shared__ double sPart[kTileWaves][kGlobalVals];
     __shared__ double sX[kTile * 8];
     typedef double d4 __attribute__((ext_vector_type(4)));
@@ -153,7 +156,10 @@ __global__ __launch_bounds__(kTile) __attribute__((amdgpu_waves_per_eu(3, 8))) v
             double c[3];
             bool ok;                                                              // (a lane with s >= S is not here: it touches no map, no volume)
             if constexpr (VOLUME) ok = associate_volume_cell<DepthT>(static_cast<const DepthT *>(aa.live), aa.vp, xp, c);
-            else ok = associate_views<DepthT>(aa.ap, aa.views, aa.n_views, xp, c);
+            else if constexpr (GATED) {
+                const D3 np_ = warped_normal(bh, p.lw.q, snrm[3 * (size_t)s], snrm[3 * (size_t)s + 1], snrm[3 * (size_t)s + 2]);
+                ok = associate_views<DepthT, true>(aa.ap, aa.views, aa.n_views, xp, c, ~0u, aa.ng.normals, aa.ng.min_cos, np_.x, np_.y, np_.z);
+            } else ok = associate_views<DepthT>(aa.ap, aa.views, aa.n_views, xp, c);
             if (ok) {
                 double Jrow[6 * K];
                 double r = data_row_from(node_dq, idx, w, K, p.lw.q, bh, nb, pfx, pfy, pfz, xp, snrm[3 * (size_t)s], snrm[3 * (size_t)s + 1],
@@ -368,12 +374,13 @@ int dfh_gn_global_apply(const double *sums29, double lm_rel, int n_nodes, double
 // f64: the maps' / the volume's type.  The problem and the frame or term are checked by the caller.
 static int gn_global_sampled_impl(const char *what, const dfh_gn_problem &q, const dfh::AssocArgs *views, const dfh::VolAssocArgs *vol, bool f64,
                                   int stride, double lm_rel, int n_steps, double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes,
-                                  void *stream) {
+                                  void *stream, const dfh::GatedAssocArgs *gated = nullptr) {
     using namespace dfh;
     const int n_samples = q.n_samples, knn = q.knn, n_nodes = q.n_nodes;
     DFH_REQUIRE(scratch && lm_rel >= 0.0, "%s: bad arguments", what);
     DFH_REQUIRE(scratch_bytes >= dfh_gn_global_sampled_bytes(n_samples, stride), "%s: scratch too small", what);
     DFH_REQUIRE(!sums_out || n_steps == 1, "%s: sums_out (the caller reduces over ranks and applies) takes one step per call", what);
+    if (gated && n_samples == 0) return DFH_OK;                      // (nothing to gate: the ungated call is the one that writes empty sums)
     BuildParams bp;
     for (int i = 0; i < 8; ++i) bp.lw.q[i] = q.lw_dq[i];
     bp.S = n_samples; bp.k = knn; bp.N = n_nodes; bp.huber = q.huber_delta;
@@ -389,6 +396,9 @@ static int gn_global_sampled_impl(const char *what, const dfh_gn_problem &q, con
     if (vol)                                                                                                                       \
         hipLaunchKernelGGL((gn_global_rows_kernel<KK, T, true>), dim3((unsigned)n_wg), dim3(kTile), 0, st, q.sample_pos, q.sample_nrm,  \
                            q.nbr, q.weights, (const double *)q.node_dq, bp, stride, n_sub, tile_part, *vol);                         \
+    else if (gated)                                                                                                                \
+        hipLaunchKernelGGL((gn_global_rows_kernel<KK, T, false, true>), dim3((unsigned)n_wg), dim3(kTile), 0, st, q.sample_pos, q.sample_nrm, \
+                           q.nbr, q.weights, (const double *)q.node_dq, bp, stride, n_sub, tile_part, *gated);                       \
     else                                                                                                                           \
         hipLaunchKernelGGL((gn_global_rows_kernel<KK, T>), dim3((unsigned)n_wg), dim3(kTile), 0, st, q.sample_pos, q.sample_nrm,        \
                            q.nbr, q.weights, (const double *)q.node_dq, bp, stride, n_sub, tile_part, *views)
@@ -422,6 +432,21 @@ int dfh_gn_global_sampled(const dfh_gn_problem *problem, const dfh_gn_frame *fra
     const AssocArgs aa = assoc_args(*problem, *frame, false);
     return gn_global_sampled_impl(what, *problem, &aa, nullptr, frame->depth_dtype == DFH_F64, stride, lm_rel, n_steps, xi_out, sums_out,
                                   scratch, scratch_bytes, stream);
+}
+
+int dfh_gn_global_sampled_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate, int stride,
+                                double lm_rel, int n_steps, double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream) {
+    using namespace dfh;
+    const char *what = "dfh_gn_global_sampled_gated";
+    DFH_REQUIRE(n_steps >= 0 && n_steps <= 100 && stride >= 1, "%s: %d steps, stride %d", what, n_steps, stride);
+    if (n_steps == 0) return DFH_OK;
+    int rc = check_problem(what, problem, false);
+    if (rc == DFH_OK) rc = check_frame(what, frame, false);
+    if (rc == DFH_OK) rc = check_gate(what, gate);
+    if (rc != DFH_OK) return rc;
+    const GatedAssocArgs ga = gated_assoc_args(*problem, *frame, *gate, false);
+    return gn_global_sampled_impl(what, *problem, nullptr, nullptr, frame->depth_dtype == DFH_F64, stride, lm_rel, n_steps, xi_out, sums_out,
+                                  scratch, scratch_bytes, stream, &ga);
 }
 
 int dfh_gn_global_sampled_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, int stride, double lm_rel, int n_steps,

@@ -80,9 +80,23 @@ __device__ __forceinline__ bool associate_backproject(const AssocParams &p, cons
 // (core/fusion.py:255-276); restated in oracle/gn_np.py:associate_depth_views.
 // view_mask (wave-uniform): the views to try, bit v = view v (all of them: ~0u).  A tile of the fused build passes the views
 // its samples can possibly be valid in (tile_view_mask below): the others are not even projected.
-template <typename DepthT>
+//
+// The normal-compatibility gate (dfh_gn_normal_gate; GATED only -- the ungated instantiations read none of it): a view's
+// correspondence also needs the live normal l of the pixel the depth came from (normals: n_views x H x W x 3 float32, camera
+// space, (0,0,0) = none) to agree with the sample's warped normal n' = (npx, npy, npz) rotated into that camera, m = R n':
+// d = sgn(scale) (m . l) > 0 and d^2 >= min_cos^2 |m|^2 |l|^2 (no square root; a NaN fails both ways round).  The three floats
+// are asked for together with the depth value -- still one memory round trip per group of views -- and the test sits beside
+// the distance gate, in front of the "nearest view wins" comparison: a rejected nearer view lets a farther compatible one win.
+// It only removes correspondences, so tile_view_mask stays exact.  Restated in tests/assoc_normals_np.py.
+struct NormalGate {
+    const float *normals;
+    double min_cos;
+};
+
+template <typename DepthT, bool GATED = false>
 __device__ __forceinline__ bool associate_views(const AssocParams &p, const AssocView *__restrict__ views, int n_views, const D3 &xp,
-                                                double (&c)[3], unsigned view_mask = ~0u) {
+                                                double (&c)[3], unsigned view_mask = ~0u, const float *__restrict__ normals = nullptr,
+                                                double min_cos = 0.0, double npx = 0.0, double npy = 0.0, double npz = 0.0) {
     bool any = false;
     double best = __builtin_huge_val();
     c[0] = 0.0; c[1] = 0.0; c[2] = 0.0;
@@ -90,12 +104,14 @@ __device__ __forceinline__ bool associate_views(const AssocParams &p, const Asso
     unsigned todo = view_mask & (n_views >= 32 ? ~0u : ((1u << n_views) - 1u));
     while (todo) {                                         // (uniform: the views' parameters come through scalar loads)
         double u[G], vv[G], z[G];
+        float l[GATED ? G : 1][3];
         bool ok[G];
         int vi_[G];
 #pragma unroll
         for (int j = 0; j < G; ++j) {
             ok[j] = false; z[j] = 0.0; u[j] = 0.0; vv[j] = 0.0;
             vi_[j] = -1;
+            if constexpr (GATED) { l[j][0] = 0.0f; l[j][1] = 0.0f; l[j][2] = 0.0f; }
             if (todo) {
                 const int v = __builtin_ctz(todo);         // (ascending: the surviving views in view order)
                 todo &= todo - 1u;
@@ -104,6 +120,10 @@ __device__ __forceinline__ bool associate_views(const AssocParams &p, const Asso
                 if (ok[j]) {
                     const int ui = (int)rint(u[j]), vi = (int)rint(vv[j]);
                     z[j] = -1.0 * (double)static_cast<const DepthT *>(views[v].depth)[(size_t)vi * p.W + ui];     // :196
+                    if constexpr (GATED) {
+                        const float *ln = normals + (((size_t)v * p.H + vi) * p.W + ui) * 3;
+                        l[j][0] = ln[0]; l[j][1] = ln[1]; l[j][2] = ln[2];
+                    }
                 }
             }
         }
@@ -113,6 +133,17 @@ __device__ __forceinline__ bool associate_views(const AssocParams &p, const Asso
                 double c0, c1, c2, d2;
                 bool good = associate_backproject(p, views[vi_[j]].lw_cam, views[vi_[j]].Rinv, z[j], u[j], vv[j], xp, c0, c1, c2, d2);
                 if (good && p.max_dist > 0.0) good = d2 <= p.max_dist * p.max_dist;
+                if constexpr (GATED) {
+                    const double *R = views[vi_[j]].lw_cam;
+                    const double m0 = (R[0] * npx + R[1] * npy) + R[2] * npz;
+                    const double m1 = (R[4] * npx + R[5] * npy) + R[6] * npz;
+                    const double m2 = (R[8] * npx + R[9] * npy) + R[10] * npz;
+                    const double l0 = (double)l[j][0], l1 = (double)l[j][1], l2 = (double)l[j][2];
+                    const double sgn = p.scale > 0.0 ? 1.0 : -1.0;
+                    const double d = sgn * ((m0 * l0 + m1 * l1) + m2 * l2);
+                    const double mm = (m0 * m0 + m1 * m1) + m2 * m2, ll = (l0 * l0 + l1 * l1) + l2 * l2;
+                    good = good && d > 0.0 && d * d >= (min_cos * min_cos) * (mm * ll);      // (a NaN fails)
+                }
                 // (strict, best starts at +inf: a depth of -inf -- c and d2 inf or NaN -- or a d2 that overflows is no data row, with
                 // or without the gate; oracle/gn_np.py:associate_depth states the same rule)
                 if (good && d2 < best) { best = d2; c[0] = c0; c[1] = c1; c[2] = c2; any = true; }
@@ -217,6 +248,13 @@ __host__ __device__ constexpr int gn_gram_index(int K, int sa, int sb, int ia, i
     return sa <= sb ? 36 * gn_sub(K, sa, sb) + 6 * ia + ib : 36 * gn_sub(K, sb, sa) + 6 * ib + ia;
 }
 
+// A sample's warped normal n' as data_row_from computes it for the row (the same functions on the same values: the same bits) --
+// what the normal gate compares with the live normals, before the association.
+__device__ __forceinline__ D3 warped_normal(const double *bh, const double *lwq, double nx, double ny, double nz) {
+    const D3 n1 = dqb_warp_normal_exact(bh, round_f32(nx), round_f32(ny), round_f32(nz));
+    return dqb_warp_normal_exact(lwq, round_f32(n1.x), round_f32(n1.y), round_f32(n1.z));
+}
+
 // Residual and 6-DoF Jacobian rows of one data sample (formulas: oracle/gn_np.py
 // data_residual_jacobian).  J is written as k x 6 into Jrow (row-major), returns r.
 // second half of data_row: from the normalised blend bh (|b|_8 = nb), the float32-rounded point pf and the warped point xp
@@ -283,6 +321,10 @@ struct AssocArgs {
     int n_views;
     int cull;                   // 1: drop, per tile, the views none of its samples can be valid in (tile_view_mask)
 };
+// ... and a kernel that associates through the normal gate (its own struct: the ungated kernels' arguments stay what they are)
+struct GatedAssocArgs : AssocArgs {
+    NormalGate ng;
+};
 
 // ------------------------------------------------------------------------------- host side
 // What every GN entry point checks of its problem: the samples and nodes; with `system` also the block system and the plans.
@@ -318,6 +360,14 @@ inline int check_frame(const char *what, const dfh_gn_frame *f, bool fused) {
     return DFH_OK;
 }
 
+// ... and of its normal gate
+inline int check_gate(const char *what, const dfh_gn_normal_gate *g) {
+    DFH_REQUIRE(g, "%s: null normal gate", what);
+    DFH_REQUIRE(g->normals, "%s: null normal maps", what);
+    DFH_REQUIRE(g->min_cos >= 0.0 && g->min_cos <= 1.0, "%s: min_cos %g outside [0, 1]", what, g->min_cos);      // (NaN fails)
+    return DFH_OK;
+}
+
 // The association's kernel arguments.  cull: drop, per tile, the views none of its samples can be valid in (tile_view_mask):
 // it costs a tile one barrier and one memory round trip (+5 % on the 3-view frame, where the views all face the object and
 // nothing is dropped), so it is taken from four views up (the 8-view orbit: -9 % of the solve stage).
@@ -332,6 +382,12 @@ inline AssocArgs assoc_args(const dfh_gn_problem &p, const dfh_gn_frame &f, bool
     aa.n_views = f.n_views;
     aa.cull = cull && f.n_views >= 4 && !on(opt().gn_no_view_cull) ? 1 : 0;
     return aa;
+}
+inline GatedAssocArgs gated_assoc_args(const dfh_gn_problem &p, const dfh_gn_frame &f, const dfh_gn_normal_gate &g, bool cull) {
+    GatedAssocArgs ga;
+    static_cast<AssocArgs &>(ga) = assoc_args(p, f, cull);
+    ga.ng = NormalGate{g.normals, g.min_cos};
+    return ga;
 }
 
 }  // namespace dfh

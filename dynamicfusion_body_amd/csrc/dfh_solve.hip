@@ -49,6 +49,37 @@ __global__ __launch_bounds__(256) void associate_kernel(const double *__restrict
     valid[i] = ok ? 1 : 0;
 }
 
+// associate_kernel through the normal gate (dfh_gn_associate_gated): the sample's warped normal first -- data_row_from's n', the
+// same bits -- then the association with the live normals beside the depth values.
+template <typename DepthT>
+__global__ __launch_bounds__(256) void associate_gated_kernel(const double *__restrict__ spos, const double *__restrict__ snrm,
+                                                               const int *__restrict__ nbr, const double *__restrict__ wts, int S,
+                                                               const double *__restrict__ node_dq, const AssocParams p,
+                                                               double *__restrict__ corr, unsigned char *__restrict__ valid,
+                                                               const AssocView *__restrict__ views, int n_views, const NormalGate ng) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= S) return;
+    int idx[kKMaxS];
+    double w[kKMaxS];
+#pragma unroll
+    for (int j = 0; j < kKMaxS; ++j) {
+        idx[j] = j < p.k ? nbr[(size_t)i * p.k + j] : 0;
+        w[j] = j < p.k ? wts[(size_t)i * p.k + j] : 0.0;
+    }
+    double b[8];
+    blend_static(node_dq, idx, w, p.k, b);
+    const double px = spos[3 * (size_t)i], py = spos[3 * (size_t)i + 1], pz = spos[3 * (size_t)i + 2];
+    const D3 x1 = dqb_warp_exact(b, round_f32(px), round_f32(py), round_f32(pz));
+    const D3 xp = dqb_warp_exact(p.lw.q, round_f32(x1.x), round_f32(x1.y), round_f32(x1.z));
+    const D3 np_ = warped_normal(b, p.lw.q, snrm[3 * (size_t)i], snrm[3 * (size_t)i + 1], snrm[3 * (size_t)i + 2]);
+    double c[3];
+    const bool ok = associate_views<DepthT, true>(p, views, n_views, xp, c, ~0u, ng.normals, ng.min_cos, np_.x, np_.y, np_.z);
+    corr[3 * (size_t)i] = c[0];
+    corr[3 * (size_t)i + 1] = c[1];
+    corr[3 * (size_t)i + 2] = c[2];
+    valid[i] = ok ? 1 : 0;
+}
+
 // ------------------------------------------------------------------------------- normal equations
 // One kTile-sample tile per block.  Samples must be sorted by their k-tuple of nodes (any order
 // is CORRECT; sorted order just means few runs per tile and therefore few atomics).
@@ -82,10 +113,13 @@ __device__ void gn_reg_pairs(int block, const int *__restrict__ node_nbr, int N,
 // against the frame's views (associate_kernel's arithmetic, same bits).  Volume: one trilinear cell of a live TSDF volume
 // (associate_volume_kernel's arithmetic, same bits: dfh_assoc_volume.h) -- no views, so no tile box and no view mask.
 // The kernel's last argument is what its mode reads: the views' arguments (also for None, which reads nothing: its kernarg
-// segment is what it was), or the volume's.
-enum class AssocMode { None, Views, Volume };
+// segment is what it was), or the volume's.  ViewsGated: Views through the normal gate (dfh_gn_rows.h: associate_views<.., true>) --
+// the sample's warped normal is computed in front of the association, and the gate's arguments travel in a struct of this mode's
+// own, so the other modes get no new kernel argument.
+enum class AssocMode { None, Views, Volume, ViewsGated };
 template <AssocMode MODE> struct AssocArgsOf { typedef AssocArgs type; };
 template <> struct AssocArgsOf<AssocMode::Volume> { typedef VolAssocArgs type; };
+template <> struct AssocArgsOf<AssocMode::ViewsGated> { typedef GatedAssocArgs type; };
 #ifdef DFH_BUILD_TRACE   // experiment builds only: wall-clock stamps of every tile's phases
 __device__ unsigned long long g_build_trace[8192][8];
 #define BT_STAMP(k) do { if (threadIdx.x == 0 && blockIdx.x < 8192) g_build_trace[blockIdx.x][k] = wall_clock64(); } while (0)
@@ -150,7 +184,7 @@ __global__ __launch_bounds__(kTile) void gn_build_data_kernel(const double *__re
         const D3 x1 = dqb_warp_exact(a_bh, a_pf[0], a_pf[1], a_pf[2]);
         a_xp = dqb_warp_exact(p.lw.q, round_f32(x1.x), round_f32(x1.y), round_f32(x1.z));
     }
-    if constexpr (MODE == AssocMode::Views) {
+    if constexpr (MODE == AssocMode::Views || MODE == AssocMode::ViewsGated) {
         unsigned view_mask = ~0u;
         if (aa.views && aa.cull) {                                            // (workgroup-uniform)
             // the tile's warped samples' box -> the views any of them can be valid in
@@ -177,8 +211,17 @@ __global__ __launch_bounds__(kTile) void gn_build_data_kernel(const double *__re
             }
             view_mask = tile_view_mask(aa.ap, aa.views, aa.n_views, box, &sMask);
         }
-        if (tid < tile_n)
-            a_ok = associate_views<float>(aa.ap, aa.views, aa.n_views, a_xp, a_c, view_mask);
+        if constexpr (MODE == AssocMode::ViewsGated) {
+            // (n' before the association; data_row_from arrives at the same bits afterwards -- the same inlined functions on the same
+            // values, so whether the registers are kept or the normal is warped again is the compiler's choice)
+            if (tid < tile_n) {
+                const D3 a_np = warped_normal(a_bh, p.lw.q, a_n[0], a_n[1], a_n[2]);
+                a_ok = associate_views<float, true>(aa.ap, aa.views, aa.n_views, a_xp, a_c, view_mask, aa.ng.normals, aa.ng.min_cos, a_np.x, a_np.y, a_np.z);
+            }
+        } else {
+            if (tid < tile_n)
+                a_ok = associate_views<float>(aa.ap, aa.views, aa.n_views, a_xp, a_c, view_mask);
+        }
     } else if constexpr (MODE == AssocMode::Volume) {
         // (lanes beyond the ragged last tile hold no sample: they issue no live-volume load)
         if (tid < tile_n) a_ok = associate_volume_cell<float>(static_cast<const float *>(aa.live), aa.vp, a_xp, a_c);
@@ -910,6 +953,28 @@ int dfh_gn_associate(const dfh_gn_problem *problem, const dfh_gn_frame *frame, v
     return DFH_OK;
 }
 
+int dfh_gn_associate_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate, void *stream) {
+    using namespace dfh;
+    const char *what = "dfh_gn_associate_gated";
+    int rc = check_problem(what, problem, false);
+    if (rc == DFH_OK) rc = check_frame(what, frame, false);
+    if (rc == DFH_OK) rc = check_gate(what, gate);
+    if (rc != DFH_OK) return rc;
+    const dfh_gn_problem &q = *problem;
+    if (q.n_samples == 0) return DFH_OK;
+    const GatedAssocArgs ga = gated_assoc_args(q, *frame, *gate, false);
+    dim3 grid((q.n_samples + 255) / 256), block(256);
+    if (frame->depth_dtype == DFH_F32) {
+        hipLaunchKernelGGL(associate_gated_kernel<float>, grid, block, 0, (hipStream_t)stream, q.sample_pos, q.sample_nrm, q.nbr, q.weights,
+                           q.n_samples, q.node_dq, ga.ap, q.corr, q.valid, ga.views, ga.n_views, ga.ng);
+    } else {
+        hipLaunchKernelGGL(associate_gated_kernel<double>, grid, block, 0, (hipStream_t)stream, q.sample_pos, q.sample_nrm, q.nbr, q.weights,
+                           q.n_samples, q.node_dq, ga.ap, q.corr, q.valid, ga.views, ga.n_views, ga.ng);
+    }
+    DFH_HIP_CHECK(hipGetLastError());
+    return DFH_OK;
+}
+
 // The table travels as kernel arguments of a one-workgroup launch that writes it to device memory (a hipMemcpyAsync from
 // pageable host memory is staged by the runtime and stalls the stream for tens of microseconds)
 namespace dfh {
@@ -1014,10 +1079,11 @@ int dfh_gn_pack_views(void *out, int n_views, const void *const *depth, int dept
 }
 
 // The association fused into the data-row kernel (the caller checked that there is a plan): against the frame's views, against
-// a live volume, or (both null) none.
+// a live volume, against the views through the normal gate, or (all null) none.
 struct BuildAssoc {
     const dfh::AssocArgs *views;
     const dfh::VolAssocArgs *vol;
+    const dfh::GatedAssocArgs *gated = nullptr;
 };
 
 // zero_ptr / zero_count: doubles the launch's last workgroups clear (*zeroed says whether they did).  The problem is checked
@@ -1070,6 +1136,9 @@ static int gn_build_impl(const dfh_gn_problem &q, const BuildAssoc &ba, void *st
         if (ba.vol)                                                                                                 \
             hipLaunchKernelGGL((gn_build_data_kernel<KK, true, AssocMode::Volume>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
                                q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, *ba.vol); \
+        else if (ba.gated)                                                                                          \
+            hipLaunchKernelGGL((gn_build_data_kernel<KK, true, AssocMode::ViewsGated>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
+                               q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, *ba.gated); \
         else if (assoc)                                                                                             \
             hipLaunchKernelGGL((gn_build_data_kernel<KK, true, AssocMode::Views>), grid, block, 0, s, q.sample_pos, q.sample_nrm, q.nbr, q.weights, \
                                q.corr, q.valid, q.node_dq, p, q.row_ptr, q.col, vals, rhs, cost_count, q.run_id, partial, tile_cost, rt, aa); \
@@ -1137,6 +1206,27 @@ int dfh_gn_build(const dfh_gn_problem *problem, const dfh_gn_frame *frame, void 
     return gn_build_impl(*problem, BuildAssoc{&aa, nullptr}, stream);
 }
 
+// the checks the fused gated entry points share; *ga <- the data-row kernel's arguments
+static int check_fused_gated(const char *what, const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate,
+                             dfh::GatedAssocArgs *ga) {
+    using namespace dfh;
+    int rc = check_problem(what, problem, true);
+    if (rc == DFH_OK) rc = check_frame(what, frame, true);
+    if (rc == DFH_OK) rc = check_gate(what, gate);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(problem->blk_ptr, "%s: null blk_ptr (the fused association needs a plan)", what);
+    *ga = gated_assoc_args(*problem, *frame, *gate, true);
+    return DFH_OK;
+}
+
+int dfh_gn_build_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate, void *stream) {
+    dfh::GatedAssocArgs ga;
+    const int rc = check_fused_gated("dfh_gn_build_gated", problem, frame, gate, &ga);
+    if (rc != DFH_OK) return rc;
+    if (problem->n_samples == 0) return DFH_OK;                      // (nothing to gate: dfh_gn_build builds the sample-less system)
+    return gn_build_impl(*problem, BuildAssoc{nullptr, nullptr, &ga}, stream);
+}
+
 // the checks the fused volume entry points share; *va <- the data-row kernel's arguments
 static int check_fused_volume(const char *what, const dfh_gn_problem *problem, const dfh_gn_volume_term *term, dfh::VolAssocArgs *va) {
     using namespace dfh;
@@ -1181,6 +1271,7 @@ static int gn_solve_impl(const char *what, const dfh_gn_problem &q, const BuildA
     DFH_REQUIRE(sp.n_global >= 0 && sp.n_global <= 100, "%s: %d rigid-mode steps", what, sp.n_global);
     DFH_REQUIRE(sp.pcg_iters >= 1 && sp.x_out && sp.pcg_workspace, "%s: bad solve arguments", what);
     DFH_REQUIRE(sp.pcg_workspace_bytes >= dfh_pcg_workspace_bytes(q.n_nodes, sp.pcg_iters), "%s: solve workspace too small", what);
+    if (ba.gated && q.n_samples == 0) return DFH_OK;                 // (nothing to gate: dfh_gn_solve runs the sample-less schedule)
     int rc;
     for (int g = 0; g < sp.n_global; ++g) {
         rc = gn_build_impl(q, ba, stream);
@@ -1212,6 +1303,14 @@ int dfh_gn_solve(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const
     DFH_REQUIRE(problem->blk_ptr, "dfh_gn_solve: null blk_ptr (the fused association needs a plan)");
     const AssocArgs aa = assoc_args(*problem, *frame, true);
     return gn_solve_impl("dfh_gn_solve", *problem, BuildAssoc{&aa, nullptr}, params, stream);
+}
+
+int dfh_gn_solve_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate,
+                       const dfh_gn_solve_params *params, void *stream) {
+    dfh::GatedAssocArgs ga;
+    const int rc = check_fused_gated("dfh_gn_solve_gated", problem, frame, gate, &ga);
+    if (rc != DFH_OK) return rc;
+    return gn_solve_impl("dfh_gn_solve_gated", *problem, BuildAssoc{nullptr, nullptr, &ga}, params, stream);
 }
 
 int dfh_gn_solve_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, const dfh_gn_solve_params *params, void *stream) {

@@ -93,24 +93,30 @@ class FrameSolver:
         self.solver.set_samples(pos, nrm, knn_bricks=knn_bricks)
         return pos.shape[0]
 
-    def gn_iteration(self, depth, lw_cam, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.0, n_iters=1, n_global=0, global_lm=0.1):
+    def gn_iteration(self, depth, lw_cam, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.0, n_iters=1, n_global=0, global_lm=0.1,
+                     normals=None, normal_cos=0.5):
         """associate -> build (+ all-reduce) -> PCG -> twist update, n_iters times; asynchronous.  depth / lw_cam may be lists
         (several live views: every sample associates with the view in which it lies closest to the observed surface).
-        n_global: that many rigid-mode steps first (global_iteration), in the same library call on one GPU."""
+        n_global: that many rigid-mode steps first (global_iteration), in the same library call on one GPU.
+        normals / normal_cos: the normal gate of WarpSolver.associate_depth ((V, H, W, 3) float32 live normal maps; None: none)."""
         self.solver.iterate_associated(depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.half, self.lw, rw, max_dist, huber,
-                                       lm_abs, lm_rel, n_iters=n_iters, n_global=n_global, global_lm=global_lm)
+                                       lm_abs, lm_rel, n_iters=n_iters, n_global=n_global, global_lm=global_lm, normals=normals,
+                                       normal_cos=normal_cos)
 
-    def global_iteration(self, depth, lw_cam, rw=5.0, max_dist=2.0, huber=0.0, lm_rel=0.1, n_iters=1, built=False, stride=1):
+    def global_iteration(self, depth, lw_cam, rw=5.0, max_dist=2.0, huber=0.0, lm_rel=0.1, n_iters=1, built=False, stride=1,
+                         normals=None, normal_cos=0.5):
         """The rigid mode alone -- one twist shared by all nodes -- n_iters times; asynchronous.  Worth several node iterations where
         the live frame has moved as a whole: ten truncated PCG iterations hardly touch that mode.  Default: straight from the
         samples (WarpSolver.global_sampled: data rows only, two short launches a step); built=True: from the built normal
-        equations, regulariser included (associate -> build (+ all-reduce) -> WarpSolver.global_step)."""
+        equations, regulariser included (associate -> build (+ all-reduce) -> WarpSolver.global_step).
+        normals / normal_cos: the normal gate of WarpSolver.associate_depth, on either route."""
         if not built:
             self.solver.global_sampled(depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.half, self.lw, max_dist, huber, lm_rel,
-                                       n_steps=n_iters, stride=stride)
+                                       n_steps=n_iters, stride=stride, normals=normals, normal_cos=normal_cos)
             return
         for _ in range(int(n_iters)):
-            self.solver.build_associated(depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.half, self.lw, rw, max_dist, huber)
+            self.solver.build_associated(depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.half, self.lw, rw, max_dist, huber,
+                                         normals, normal_cos)
             self.solver.global_step(lm_rel)
 
     def gn_iteration_volume(self, live, band, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.0, n_iters=1, min_grad=0.5,
@@ -159,8 +165,13 @@ class SlabFrame:
     sample_source = "band"   # set_sample_source(): where refresh_samples() takes the solve's samples from
 
     def __init__(self, K, scale, center, res, tdist_vox, node_pos, node_w, knn=4, pcg_iters=10, band=4.0, volume_dtype=torch.float32,
-                 distributed=True, solve_mode="auto", depth_prep=None):
-        """depth_prep: a depth_prep.DepthPrep, or None.  step() then cleans the frame's depth maps once, before anything reads
+                 distributed=True, solve_mode="auto", depth_prep=None, normal_gate=None):
+        """normal_gate: None, or the smallest cosine between a sample's warped normal and the live normal of the pixel it is matched
+        to that still gives a correspondence (the normal gate of the depth data term, WarpSolver.associate_depth; 0.5 = 60 degrees):
+        step() then passes this frame's live normal maps to the rigid-mode steps and the node iterations.  It needs depth_prep
+        (where the normal maps come from) and data_term="depth"; step(normal_gate=...) overrides it per call.  The normal maps are a
+        per-frame input on every rank, so several ranks need nothing further (that case has not been measured).
+        depth_prep: a depth_prep.DepthPrep, or None.  step() then cleans the frame's depth maps once, before anything reads
         them (the live sweep, the solve's association, an update="depth" fusion), and keeps the cleaned maps in
         `self.clean_depth` (list of (H, W) float32 views) and the live normal maps in `self.live_normals` ((V, H, W, 3)) for the
         caller; both are rewritten in place by the next step() with maps of the same number and size.
@@ -195,6 +206,7 @@ class SlabFrame:
         if (node_pos is None) != (node_w is None):
             raise ValueError("node_pos and node_w come together (both None: construct_graph() builds the graph)")
         self.depth_prep = depth_prep
+        self.normal_gate = self._check_normal_gate(normal_gate, depth_prep)
         self.clean_depth = self.live_normals = None
         self._prep_out = None                    # step()'s output buffers of depth_prep, reused from frame to frame
         self.ws_views = None                     # the multi-view dfh_integrate_depth's scratch (parameters + depth pyramids): sized on first use
@@ -210,6 +222,20 @@ class SlabFrame:
             ident = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0, 0]), (N, 1))
             self.fs.set_graph(node_pos, ident, node_w)
             self._graph_workspaces(node_pos, N)
+
+    @staticmethod
+    def _check_normal_gate(normal_gate, depth_prep):
+        """A normal gate's value: None, or a cosine in [0, 1] together with a depth_prep (the source of the live normals)."""
+        if normal_gate is None:
+            return None
+        cos = float(normal_gate)
+        if not 0.0 <= cos <= 1.0:
+            raise ValueError("normal_gate must be None or a cosine in [0, 1], got %r" % (normal_gate,))
+        if depth_prep is None:
+            raise ValueError("normal_gate needs depth_prep: the live normal maps come from there")
+        return cos
+
+    _KEEP = object()          # step(normal_gate=...): "the constructor's value"
 
     def _graph_workspaces(self, node_pos, N):
         """K3's workspace and the per-brick candidate lists for a graph of N nodes (the samples' node search uses the same lists)."""
@@ -435,8 +461,10 @@ class SlabFrame:
 
     def step(self, depth, lw_cam, gn_iters=10, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.5, stage_ms=None,
              update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None,
-             data_term="depth", global_built=None, update="volume", update_weight="node_distance", graph_sampler="host"):
-        """update: how the canonical slab takes the frame in.  "volume" = the reference's two stages: the live volume fused from
+             data_term="depth", global_built=None, update="volume", update_weight="node_distance", graph_sampler="host",
+             normal_gate=_KEEP):
+        """normal_gate: this call's normal gate (a cosine, or None for none) instead of the constructor's; see there.
+        update: how the canonical slab takes the frame in.  "volume" = the reference's two stages: the live volume fused from
         the depth maps (K1) is resampled through the warp field (K3, kernels.fuse_volume_dqb; the warp gathers across slab faces,
         so several ranks all-gather the live volume).  "depth" = DynamicFusion's surface fusion (K1w,
         kernels.integrate_depth_dqb): every canonical voxel of this rank's slab is warped into the live frame, projected into the
@@ -473,6 +501,9 @@ class SlabFrame:
             raise ValueError("update must be 'depth' or 'volume'")
         if update == "depth" and update_weight not in kernels.WARPED_WEIGHTS:
             raise ValueError("update_weight must be one of %s" % sorted(kernels.WARPED_WEIGHTS))
+        gate_cos = self.normal_gate if normal_gate is SlabFrame._KEEP else self._check_normal_gate(normal_gate, self.depth_prep)
+        if gate_cos is not None and data_term != "depth":
+            raise ValueError("normal_gate is the depth data term's: data_term must be 'depth'")
         if not self.has_graph:
             raise ValueError("no deformation graph yet: call construct_graph() first")
         need_live = update == "volume" or data_term == "volume"       # (update="depth" fuses the maps themselves)
@@ -506,6 +537,7 @@ class SlabFrame:
         depth, lw_cam = depth_list[0], lw_list[0]
         nd = len(depth_list) if data_views is None else max(1, min(int(data_views), len(depth_list)))
         solve_depth, solve_lw = (depth_list[:nd], lw_list[:nd]) if nd > 1 else (depth, lw_cam)
+        gate_kw = {} if gate_cos is None else {"normals": self.live_normals[:nd], "normal_cos": gate_cos}
         def sweep_live():
             if self.ws_views is None:
                 self.ws_views = kernels.integrate_workspace(min(len(depth_list), 16), depth.shape[0], depth.shape[1], (R, R, R), (self.a, self.b), self.live.device)
@@ -555,9 +587,10 @@ class SlabFrame:
             # (every `global_stride`-th tile of THIS rank's samples: with the samples sharded over ranks a stride > 1 thins another
             # subsample than one GPU does -- the same estimator on other data; stride 1 is partition-independent)
             self.fs.global_iteration(solve_depth, solve_lw, max_dist=max_dist, huber=huber, lm_rel=global_lm, n_iters=ng,
-                                     stride=self.GLOBAL_STRIDE if global_stride is None else int(global_stride))
+                                     stride=self.GLOBAL_STRIDE if global_stride is None else int(global_stride), **gate_kw)
         if data_term == "depth":
-            self.fs.gn_iteration(solve_depth, solve_lw, rw=rw, lm_abs=lm_abs, lm_rel=lm_rel, max_dist=max_dist, huber=huber, n_iters=gn_iters)
+            self.fs.gn_iteration(solve_depth, solve_lw, rw=rw, lm_abs=lm_abs, lm_rel=lm_rel, max_dist=max_dist, huber=huber, n_iters=gn_iters,
+                                 **gate_kw)
         mark("solve")
         if not joined:
             torch.cuda.current_stream().wait_stream(self._side)

@@ -247,6 +247,7 @@ class WarpSolver:
         self.S = 0
         self._prob, self._frm, self._sp = _lib.Problem(), _lib.Frame(), _lib.SolveParams()     # the C ABI's structs, refilled per call
         self._term = _lib.VolumeTerm()
+        self._gate_s = _lib.NormalGate()
         if _dist.ranks_share_a_gpu():                  # (whether or not THIS solver runs collectives: ADVICE round 2)
             # several processes time-share this GPU (a rehearsal of the multi-GPU job on one card): co-residency of the
             # persistent PCG's workgroups is not guaranteed across processes -> two launches per iteration, no grid barrier
@@ -657,11 +658,33 @@ class WarpSolver:
         f.scale, f.half, f.max_dist = float(scale), float(half), float(max_dist)
         return f
 
-    def associate_depth(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist=0.0):
+    def _gate(self, normals, normal_cos, frame):
+        """The normal gate (dfh_gn_normal_gate) of a frame, or None without normal maps.  normals: the views' live normal maps, a
+        contiguous (V, H, W, 3) float32 CUDA tensor with V the number of views passed (depth_prep's layout); normal_cos: the
+        smallest cosine between a sample's warped normal and the live normal that still gives a correspondence."""
+        if normals is None:
+            return None
+        if not (isinstance(normals, torch.Tensor) and normals.is_cuda and normals.dtype == torch.float32 and normals.is_contiguous()
+                and tuple(normals.shape) == (frame.n_views, frame.H, frame.W, 3)):
+            raise ValueError("normals must be a contiguous (%d, %d, %d, 3) float32 CUDA tensor: one map per view passed"
+                             % (frame.n_views, frame.H, frame.W))
+        cos = float(normal_cos)
+        if not 0.0 <= cos <= 1.0:
+            raise ValueError("normal_cos must lie in [0, 1], got %r" % (normal_cos,))
+        g = self._gate_s
+        g.normals, g.min_cos = normals.data_ptr(), cos
+        return g
+
+    def associate_depth(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist=0.0, normals=None, normal_cos=0.5):
         """Projective association of the warped samples against a live depth map (CUDA tensor) -- or against several
         (lists of depth maps and extrinsics): each sample keeps the correspondence of the view in which it lies closest to
-        the observed surface (dfh_gn_associate)."""
+        the observed surface (dfh_gn_associate).  normals (see _gate): only views whose live normal at the pixel makes a cosine
+        of at least normal_cos with the sample's warped normal count (dfh_gn_associate_gated); None: no such test."""
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        gate = self._gate(normals, normal_cos, frame)
+        if gate is not None:
+            _lib.check(self.lib.dfh_gn_associate_gated(self._problem(lw_dq), frame, gate, current_stream_ptr()), "dfh_gn_associate_gated")
+            return
         _lib.check(self.lib.dfh_gn_associate(self._problem(lw_dq), frame, current_stream_ptr()), "dfh_gn_associate")
 
     def _volume_term(self, live, band, max_dist, min_grad, value_to_vox):
@@ -741,46 +764,60 @@ class WarpSolver:
                                          current_stream_ptr()), "dfh_gn_build")
         self._allreduce_system()                  # no-op on one GPU; samples are sharded by slab
 
-    def build_associated(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist=0.0, huber=0.0):
+    def build_associated(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist=0.0, huber=0.0, normals=None,
+                         normal_cos=0.5):
         """associate_depth + build in one launch sequence (dfh_gn_build with a frame): same corr / valid, same system, bit
-        for bit; float32 depth maps and the planned build only (otherwise the two calls are made)."""
+        for bit; float32 depth maps and the planned build only (otherwise the two calls are made).  normals / normal_cos: the
+        normal gate of associate_depth (dfh_gn_build_gated)."""
         if self._pattern is None:
             self._build_pattern()
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        gate = self._gate(normals, normal_cos, frame)
         if (frame.depth_dtype != _lib.F32 or self.S == 0 or _lib.opt_on("py_gn_atomic") or _lib.opt_on("py_gn_no_fused_assoc")):
-            self.associate_depth(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist)
+            self.associate_depth(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist, normals, normal_cos)
             return self.build(lw_dq, rw, huber)
         reg_here = (not self.distributed) or _dist.world()[0] == 0
-        _lib.check(self.lib.dfh_gn_build(self._problem(lw_dq, rw, huber, reg=reg_here), frame, current_stream_ptr()), "dfh_gn_build")
+        prob = self._problem(lw_dq, rw, huber, reg=reg_here)
+        if gate is not None:
+            _lib.check(self.lib.dfh_gn_build_gated(prob, frame, gate, current_stream_ptr()), "dfh_gn_build_gated")
+        else:
+            _lib.check(self.lib.dfh_gn_build(prob, frame, current_stream_ptr()), "dfh_gn_build")
         self._allreduce_system()
 
     def iterate_associated(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist=0.0, huber=0.0, lm_abs=0.0, lm_rel=0.0,
-                           n_iters=1, n_global=0, global_lm=0.1):
+                           n_iters=1, n_global=0, global_lm=0.1, normals=None, normal_cos=0.5):
         """n_global rigid-mode steps (build_associated + global_step each), then n_iters GN iterations (build_associated +
         solve_update each).  On one GPU (no all-reduce between the halves) they are ONE call, dfh_gn_solve: the iterations are
         queued back to back without returning to Python, and in each the clearing of the solve's workspace rides in the data-row
-        launch -- the same bits as separate calls.  option py_gn_iter_per_call: one dfh_gn_solve call per iteration."""
+        launch -- the same bits as separate calls.  option py_gn_iter_per_call: one dfh_gn_solve call per iteration.
+        normals / normal_cos: the normal gate of associate_depth in every build (dfh_gn_solve_gated; the py_gn_* options steer the
+        gated sequences as they steer the ungated ones, and all of them leave the same bits)."""
         if self._pattern is None:
             self._build_pattern()
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        gate = self._gate(normals, normal_cos, frame)
         one_call = (frame.depth_dtype == _lib.F32 and self.S > 0 and not _lib.opt_on("py_gn_atomic") and
                     not _lib.opt_on("py_gn_no_fused_assoc") and not _lib.opt_on("py_gn_no_fused_iter") and
                     not (self.distributed and (_dist.world()[1] > 1 or self.force_collective)))
         per_call = one_call and _lib.opt_on("py_gn_iter_per_call")
         if not one_call or per_call:
             for _ in range(int(n_global)):                # the rigid mode first (global_step): one twist for all nodes
-                self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber)
+                self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber, normals, normal_cos)
                 self.global_step(global_lm)
             if not one_call:
                 for _ in range(int(n_iters)):
-                    self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber)
+                    self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber, normals, normal_cos)
                     self.solve_update(lm_abs, lm_rel)
                 return
             frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+            gate = self._gate(normals, normal_cos, frame)
         sp = self._solve_params(lm_abs, lm_rel, n_iters, n_global, global_lm, per_call)
         prob = self._problem(lw_dq, rw, huber)
         for _ in range(int(n_iters) if per_call else 1):
-            _lib.check(self.lib.dfh_gn_solve(prob, frame, sp, current_stream_ptr()), "dfh_gn_solve")
+            if gate is not None:
+                _lib.check(self.lib.dfh_gn_solve_gated(prob, frame, gate, sp, current_stream_ptr()), "dfh_gn_solve_gated")
+            else:
+                _lib.check(self.lib.dfh_gn_solve(prob, frame, sp, current_stream_ptr()), "dfh_gn_solve")
 
     def _solve_params(self, lm_abs, lm_rel, n_iters, n_global, global_lm, per_call):
         """One dfh_gn_solve / dfh_gn_solve_volume call's schedule (per_call: one node iteration, the rigid-mode steps were taken)."""
@@ -826,12 +863,20 @@ class WarpSolver:
                                           self.pcg_ws.data_ptr(), self.pcg_ws.numel() * 8, current_stream_ptr()),
                    "dfh_pcg_solve")
 
-    def global_sampled(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist=0.0, huber=0.0, lm_rel=0.1, n_steps=1, stride=1):
+    def global_sampled(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist=0.0, huber=0.0, lm_rel=0.1, n_steps=1, stride=1,
+                       normals=None, normal_cos=0.5):
         """n_steps rigid-mode steps straight from the samples (dfh_gn_global_sampled): ONE twist shared by all nodes, fitted
         to the data rows of every `stride`-th tile (no built system, no regulariser), applied to every node.  depth / lw_cam:
         one view or lists.  Samples sharded over ranks: the 29 sums are all-reduced, every rank applies the same twist.
-        Asynchronous; self.global_xi holds the last step's twist | objective | valid count."""
+        Asynchronous; self.global_xi holds the last step's twist | objective | valid count.  normals / normal_cos: the normal
+        gate of associate_depth on the rows' association (dfh_gn_global_sampled_gated)."""
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
+        gate = self._gate(normals, normal_cos, frame)
+        if gate is not None and self.S > 0:         # (no samples: nothing to gate, and the ungated call writes the empty sums)
+            def call(prob, frm, *rest):
+                return self.lib.dfh_gn_global_sampled_gated(prob, frm, gate, *rest)
+            self._global_sampled(call, "dfh_gn_global_sampled_gated", frame, lw_dq, huber, lm_rel, n_steps, stride)
+            return
         self._global_sampled(self.lib.dfh_gn_global_sampled, "dfh_gn_global_sampled", frame, lw_dq, huber, lm_rel, n_steps, stride)
 
     def global_sampled_volume(self, live, lw_dq, band, max_dist=0.0, huber=0.0, lm_rel=0.1, n_steps=1, stride=1, min_grad=0.5,

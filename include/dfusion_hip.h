@@ -527,6 +527,43 @@ int dfh_gn_solve(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const
  * dfh_gn_build_volume and dfh_gn_solve refuse. */
 int dfh_gn_solve_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, const dfh_gn_solve_params *params, void *stream);
 
+/* The normal-compatibility gate of the depth data term (opt-in: the calls above know nothing of it).  dfh_gn_associate accepts a
+ * view's correspondence when the sample projects inside the image, the pixel has depth and |c - x'| <= max_dist; on anything
+ * thinner than max_dist, and under an orbit of cameras, that matches samples to the far side of what they sit on.  With a gate the
+ * view's correspondence must also face the way the model surface does: the live normal of the pixel the depth came from
+ * (dfh_depth_prep's maps: camera space, flipped to face the camera) against the sample's warped normal (the TSDF gradient, which
+ * points into free space: the two agree on a visible surface, so "compatible" is a POSITIVE cosine).  KinectFusion and
+ * DynamicFusion reject such pairs the same way; the reference (mesh-to-mesh correspondences, core/fusion.py:255-276) has no
+ * counterpart.  Everything is fp64, operation by operation in this order, no contraction.  For a sample:
+ *  1. n' = its normal warped exactly as the data row warps it, the same functions and the same bits:
+ *     dqb_warp_normal(lw_dq, f32(dqb_warp_normal(b^, f32(n)))), b^ the normalised static blend of its knn node DQs.
+ *  2. for view v and the pixel (ui, vi) = (rint(u), rint(v)) dfh_gn_associate takes the depth from:
+ *     l = the three floats at ((v*H + vi)*W + ui)*3 of `normals`, widened to double;
+ *     m_i = (R_i0*n'_x + R_i1*n'_y) + R_i2*n'_z, R the 3x3 part of that view's lw_cam;
+ *     d = sgn*((m_0*l_0 + m_1*l_1) + m_2*l_2), sgn = +1 if scale > 0, else -1;
+ *     mm = (m_0*m_0 + m_1*m_1) + m_2*m_2, ll = (l_0*l_0 + l_1*l_1) + l_2*l_2.
+ *  3. the view's correspondence passes iff d > 0 and d*d >= (min_cos*min_cos)*(mm*ll): no square root, scale-free in l and n'.  A
+ *     NaN anywhere fails, and so does a pixel without a normal (l = 0: d = 0).
+ *  4. the test sits beside the distance gate, BEFORE the "smallest |c - x'|^2 wins, ties to the lower view" comparison: a rejected
+ *     nearer view lets a farther compatible one win.  The gate only removes correspondences, so the fused builds' per-tile view
+ *     cull stays exact.
+ * Restated in tests/assoc_normals_np.py.  Each call below has its ungated twin's contract -- what it reads and writes, the bits
+ * of everything the gate lets through, float32 / float64 maps and the plan where the twin needs them -- plus the gate, and
+ * additionally reads sample_nrm where the twin did not (dfh_gn_associate_gated).  dfh_gn_build_gated: corr / valid / vals / rhs /
+ * cost_count are, bit for bit, those of dfh_gn_associate_gated followed by dfh_gn_build(problem, NULL); dfh_gn_solve_gated: the
+ * schedule of dfh_gn_solve with dfh_gn_build_gated as its build, the same bits as the separate calls.  DFH_E_BADARG (before any HIP
+ * call): everything the twin refuses, a null gate, null normals, min_cos NaN or outside [0, 1].  n_samples == 0: DFH_OK and nothing
+ * is launched (there is nothing to gate; the ungated twins are the calls that build a sample-less system or write empty sums). */
+typedef struct dfh_gn_normal_gate {
+    const float *normals;   /* n_views x H x W x 3 float32 (device), view-major, contiguous: dfh_depth_prep's layout.  Camera space of
+                               each view, (0,0,0) = the pixel has no normal.  Need not be unit length. */
+    double min_cos;         /* in [0, 1]: the smallest cosine between model and live normal that still passes */
+} dfh_gn_normal_gate;
+int dfh_gn_associate_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate, void *stream);
+int dfh_gn_build_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate, void *stream);
+int dfh_gn_solve_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate,
+                       const dfh_gn_solve_params *params, void *stream);
+
 /* Multi-GPU solve: what travels in the per-iteration all-reduce.  `system` = {J^T J blocks (n_blocks x 36) | J^T r (6 n_nodes) |
  * cost, count} as the builds write it; J^T J is symmetric, so only the blocks with col >= row are packed (then J^T r and
  * {cost, count}): (36 n_upper + 6 n_nodes + 2) doubles in `packed`, about 55 % of the system.  row_of[b] / col[b]: block b's
@@ -595,6 +632,10 @@ int dfh_gn_global_sampled(const dfh_gn_problem *problem, const dfh_gn_frame *fra
  * contract.  A sample beyond n_samples touches no voxel.  n_steps == 0: DFH_OK, nothing is checked further or launched. */
 int dfh_gn_global_sampled_volume(const dfh_gn_problem *problem, const dfh_gn_volume_term *term, int stride, double lm_rel, int n_steps,
                                  double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream);
+/* dfh_gn_global_sampled through the normal gate (dfh_gn_normal_gate above): float32 or float64 maps, knn 1..8; the rows, the sums
+ * and their order, scratch, xi_out and sums_out are that call's.  n_steps == 0: DFH_OK, nothing is checked further or launched. */
+int dfh_gn_global_sampled_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate, int stride,
+                                double lm_rel, int n_steps, double *xi_out, double *sums_out, void *scratch, size_t scratch_bytes, void *stream);
 int dfh_gn_global_apply(const double *sums29, double lm_rel, int n_nodes, double *node_dq, double *xi_out, void *stream);
 size_t dfh_gn_global_step_bytes(void);
 int dfh_gn_global_step(const double *vals, int n_blocks, const double *rhs, int n_nodes, double lm_rel, double *node_dq, double *xi_out,
