@@ -195,6 +195,10 @@ _SIGNATURES = {
                                        ctypes.c_long, _vp]),
     "dfh_depth_prep": (_int, [ctypes.POINTER(DepthPrepParams), _vp, _vp, _vp]),
     "dfh_depth_prep_tile": (_int, [_c_int_p]),
+    "dfh_nearest_descriptors_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long, _int]),
+    "dfh_nearest_descriptors_path": (_int, [ctypes.c_long, ctypes.c_long, _int]),
+    "dfh_nearest_descriptors": (_int, [_vp, ctypes.c_long, _vp, ctypes.c_long, _int, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dfh_nearest_descriptors_tile": (_int, [_c_int_p]),
 }
 
 _lib = None

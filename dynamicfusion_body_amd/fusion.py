@@ -25,6 +25,9 @@ def _is_tensor(a):
 
 class Fusion:
     graph_sampler = "host"       # where construct_graph / update_graph run the radius subsampling (graph.SAMPLERS); set on an instance
+    descriptor_fn = None         # a callable (vertices (n,3), faces (m,3) or None) -> (n, D) float32 per-vertex descriptors: stands where
+                                 # the reference calls compute_correspondence(self.input, self._feature, self._sess, vertices, faces)
+                                 # (core/fusion.py:280-281); with it setupCorrespondences(method='cnn') takes the reference's CNN branch
     depth_prep = None            # a depth_prep.DepthPrep: the methods that sweep a LIST of depth maps (InitializeCanonicalSpace from
                                  # maps, updateTSDF_depths) clean the list with it first; the single-map fuseDepths stays raw
 
@@ -268,7 +271,7 @@ class Fusion:
         fr = _solve.residual_reg(dqs, nbr[vidx], pos, w, rw)
         return torch.cat([fd, fr]).cpu().numpy()
 
-    def setupCorrespondences(self, curr_tsdf, method='cnn', prune_result=True, tolerance=0.2, live_vertices=None):
+    def setupCorrespondences(self, curr_tsdf, method='cnn', prune_result=True, tolerance=0.2, live_vertices=None, descriptors=None):
         """Closest-point correspondences of the DQB-warped canonical vertices in the live surface; reference
         core/fusion.py:243-314, the branch taken without a CNN session (`self._sess is None or method ==
         'clpts'`): live mesh by marching cubes, warp each vertex / normal with its blended node DQs and `_lw`,
@@ -279,7 +282,14 @@ class Fusion:
         index, :273-274) -- the intended canonical index is used.  `live_vertices` replaces the marching-cubes call.
         method='sdf' (not in the reference): the correspondences come straight from the live VOLUME (WarpSolver.associate_volume,
         band = the truncation distance, no gate; the volume holds distances in voxels) and `keep` is the association's validity;
-        the pruning bookkeeping is the same."""
+        the pruning bookkeeping is the same.
+        method='cnn' with `descriptors` = (s_feats (V, D), l_feats (L, D)) or with `descriptor_fn` set (the pair wins): the
+        reference's CNN branch (:277-296).  Every canonical vertex takes the live vertex with the nearest descriptor
+        (solve.nearest_descriptors: exact fp64 distances, lowest index on ties); with `prune_result` the vertices whose warped
+        point-to-plane cost |n'.(v' - c)| exceeds `tolerance` are pruned (:288-296), and so is a vertex no live descriptor is
+        comparable with (index -1: NaNs); without pruning such a vertex keeps its own warped position (a zero data row).  The
+        live mesh is marching_cubes(curr_tsdf, step_size=1); with an explicit pair `live_vertices` may replace it.  Without a
+        pair and without `descriptor_fn`, method='cnn' is the closest-points branch, as in the reference without a session."""
         if self._vertices is None or self._normals is None or len(self._neighbor_look_up) == 0:
             raise ValueError('canonical vertices / normals / _neighbor_look_up have not been set')
         self._curr_tsdf = curr_tsdf
@@ -287,7 +297,39 @@ class Fusion:
         Nn = np.asarray(self._normals, dtype=np.float64)
         nbr = np.asarray(self._neighbor_look_up, dtype=np.int64)
         pos, dq, w, _ = self.node_arrays()
-        if method == 'sdf':
+        by_descriptor = method == 'cnn' and (descriptors is not None or self.descriptor_fn is not None)
+        if by_descriptor and descriptors is not None:
+            # shapes first: nothing below may touch the device with a pair that cannot be used
+            if len(descriptors) != 2:
+                raise ValueError('descriptors must be a pair (s_feats, l_feats)')
+            _solve.check_descriptor_pair(descriptors[0], descriptors[1])
+            if descriptors[0].shape[0] != len(V):
+                raise ValueError('s_feats has %d rows for %d canonical vertices' % (descriptors[0].shape[0], len(V)))
+            if live_vertices is not None and descriptors[1].shape[0] != len(live_vertices):
+                raise ValueError('l_feats has %d rows for %d live vertices' % (descriptors[1].shape[0], len(live_vertices)))
+        if by_descriptor:
+            if descriptors is not None and live_vertices is not None:
+                lverts, lfaces = np.asarray(live_vertices, dtype=np.float64), None
+            else:
+                lverts, lfaces = self.marching_cubes(curr_tsdf, step_size=1)[:2]
+            if descriptors is not None:
+                s_feats, l_feats = descriptors
+            else:
+                s_feats = self.descriptor_fn(np.asarray(self._vertices), getattr(self, '_faces', None))      # :280
+                l_feats = self.descriptor_fn(lverts, lfaces)                                                 # :281
+                _solve.check_descriptor_pair(s_feats, l_feats)
+                if s_feats.shape[0] != len(V):
+                    raise ValueError('s_feats has %d rows for %d canonical vertices' % (s_feats.shape[0], len(V)))
+            if l_feats.shape[0] != len(lverts):
+                raise ValueError('l_feats has %d rows for %d live vertices' % (l_feats.shape[0], len(lverts)))
+            idx = _solve.nearest_descriptors(s_feats, l_feats).to(torch.int64)                               # :282-284
+            vp, wn = _solve.warp_points(V, Nn, np.asarray(self._lw, dtype=np.float64), nbr=nbr, node_dq=dq, node_pos=pos, node_w=w)
+            found = idx >= 0
+            corr = torch.where(found[:, None], _solve._f64(lverts, (3,))[idx.clamp(min=0)], vp)             # :285
+            d = vp - corr
+            cost = ((wn[:, 0] * d[:, 0] + wn[:, 1] * d[:, 1]) + wn[:, 2] * d[:, 2]).abs()                    # :294
+            keep = found & ~(cost > tolerance)                                                              # :295
+        elif method == 'sdf':
             # the volume data term (dfh_gn_associate_volume): every warped vertex takes one Newton step along the live volume's
             # trilinear gradient onto its zero level set -- no marching cubes of the live volume, no search; vertices whose cell
             # is not inside the truncation band (or has no usable gradient) get no correspondence and are the ones pruned

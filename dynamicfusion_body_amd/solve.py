@@ -125,6 +125,74 @@ def closest_correspondences(warped_pos, warped_nrm, live_verts, knn, tolerance):
     return corr, cost, keep
 
 
+def _descriptors_f32(a, what):
+    """(n, D) descriptors as a contiguous CUDA float32 tensor.  float32 passes as it is; float64 must be float32-exact (the rule
+    the depth maps follow: no silent rounding), NaNs and infinities included; anything else is refused."""
+    if isinstance(a, torch.Tensor):
+        if a.dtype == torch.float64:
+            t = a.to(torch.float32)
+            back = t.to(torch.float64)
+            if not bool(((back == a) | (torch.isnan(back) & torch.isnan(a))).all()):
+                raise ValueError("%s: float64 descriptors that are not float32-exact" % what)
+        elif a.dtype == torch.float32:
+            t = a
+        else:
+            raise ValueError("%s: descriptors must be float32 or float64, got %s" % (what, a.dtype))
+    else:
+        a = np.asarray(a)
+        if a.dtype == np.float64:
+            f = a.astype(np.float32)
+            if not np.array_equal(f.astype(np.float64), a, equal_nan=True):
+                raise ValueError("%s: float64 descriptors that are not float32-exact" % what)
+            a = f
+        elif a.dtype != np.float32:
+            raise ValueError("%s: descriptors must be float32 or float64, got %s" % (what, a.dtype))
+        t = torch.from_numpy(np.ascontiguousarray(a))
+    if t.dim() != 2:
+        raise ValueError("%s: descriptors must be (n, D), got shape %s" % (what, tuple(t.shape)))
+    return t
+
+
+def check_descriptor_pair(query, base):
+    """The shape rules of nearest_descriptors on anything with a .shape, before the device is touched."""
+    qs, bs = tuple(query.shape), tuple(base.shape)
+    if len(qs) != 2 or len(bs) != 2:
+        raise ValueError("descriptors must be (n, D) arrays, got shapes %s and %s" % (qs, bs))
+    if qs[1] != bs[1]:
+        raise ValueError("query and base descriptors disagree in width: %d and %d channels" % (qs[1], bs[1]))
+    if not 1 <= qs[1] <= 64:
+        raise ValueError("descriptors must have 1..64 channels, got %d" % qs[1])
+    if bs[0] < 1:
+        raise ValueError("no base descriptors")
+
+
+def nearest_descriptors(query, base, return_d2=False, return_stats=False):
+    """idx (n_query,) int32: for every query descriptor the base descriptor at the smallest fp64 squared distance, lowest index
+    on exact ties, -1 where no pair is finite (dfh_nearest_descriptors; the reference's `KDTree(l_feats).query(s_feats[idx])`,
+    core/fusion.py:282-285).  numpy arrays or CUDA tensors, float32 or float32-exact float64.  return_d2: also the squared
+    distances (float64, +inf with -1); return_stats: also the CUDA int64 pair (pairs re-evaluated by the fast path, queries
+    handed to the exact kernel).  Asynchronous on the current stream."""
+    q, b = _descriptors_f32(query, "nearest_descriptors (query)"), _descriptors_f32(base, "nearest_descriptors (base)")
+    check_descriptor_pair(q, b)
+    require_gpu()
+    lib = _lib.load()
+    q, b = q.to(device="cuda").contiguous(), b.to(device="cuda").contiguous()
+    nq, nb, dim = q.shape[0], b.shape[0], q.shape[1]
+    idx = torch.empty(nq, dtype=torch.int32, device="cuda")
+    d2 = torch.empty(nq, dtype=torch.float64, device="cuda") if return_d2 else None
+    stats = torch.zeros(2, dtype=torch.int64, device="cuda") if return_stats else None
+    ws, ws_bytes = None, 0
+    if nq > 0 and lib.dfh_nearest_descriptors_path(nq, nb, dim) == 2:
+        ws_bytes = lib.dfh_nearest_descriptors_workspace_bytes(nq, nb, dim)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device="cuda")
+    _lib.check(lib.dfh_nearest_descriptors(q.data_ptr(), nq, b.data_ptr(), nb, dim, idx.data_ptr(),
+                                           0 if d2 is None else d2.data_ptr(), 0 if stats is None else stats.data_ptr(),
+                                           0 if ws is None else ws.data_ptr(), ws_bytes, current_stream_ptr()),
+               "dfh_nearest_descriptors")
+    out = (idx,) + ((d2,) if return_d2 else ()) + ((stats,) if return_stats else ())
+    return out[0] if len(out) == 1 else out
+
+
 def sample_knn(sample_pos, node_pos, node_w, knn, bricks=None):
     """(nbr (S,k) int32, weights (S,k) fp64) of arbitrary points: k nearest nodes, nearest first.
     bricks = (res, (x0, x1), workspace): look the candidates up in the per-brick lists of a fuse_volume_dqb workspace

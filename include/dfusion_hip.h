@@ -814,6 +814,39 @@ typedef struct dfh_depth_prep_params {
 int dfh_depth_prep(const dfh_depth_prep_params *p, float *clean, float *normals, void *stream);
 int dfh_depth_prep_tile(int tile_hw[2]);
 
+/* ---- K14  descriptor correspondences: exact nearest neighbour in feature space -------------------------------------------------
+ * The search of the reference's CNN branch (core/fusion.py:282-285): `KDTree(l_feats).query(s_feats[idx])` on the float64
+ * copies of float32 descriptors, squared (no square root), with the tie rule the KD-tree leaves open made explicit.
+ * query (n_query, dim) and base (n_base, dim): float32, row-major, device.  All arithmetic of the definition is fp64 with ONE
+ * rounding per operation (no contraction), so that tests/descriptors_np.py agrees bit for bit:
+ *   t_c      = (double)query[q][c] - (double)base[l][c]
+ *   d2(q, l) = (((t_0*t_0) + t_1*t_1) + ...) + t_{dim-1}*t_{dim-1}            channels in ascending order
+ *   the pair (q, l) COUNTS iff d2(q, l) is finite (float32 inputs cannot overflow the sum: iff neither row holds a NaN or an
+ *   infinity)
+ *   idx_out[q] = the counting l with the smallest d2(q, l), the LOWEST such l on exact ties;  d2_out[q] = that d2
+ *   a query with no counting pair: idx_out[q] = -1, d2_out[q] = +inf.
+ * Two paths give these same bits (csrc/dfh_descriptors.hip, DESIGN K14): the exact kernel evaluates every pair; the fast path
+ * filters with a float32 score on the matrix cores, keeps every base row inside a proven guard band of the smallest score
+ * and evaluates the definition on those.  Option nd_path: unset = the library decides by size, 1 = the exact kernel, 2 = the
+ * fast path (any other set value: DFH_E_BADARG); dfh_nearest_descriptors_path reports the path a call of that size takes
+ * (1 or 2).
+ * d2_out may be NULL.  stats_out (device, 2 longs) may be NULL: [0] = pairs the fast path re-evaluated with the definition,
+ * [1] = queries handed to the exact kernel (the exact path: 0 and n_query).
+ * workspace: dfh_nearest_descriptors_workspace_bytes(n_query, n_base, dim) bytes of device memory, 16-byte aligned, read and
+ * written by the fast path only (the exact path ignores it, NULL allowed there); the size is 0 for unusable sizes and for
+ * n_query == 0.  Only enqueues on `stream`.
+ * n_query == 0: DFH_OK before any launch.  DFH_E_BADARG before any HIP call: dim outside 1..64; n_base outside [1, 2^31);
+ * n_query outside [0, 2^31); a bad nd_path; null query / base / idx_out; on the fast path a null, misaligned or too small
+ * workspace. */
+size_t dfh_nearest_descriptors_workspace_bytes(long n_query, long n_base, int dim);
+int dfh_nearest_descriptors_path(long n_query, long n_base, int dim);
+int dfh_nearest_descriptors(const float *query, long n_query, const float *base, long n_base, int dim, int *idx_out, double *d2_out,
+                            long *stats_out, void *workspace, size_t workspace_bytes, void *stream);
+/* dfh_nearest_descriptors_tile: tile[0], tile[1] = queries and base rows per workgroup step of the fast path's score kernel,
+ * tile[2] = queries per workgroup of the exact kernel, tile[3] = candidate slots per query (more candidates: the exact kernel);
+ * for tests that put sizes on those edges. */
+int dfh_nearest_descriptors_tile(int tile[4]);
+
 #ifdef __cplusplus
 }
 #endif
