@@ -199,6 +199,11 @@ _SIGNATURES = {
     "dfh_nearest_descriptors_path": (_int, [ctypes.c_long, ctypes.c_long, _int]),
     "dfh_nearest_descriptors": (_int, [_vp, ctypes.c_long, _vp, ctypes.c_long, _int, _vp, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dfh_nearest_descriptors_tile": (_int, [_c_int_p]),
+    "dfh_render_vertex_ids": (_int, [_vp, ctypes.c_long, _vp, ctypes.c_long, _int, _c_double_p, _c_double_p, _int, _int, _dbl, _c_double_p,
+                                     _dbl, _dbl, _vp, ctypes.c_size_t, _dbl, _dbl, _vp, _vp, _vp]),
+    "dfh_pool_features_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long]),
+    "dfh_pool_features": (_int, [_vp, _vp, ctypes.c_long, _int, ctypes.c_long, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dfh_pool_features_tile": (_int, [_c_int_p]),
 }
 
 _lib = None

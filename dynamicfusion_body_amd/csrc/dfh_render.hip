@@ -13,6 +13,8 @@
 //   render_resolve_kernel one lane per pixel: the key -> depth (-z, the reference's storage convention) and face id; the
 //                         normal is re-interpolated from the winning face (same arithmetic as the raster pass)
 //   samples_*_kernel     the visible-surface samples (dfh_render_samples_*): see below, behind the resolve pass
+//   render_vertex_ids_kernel  one lane per pixel: the key -> the winning face's vertex with the largest perspective-correct
+//                         coordinate, and the depth as an 8-bit grey level (dfh_render_vertex_ids, K15): behind the samples
 // Everything that decides coverage and depth runs in fp64 with -ffp-contract=off, so the numpy restatement with the same
 // operation order gives the same bits.
 #include "dfh_common.h"
@@ -458,6 +460,44 @@ __global__ __launch_bounds__(kRenderBlock) void samples_emit_kernel(const double
     }
 }
 
+// ---- K15  vertex ids and the network's input image (dfh_render_vertex_ids) ---------------------------------------------------
+// One lane per pixel over the key buffer, like the resolve pass: the winning face's set-up and weights again, the vertex with
+// the largest perspective-correct coordinate (the reference's fragment shader rule), and the depth as an 8-bit grey level.
+__global__ __launch_bounds__(kRenderBlock) void render_vertex_ids_kernel(const double *__restrict__ verts, const int *__restrict__ faces,
+                                                                         RenderParams p, const unsigned long long *__restrict__ keys,
+                                                                         double znear_img, double zfar_img, int *__restrict__ vid_out,
+                                                                         unsigned char *__restrict__ image_out) {
+    const long i = (long)blockIdx.x * kRenderBlock + threadIdx.x;
+    const long hw = (long)p.H * p.W;
+    if (i >= (long)p.nv * hw) return;
+    const unsigned long long key = keys[i];
+    int vid = -1;
+    int grey = 0;
+    if (key != kRenderEmpty) {
+        const long f = (long)(unsigned)(key & 0xFFFFFFFFull);
+        const float d = __uint_as_float((unsigned)(key >> 32));
+        if ((double)d >= znear_img && (double)d <= zfar_img) {
+            const float zf = (float)zfar_img, zn = (float)znear_img;
+            const float g = ((zf - d) / (zf - zn)) * 255.0f;
+            grey = (int)g;                                   // truncation; the float32 images of the two bounds can put g a hair
+            grey = grey < 0 ? 0 : (grey > 255 ? 255 : grey); // outside [0, 255]
+            const int view = (int)(i / hw);
+            const long pix = i - (long)view * hw;
+            const int y = (int)(pix / p.W), x = (int)(pix - (long)y * p.W);
+            Tri t;
+            double l[3];
+            // (always true with the raster call's mesh and views: this face wrote the key; another mesh gets -1, not a wild read)
+            if (f < p.nfaces && render_setup(p, p.view[view], verts, faces, f, t) && render_bary(t, x, y, l)) {
+                const double a0 = l[0] / t.z[0], a1 = l[1] / t.z[1], a2 = l[2] / t.z[2];
+                const int w = (a0 > a1 && a0 > a2) ? 0 : (a1 > a2 ? 1 : 2);
+                vid = faces[3 * f + w];
+            }
+        }
+    }
+    vid_out[i] = vid;
+    if (image_out) image_out[i] = (unsigned char)grey;
+}
+
 struct SamplesWorkspace {
     int *block_cnt, *block_off;
     long *chunk_tot, *chunk_base;
@@ -607,6 +647,27 @@ int dfh_render_samples_emit(const double *verts, const double *canon_pos, const 
     hipLaunchKernelGGL(samples_emit_kernel, dim3((unsigned)((rows + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0, s, verts,
                        canon_pos, canon_nrm, faces, p, (const unsigned long long *)w.keys, (const long *)sw.chunk_base, (int)sw.nchunks,
                        capacity, (const long *)pixel_out, pos_out, nrm_out);
+    DFH_HIP_CHECK(hipGetLastError());
+    return DFH_OK;
+}
+
+int dfh_render_vertex_ids(const double *verts, long n_verts, const int *faces, long n_faces, int n_views, const double *K, const double *lw,
+                          int H, int W, double scale, const double center[3], double half, double znear, const void *workspace,
+                          size_t workspace_bytes, double znear_img, double zfar_img, int *vid_out, unsigned char *image_out, void *stream) {
+    using namespace dfh;
+    RenderParams p;
+    const int rc = render_params("dfh_render_vertex_ids", n_views, K, lw, H, W, n_verts, n_faces, scale, center, half, znear, p);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(std::isfinite(znear_img) && std::isfinite(zfar_img) && zfar_img > znear_img,
+                "dfh_render_vertex_ids: the image range needs finite znear_img < zfar_img");
+    DFH_REQUIRE(workspace, "dfh_render_vertex_ids: null workspace");
+    DFH_REQUIRE(workspace_bytes >= dfh_render_workspace_bytes(n_views, H, W, n_faces), "dfh_render_vertex_ids: workspace too small");
+    DFH_REQUIRE(vid_out, "dfh_render_vertex_ids: null output");
+    DFH_REQUIRE(n_faces == 0 || (faces && verts), "dfh_render_vertex_ids: null mesh");
+    const RenderWorkspace w = render_workspace(n_views, H, W, n_faces, const_cast<void *>(workspace));
+    const long npix = (long)n_views * H * W;
+    hipLaunchKernelGGL(render_vertex_ids_kernel, dim3((unsigned)((npix + kRenderBlock - 1) / kRenderBlock)), dim3(kRenderBlock), 0,
+                       (hipStream_t)stream, verts, faces, p, (const unsigned long long *)w.keys, znear_img, zfar_img, vid_out, image_out);
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;
 }

@@ -28,6 +28,7 @@ class Fusion:
     descriptor_fn = None         # a callable (vertices (n,3), faces (m,3) or None) -> (n, D) float32 per-vertex descriptors: stands where
                                  # the reference calls compute_correspondence(self.input, self._feature, self._sess, vertices, faces)
                                  # (core/fusion.py:280-281); with it setupCorrespondences(method='cnn') takes the reference's CNN branch
+                                 # (descriptors.PooledDescriptors(feature_fn) is that function around a per-pixel feature network)
     depth_prep = None            # a depth_prep.DepthPrep: the methods that sweep a LIST of depth maps (InitializeCanonicalSpace from
                                  # maps, updateTSDF_depths) clean the list with it first; the single-map fuseDepths stays raw
 

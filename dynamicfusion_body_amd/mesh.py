@@ -254,6 +254,34 @@ def render_samples(verts, faces, canon_pos, canon_nrm, K, lws, H, W, scale=1.0, 
     return pos, nrm, pixel
 
 
+RENDER_MAX_VIEWS = 16                                  # views per dfh_render_raster call
+
+
+def render_vertex_ids(verts, faces, K, lws, H, W, znear_img, zfar_img, scale=1.0, center=0.0, half=0.0, znear=1e-3, workspace=None):
+    """Vertex-id maps and 8-bit depth images of one triangle mesh in V views (csrc/dfh_render.hip, semantics in
+    include/dfusion_hip.h, dfh_render_vertex_ids): the mesh is rasterised as by `render` (same arguments, K one 3x3 or one per
+    view); every covered pixel whose depth lies in [znear_img, zfar_img] gets the vertex of the visible face with the largest
+    perspective-correct barycentric coordinate and the grey level trunc(255 (zfar_img - z) / (zfar_img - znear_img)).
+    Any number of views: the rasteriser takes 16 per call, the batches fill slices of one result.
+    Returns (vid (V,H,W) int32, -1 where there is none; image (V,H,W) uint8, 0 there) as CUDA tensors."""
+    require_gpu()
+    lib = _lib.load()
+    Kf, lwf, nv = _view_table(K, lws)
+    Kf, lwf = Kf.reshape(nv, 3, 3), lwf.reshape(nv, 3, 4)
+    H, W = int(H), int(W)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    V = _rows3(verts, "verts", dev)
+    vid = torch.empty((nv, H, W), dtype=torch.int32, device=dev)
+    image = torch.empty((nv, H, W), dtype=torch.uint8, device=dev)
+    for b0 in range(0, nv, RENDER_MAX_VIEWS):
+        b1 = min(nv, b0 + RENDER_MAX_VIEWS)
+        _, _, faces, msh, views, workspace = _render_args(V, faces, Kf[b0:b1], lwf[b0:b1], H, W, scale, center, half, znear, workspace)
+        _lib.check(lib.dfh_render_raster(*msh, *views, current_stream_ptr()), "dfh_render_raster")
+        _lib.check(lib.dfh_render_vertex_ids(*msh, *views, float(znear_img), float(zfar_img), vid[b0:b1].data_ptr(), image[b0:b1].data_ptr(),
+                                             current_stream_ptr()), "dfh_render_vertex_ids")
+    return vid, image
+
+
 def depth_error(rendered, observed, gate):
     """Rendered against observed depth maps (reference storage convention: negative, 0 = none), per view: a list of dicts
     {n_valid: pixels valid in both, n_within: those with |difference| <= gate, mean, median: of |difference| over the valid

@@ -847,6 +847,54 @@ int dfh_nearest_descriptors(const float *query, long n_query, const float *base,
  * for tests that put sizes on those edges. */
 int dfh_nearest_descriptors_tile(int tile[4]);
 
+/* ---- K15  rendered-view descriptors: vertex ids, the network's input image, features pooled onto vertices --------------------
+ * The reference's compute_correspondence (core/sdf.py:95-150) without its network: the mesh is rendered from a ring of cameras
+ * with a vertex id in every pixel, each depth buffer becomes an 8-bit image, a per-pixel feature network (the caller's) runs on
+ * the images, and every vertex takes the mean of the features of its pixels over all views.
+ *
+ * dfh_render_vertex_ids: after dfh_render_raster with the same mesh, views and workspace (as dfh_render_samples_* are).
+ * Semantics (restated in numpy by tests/pool_np.py; fp64 unless said otherwise, no fused multiply-add, operations in the order
+ * written).  For each pixel whose key is not the empty key:
+ *  - f = the low 32 bits of the key, d = the float32 in its high bits (the camera depth z of the raster pass).
+ *  - lambda_i, z_i = the rasterizer's barycentric weights and vertex depths of face f in that view at the pixel (the set-up and
+ *    edge values above); a_i = lambda_i / z_i, the perspective-correct coordinates up to a common factor.
+ *  - The winner is the reference's fragment-shader rule, i = (a0 > a1 && a0 > a2) ? 0 : (a1 > a2 ? 1 : 2): the corner with the
+ *    largest coordinate; a tie between 0 and 1 goes to 1, every tie that involves corner 2 at the top goes to 2.
+ *    vid = faces[f][i].
+ *  - image, in float32 with one rounding per operation, zf = (float)zfar_img, zn = (float)znear_img:
+ *    g = ((zf - d) / (zf - zn)) * 255, image = (uint8)g truncated toward zero (and clamped to [0, 255]: the float32 images of
+ *    the bounds can put g a rounding outside).  The reference's expression on a GL depth buffer is algebraically the same.
+ * A pixel whose key is empty, or whose d lies outside [znear_img, zfar_img] (compared in fp64), gets vid = -1 and image = 0
+ * (the reference's background also maps to 0).  GL clips such fragments and shows what lies behind them; that is not
+ * reproduced.  vid_out: V x H x W int32; image_out: V x H x W uint8, may be NULL.  Only enqueues on `stream`.
+ * DFH_E_BADARG before any HIP call: null required pointers, sizes the raster call refuses, a workspace smaller than its size
+ * query, zfar_img <= znear_img or either of them not finite. */
+int dfh_render_vertex_ids(const double *verts, long n_verts, const int *faces, long n_faces, int n_views, const double *K, const double *lw,
+                          int H, int W, double scale, const double center[3], double half, double znear, const void *workspace,
+                          size_t workspace_bytes, double znear_img, double zfar_img, int *vid_out, unsigned char *image_out, void *stream);
+
+/* dfh_pool_features: the ordered segmented mean (core/sdf.py:138-149).  vid (n_pixels int32) and feat (n_pixels x dim float32,
+ * row-major) are device arrays; any id outside [0, n_verts) means "no vertex".  For every vertex v (restated in numpy by
+ * tests/pool_np.py):
+ *   cnt_out[v]     = the number of p with vid[p] == v
+ *   acc            = +0.0f;  acc = acc + feat[p][c] over those p in ASCENDING order, float32, one rounding per addition
+ *   feat_out[v][c] = acc / (float)cnt_out[v] (an IEEE float32 division) if cnt_out[v] > 0, else +0.0f
+ * NaN and infinities propagate as the additions make them.  The output is a function of the input alone, bit-identical from
+ * run to run: no floating-point atomic; one integer atomic per pixel counts and hands out a slot, every segment is then put into ascending pixel
+ * order (in LDS up to tile[2] entries, by an ordered walk over vid beyond that) before one lane per channel sums it.
+ * feat_out: n_verts x dim float32; cnt_out: n_verts int32.  workspace: dfh_pool_features_workspace_bytes(n_pixels, n_verts)
+ * bytes of device memory, 16-byte aligned (0 for unusable sizes and when either count is 0: no workspace is needed then).
+ * Only enqueues on `stream`, no host synchronisation.  n_pixels == 0: DFH_OK, zeros and cnt = 0 written.
+ * DFH_E_BADARG before any HIP call: dim outside 1..64; n_pixels or n_verts negative or >= 2^31; null vid / feat (with pixels),
+ * null feat_out / cnt_out (with vertices); a null, misaligned or too small workspace (with both). */
+size_t dfh_pool_features_workspace_bytes(long n_pixels, long n_verts);
+int dfh_pool_features(const int *vid, const float *feat, long n_pixels, int dim, long n_verts, float *feat_out, int *cnt_out,
+                      void *workspace, size_t workspace_bytes, void *stream);
+/* dfh_pool_features_tile: tile[0] = pixels per workgroup of the count and scatter passes, tile[1] = vertices per workgroup of
+ * the scan, tile[2] = the longest segment ordered in LDS (longer ones take the ordered walk), tile[3] = pixels per step of
+ * that walk; for tests that put sizes on those edges. */
+int dfh_pool_features_tile(int tile[4]);
+
 #ifdef __cplusplus
 }
 #endif
