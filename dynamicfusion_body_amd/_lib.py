@@ -92,16 +92,25 @@ class NormalGate(ctypes.Structure):
     _fields_ = [("normals", _vp), ("min_cos", _dbl)]
 
 
+class Landmarks(ctypes.Structure):
+    """dfh_gn_landmarks: the point-to-point landmark term -- landmarks sorted by node tuple, their plan and the term's settings."""
+    _fields_ = [("pos", _vp), ("nbr", _vp), ("weights", _vp), ("target", _vp), ("valid", _vp), ("conf", _vp), ("n", _int),
+                ("weight", _dbl), ("huber_delta", _dbl), ("max_dist", _dbl),
+                ("run_id", _vp), ("n_rows", _int), ("partial", _vp), ("blk_ptr", _vp), ("blk_ent", _vp), ("node_ptr", _vp),
+                ("node_ent", _vp), ("active_out", _vp)]
+
+
 _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
 _volume_p = ctypes.POINTER(Volume)
 _term_p = ctypes.POINTER(VolumeTerm)
 _gate_p = ctypes.POINTER(NormalGate)
+_landmarks_p = ctypes.POINTER(Landmarks)
 STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams, "dfh_slab": Slab,
            "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes,
            "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams,
-           "dfh_gn_normal_gate": NormalGate}
+           "dfh_gn_normal_gate": NormalGate, "dfh_gn_landmarks": Landmarks}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -149,6 +158,8 @@ _SIGNATURES = {
     "dfh_gn_associate_gated": (_int, [_problem_p, _frame_p, _gate_p, _vp]),
     "dfh_gn_build_gated": (_int, [_problem_p, _frame_p, _gate_p, _vp]),
     "dfh_gn_solve_gated": (_int, [_problem_p, _frame_p, _gate_p, ctypes.POINTER(SolveParams), _vp]),
+    "dfh_gn_add_landmarks": (_int, [_problem_p, _landmarks_p, _vp]),
+    "dfh_gn_solve_landmarks": (_int, [_problem_p, _frame_p, _landmarks_p, ctypes.POINTER(SolveParams), _vp]),
     "dfh_gn_global_sampled_gated": (_int, [_problem_p, _frame_p, _gate_p, _int, _dbl, _int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dfh_gn_pack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "dfh_gn_unpack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),

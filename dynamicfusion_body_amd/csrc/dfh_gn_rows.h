@@ -383,6 +383,30 @@ inline AssocArgs assoc_args(const dfh_gn_problem &p, const dfh_gn_frame &f, bool
     aa.cull = cull && f.n_views >= 4 && !on(opt().gn_no_view_cull) ? 1 : 0;
     return aa;
 }
+// ... and of a landmark term (dfh_gn_landmarks; a NaN fails every comparison it meets)
+inline int check_landmarks(const char *what, const dfh_gn_landmarks *l) {
+    DFH_REQUIRE(l, "%s: null landmarks", what);
+    DFH_REQUIRE(l->n >= 0, "%s: negative landmark count", what);
+    DFH_REQUIRE(l->weight >= 0.0 && l->weight < __builtin_huge_val(), "%s: landmark weight negative or not finite", what);
+    DFH_REQUIRE(l->huber_delta >= 0.0, "%s: landmark huber_delta negative or NaN", what);
+    DFH_REQUIRE(l->max_dist == l->max_dist, "%s: landmark max_dist is NaN", what);
+    if (l->n > 0) {
+        DFH_REQUIRE(l->pos && l->nbr && l->weights && l->target, "%s: null landmark pointer", what);
+        DFH_REQUIRE(l->n_rows >= 1 && l->run_id && l->partial && l->blk_ptr && l->blk_ent && l->node_ptr && l->node_ent,
+                    "%s: null landmark plan array", what);
+    }
+    return DFH_OK;
+}
+
+// The launch of gn_gather_kernel<knn> (dfh_solve.hip) for callers outside that file: the rows of `partial` (live flags behind the
+// per-tile {cost, count} pairs `cc`) summed through the lists into vals / rhs / cost_count; no regulariser lists, every part.
+int gn_gather_launch(int knn, const double *partial, const double *live, int n_rows, const int *blk_ptr, const int *blk_ent, int n_blocks,
+                     const int *node_ptr, const int *node_ent, int n_nodes, double *vals, double *rhs, double *cost_count, const double *cc,
+                     int n_cc, bool accumulate, const int *upper, int n_upper, void *stream);
+
+// The landmark term added to the problem's system (dfh_landmarks.hip); both structs are checked by the caller.
+int gn_add_landmarks_impl(const dfh_gn_problem &q, const dfh_gn_landmarks &l, void *stream);
+
 inline GatedAssocArgs gated_assoc_args(const dfh_gn_problem &p, const dfh_gn_frame &f, const dfh_gn_normal_gate &g, bool cull) {
     GatedAssocArgs ga;
     static_cast<AssocArgs &>(ga) = assoc_args(p, f, cull);

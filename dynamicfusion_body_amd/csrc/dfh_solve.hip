@@ -928,6 +928,28 @@ __global__ __launch_bounds__(256) void gn_build_reg_kernel(const int *__restrict
     gn_reg_pairs((int)blockIdx.x, node_nbr, N, k, node_dq, node_pos, node_w, rw, row_ptr, col, vals, rhs, cost_count, partial_reg);
 }
 
+// gn_gather_kernel<knn> for a term built outside this file (the landmark rows, dfh_landmarks.hip): the instantiations above, no
+// regulariser lists, every part of the gather.
+int gn_gather_launch(int knn, const double *partial, const double *live, int n_rows, const int *blk_ptr, const int *blk_ent, int n_blocks,
+                     const int *node_ptr, const int *node_ent, int n_nodes, double *vals, double *rhs, double *cost_count, const double *cc,
+                     int n_cc, bool accumulate, const int *upper, int n_upper, void *stream) {
+    const int2 *up = (upper && n_upper > 0) ? reinterpret_cast<const int2 *>(upper) : nullptr;
+    const int n_walk = up ? n_upper : n_blocks;
+    dim3 grid((unsigned)((n_walk + 3) / 4 + (n_nodes + 3) / 4 + 1)), block(256);
+#define DFH_GATHER_TERM(KK)                                                                                         \
+    case KK:                                                                                                        \
+        hipLaunchKernelGGL(gn_gather_kernel<KK>, grid, block, 0, (hipStream_t)stream, partial, live, n_rows, blk_ptr, blk_ent, n_blocks, \
+                           node_ptr, node_ent, n_nodes, vals, rhs, cost_count, cc, n_cc, 2, accumulate, 0, RegLists{}, up, n_upper);    \
+        break
+    switch (knn) {
+        DFH_GATHER_TERM(1); DFH_GATHER_TERM(2); DFH_GATHER_TERM(3); DFH_GATHER_TERM(4);
+        DFH_GATHER_TERM(5); DFH_GATHER_TERM(6); DFH_GATHER_TERM(7); DFH_GATHER_TERM(8);
+    }
+#undef DFH_GATHER_TERM
+    DFH_HIP_CHECK(hipGetLastError());
+    return DFH_OK;
+}
+
 }  // namespace dfh
 
 // =================================================================================== C ABI
@@ -1263,7 +1285,9 @@ int dfh_debug_gather_trace(unsigned long long *out) {
 #endif
 
 // The body of dfh_gn_solve / dfh_gn_solve_volume: the problem, its plan and the association's arguments are checked by the caller.
-static int gn_solve_impl(const char *what, const dfh_gn_problem &q, const BuildAssoc &ba, const dfh_gn_solve_params *params, void *stream) {
+// lm (optional): a checked landmark term, added to the system after every build (dfh_gn_solve_landmarks); NULL: none.
+static int gn_solve_impl(const char *what, const dfh_gn_problem &q, const BuildAssoc &ba, const dfh_gn_solve_params *params, void *stream,
+                         const dfh_gn_landmarks *lm = nullptr) {
     using namespace dfh;
     DFH_REQUIRE(params, "%s: null params", what);
     const dfh_gn_solve_params &sp = *params;
@@ -1275,6 +1299,7 @@ static int gn_solve_impl(const char *what, const dfh_gn_problem &q, const BuildA
     int rc;
     for (int g = 0; g < sp.n_global; ++g) {
         rc = gn_build_impl(q, ba, stream);
+        if (rc == DFH_OK && lm) rc = gn_add_landmarks_impl(q, *lm, stream);
         if (rc != DFH_OK) return rc;
         rc = dfh_gn_global_step(q.vals, q.n_blocks, q.rhs, q.n_nodes, sp.global_lm, q.node_dq, sp.global_xi_out, sp.global_scratch,
                                 sp.global_scratch_bytes, stream);
@@ -1287,6 +1312,7 @@ static int gn_solve_impl(const char *what, const dfh_gn_problem &q, const BuildA
     for (int it = 0; it < sp.n_iters; ++it) {
         bool zeroed = false;
         rc = gn_build_impl(q, ba, stream, on(opt().gn_iter_own_clear) ? nullptr : zbegin, zcount, &zeroed);
+        if (rc == DFH_OK && lm) rc = gn_add_landmarks_impl(q, *lm, stream);
         if (rc != DFH_OK) return rc;
         rc = pcg_solve_impl(q.row_ptr, q.col, q.vals, q.rhs, q.n_nodes, sp.pcg_iters, sp.lm_abs, sp.lm_rel, sp.x_out, sp.pcg_workspace,
                             sp.pcg_workspace_bytes, q.node_dq, sp.step, stream, zeroed);
@@ -1303,6 +1329,20 @@ int dfh_gn_solve(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const
     DFH_REQUIRE(problem->blk_ptr, "dfh_gn_solve: null blk_ptr (the fused association needs a plan)");
     const AssocArgs aa = assoc_args(*problem, *frame, true);
     return gn_solve_impl("dfh_gn_solve", *problem, BuildAssoc{&aa, nullptr}, params, stream);
+}
+
+int dfh_gn_solve_landmarks(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_landmarks *landmarks,
+                           const dfh_gn_solve_params *params, void *stream) {
+    using namespace dfh;
+    const char *what = "dfh_gn_solve_landmarks";
+    int rc = check_problem(what, problem, true);
+    if (rc == DFH_OK && frame) rc = check_frame(what, frame, true);
+    if (rc == DFH_OK) rc = check_landmarks(what, landmarks);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(problem->blk_ptr, "dfh_gn_solve_landmarks: null blk_ptr (the solve needs a plan)");
+    if (!frame) return gn_solve_impl(what, *problem, BuildAssoc{nullptr, nullptr}, params, stream, landmarks);
+    const AssocArgs aa = assoc_args(*problem, *frame, true);
+    return gn_solve_impl(what, *problem, BuildAssoc{&aa, nullptr}, params, stream, landmarks);
 }
 
 int dfh_gn_solve_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate,

@@ -50,6 +50,7 @@ class Fusion:
         self._nodes = []
         self._neighbor_look_up = []
         self._correspondences = []
+        self.landmark_weight = 0.0               # > 0: solve() also uses the correspondences as POINTS (WarpSolver.set_landmarks)
         self._vertices = None
         self._normals = None
         self._kdtree = None
@@ -398,6 +399,11 @@ class Fusion:
             s_.set_graph(pos, dq, w, node_nbr=nbr[vidx])
             s_.set_samples(V, Nn, nbr=nbr)
             s_.set_correspondences(C)
+            if float(self.landmark_weight) > 0.0:
+                # the correspondences as 3-D constraints beside their point-to-plane rows (with method='cnn' and descriptors: the
+                # feature matches of setupCorrespondences, which are what stops motion inside the surface)
+                s_.landmark_weight = float(self.landmark_weight)
+                s_.set_landmarks(V, C, nbr=nbr)
             return s_
 
         sv = make_solver()

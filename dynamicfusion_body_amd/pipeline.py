@@ -86,6 +86,22 @@ class FrameSolver:
         node_nbr, _ = sample_knn(node_pos, node_pos, node_w, self.knn)        # a node's own k nearest nodes
         self.solver.set_graph(node_pos, node_dq, node_w, node_nbr=node_nbr)
 
+    def set_landmarks(self, pos, target, conf=None, weight=1.0, huber=0.0, max_dist=0.0):
+        """The landmark term of the solve (WarpSolver.set_landmarks): canonical points `pos` with live 3-D targets `target`, both in
+        index space, as three point-to-point rows each of weight `weight` (x conf), with the vector Huber delta `huber` and the
+        gate `max_dist` on |x' - c| in voxels.  Every build of this solver adds them until clear_landmarks() or a new graph."""
+        sv = self.solver
+        sv.landmark_weight, sv.landmark_huber, sv.landmark_max_dist = float(weight), float(huber), float(max_dist)
+        sv.set_landmarks(pos, target, conf=conf)
+
+    def clear_landmarks(self):
+        self.solver.clear_landmarks()
+
+    def landmarks_active(self):
+        """True while the builds add a landmark term."""
+        sv = self.solver
+        return sv._lm is not None and sv._lm["L"] > 0 and float(sv.landmark_weight) != 0.0
+
     def set_canonical(self, T, Wt, band=1.0, x0=0, max_samples=None, knn_bricks=None):
         """knn_bricks: see solve.sample_knn (candidate lists of the K3 workspace: the samples' node search skips its
         per-workgroup bounding-box pass)."""
@@ -216,12 +232,33 @@ class SlabFrame:
         self.knn_bricks = None
         self._first = True
         self.ident_lw = np.array([1.0, 0, 0, 0, 0, 0, 0, 0])
+        self._landmarks = None                   # set_landmarks()'s arguments: handed to the solver again after a graph change
         self.has_graph = node_pos is not None    # False: everything that depends on the graph waits for construct_graph()
         if self.has_graph:
             N = len(node_pos)
             ident = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0, 0]), (N, 1))
             self.fs.set_graph(node_pos, ident, node_w)
             self._graph_workspaces(node_pos, N)
+
+    def set_landmarks(self, canon_pos, target, conf=None, weight=1.0, huber=0.0, max_dist=0.0):
+        """Feature correspondences as 3-D constraints of every following step()'s solve (FrameSolver.set_landmarks): canonical
+        points `canon_pos` (L, 3) and their live targets (L, 3) in index space, conf (L,) optional.  They survive the sample refresh
+        at the end of a step and are handed to the solver again when the graph changes (construct_graph, update_graph: their
+        node tuples are searched anew).  While they are set, the rigid-mode steps of step() come from the BUILT system (the sampled
+        steps read the data rows only and would not see them).  Every rank passes the same landmarks."""
+        self._landmarks = (canon_pos, target, conf, float(weight), float(huber), float(max_dist))
+        if self.has_graph:
+            self.fs.set_landmarks(*self._landmarks)
+
+    def clear_landmarks(self):
+        self._landmarks = None
+        self.fs.clear_landmarks()
+
+    def _set_graph(self, node_pos, node_dq, node_w):
+        """FrameSolver.set_graph, then the landmarks again (a new graph drops the solver's: their node tuples were the old graph's)."""
+        self.fs.set_graph(node_pos, node_dq, node_w)
+        if self._landmarks is not None:
+            self.fs.set_landmarks(*self._landmarks)
 
     @staticmethod
     def _check_normal_gate(normal_gate, depth_prep):
@@ -304,7 +341,7 @@ class SlabFrame:
             raise ValueError("construct_graph: %d band samples gave %d nodes, fewer than knn = %d" % (pts.shape[0], N, self.knn))
         ident = torch.zeros((N, 8), dtype=torch.float64, device="cuda")
         ident[:, 0] = 1.0
-        self.fs.set_graph(nodes, ident, torch.full((N,), 2.0 * radius, dtype=torch.float64, device="cuda"))
+        self._set_graph(nodes, ident, torch.full((N,), 2.0 * radius, dtype=torch.float64, device="cuda"))
         self.has_graph = True
         self._graph_workspaces(nodes, N)
         self.refresh_samples()
@@ -391,7 +428,7 @@ class SlabFrame:
                                                                     sampler=sampler)
         if n_new == 0:
             return 0
-        self.fs.set_graph(P2, Q2, W2)                    # resets the block pattern; node-node table of the regulariser rebuilt
+        self._set_graph(P2, Q2, W2)                      # resets the block pattern; node-node table of the regulariser rebuilt
         self._graph_workspaces(P2, int(P2.shape[0]))
         self.refresh_samples()
         return n_new
@@ -566,6 +603,7 @@ class SlabFrame:
         # the rigid mode first (two steps: one twist shared by all nodes, fitted to the data rows -- FrameSolver.global_iteration),
         # then the node iterations (one host call: nothing between their launches depends on the host)
         ng = self.GLOBAL_ITERS if global_iters is None else int(global_iters)
+        lm_on = self.fs.landmarks_active()     # (landmarks: the rigid-mode steps from the built system, which holds their rows)
         live_full = None
         if data_term == "volume":
             # the solve reads the live volume: the side stream (which has overlapped the plan's launches) joins here, and the
@@ -578,19 +616,19 @@ class SlabFrame:
             # strict, so the cells that touch a voxel no view updated drop out
             band = float(torch.tensor(self.tvox, dtype=self.live.dtype))
             if ng > 0:
-                sampled = global_built is not None and not global_built
+                sampled = global_built is not None and not global_built and not lm_on
                 self.fs.global_iteration_volume(live_full, band, rw=rw, max_dist=max_dist, huber=huber, lm_rel=global_lm, n_iters=ng,
                                                 built=not sampled, stride=self.GLOBAL_STRIDE if global_stride is None else int(global_stride))
             self.fs.gn_iteration_volume(live_full, band, rw=rw, lm_abs=lm_abs, lm_rel=lm_rel, max_dist=max_dist, huber=huber,
                                         n_iters=gn_iters)
-        elif ng > 0:
+        elif ng > 0 and not lm_on:
             # (every `global_stride`-th tile of THIS rank's samples: with the samples sharded over ranks a stride > 1 thins another
             # subsample than one GPU does -- the same estimator on other data; stride 1 is partition-independent)
             self.fs.global_iteration(solve_depth, solve_lw, max_dist=max_dist, huber=huber, lm_rel=global_lm, n_iters=ng,
                                      stride=self.GLOBAL_STRIDE if global_stride is None else int(global_stride), **gate_kw)
         if data_term == "depth":
             self.fs.gn_iteration(solve_depth, solve_lw, rw=rw, lm_abs=lm_abs, lm_rel=lm_rel, max_dist=max_dist, huber=huber, n_iters=gn_iters,
-                                 **gate_kw)
+                                 n_global=ng if lm_on else 0, global_lm=global_lm, **gate_kw)
         mark("solve")
         if not joined:
             torch.cuda.current_stream().wait_stream(self._side)

@@ -300,6 +300,8 @@ class WarpSolver:
                   block pattern of J^T J
     set_correspondences() / associate_depth() / associate_volume()  fixed correspondences, projective association against
                   depth maps, or association against a live TSDF volume
+    set_landmarks()  optional point-to-point rows (canonical points with live 3-D targets: feature matches), added to every
+                  build while landmark_weight != 0
     step()        one iteration: build -> PCG -> twist update (asynchronous)
     """
 
@@ -316,7 +318,14 @@ class WarpSolver:
         self._prob, self._frm, self._sp = _lib.Problem(), _lib.Frame(), _lib.SolveParams()     # the C ABI's structs, refilled per call
         self._term = _lib.VolumeTerm()
         self._gate_s = _lib.NormalGate()
-        if _dist.ranks_share_a_gpu():                  # (whether or not THIS solver runs collectives: ADVICE round 2)
+        # the landmark term (set_landmarks; off while landmark_weight is 0): weight of a landmark's three rows, the delta of the
+        # vector Huber loss on |x' - c| (0: plain least squares) and the gate on |x' - c| in voxels (<= 0: none)
+        self._lm_s = _lib.Landmarks()
+        self._lm = None
+        self.landmark_weight = 0.0
+        self.landmark_huber = 0.0
+        self.landmark_max_dist = 0.0
+        if _dist.ranks_share_a_gpu():                 # (whether or not THIS solver runs collectives: ADVICE round 2)
             # several processes time-share this GPU (a rehearsal of the multi-GPU job on one card): co-residency of the
             # persistent PCG's workgroups is not guaranteed across processes -> two launches per iteration, no grid barrier
             _lib.check(self.lib.dfh_pcg_set_mode(2), "dfh_pcg_set_mode")
@@ -347,8 +356,166 @@ class WarpSolver:
         self.node_nbr = None if node_nbr is None else _i32(node_nbr, (self.knn,))
         self._pattern = None
         self._pattern_keys = None
+        self._lm = None                               # (landmarks hold node tuples of the old graph)
 
-    # -- samples -----------------------------------------------------------------------------
+    # -- landmarks ---------------------------------------------------------------------------
+    def set_landmarks(self, pos, target, conf=None, valid=None, nbr=None, weights=None):
+        """The landmark term's points (dfh_gn_landmarks): canonical positions `pos` (L, 3) with live targets `target` (L, 3), both
+        in index space; conf (L,): per-landmark confidence multiplying landmark_weight; valid (L,): 0 drops a landmark.  Their k
+        nearest nodes and static blend weights are computed as for samples unless nbr / weights are given.  The landmarks are
+        sorted by node tuple (the permutation is kept: landmark_active() answers in the caller's order) and planned with the next
+        build; the block pattern grows where a landmark tuple needs it.  The term is added while landmark_weight != 0."""
+        pos, target = _f64(pos, (3,)), _f64(target, (3,))
+        if pos.shape[0] != target.shape[0]:
+            raise ValueError("landmark positions and targets disagree in length")
+        L = pos.shape[0]
+        if nbr is None:
+            nbr, weights = sample_knn(pos, self.node_pos, self.node_w, self.knn)
+        else:
+            nbr = _i32(nbr, (self.knn,))
+            if weights is None:
+                d = pos[:, None, :] - self.node_pos[nbr.long()]
+                dist = torch.sqrt((d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2])
+                weights = torch.exp(-1.0 * (dist / (2 * self.node_w[nbr.long()])) ** 2)
+            weights = _f64(weights, (self.knn,))
+        if nbr.shape[0] != L or weights.shape[0] != L:
+            raise ValueError("landmark neighbour table / weights disagree with the positions in length")
+        order = None
+        if L > 0:
+            key = self._pack_tuples(nbr)
+            if key is not None:
+                _, order = torch.sort(key, stable=True)
+            else:
+                _, inv = torch.unique(nbr, dim=0, return_inverse=True)
+                order = torch.argsort(inv, stable=True)
+            pos, nbr, weights = pos[order], nbr[order], weights[order]
+        self._lm = {"L": L, "order": order, "pos": pos.contiguous(), "nbr": nbr.contiguous(), "wts": weights.contiguous(),
+                    "packed": L > 0 and float(self.N) ** self.knn < 2.0 ** 62, "plan": None, "plan_keys": None,
+                    "active": torch.zeros(L, dtype=torch.uint8, device="cuda")}
+        self.set_landmark_targets(target, valid, conf)
+        self._pattern = None
+
+    def set_landmark_targets(self, target, valid=None, conf=None):
+        """New targets (and validity / confidence) for the landmarks of set_landmarks, in the caller's order: no replanning."""
+        lm = self._lm
+        if lm is None:
+            raise ValueError("set_landmarks first")
+
+        def take(a, conv, what):
+            if a is None:
+                return None
+            t = conv(a)
+            if t.shape[0] != lm["L"]:
+                raise ValueError("landmark %s disagree with the landmarks in length" % what)
+            return (t[lm["order"]] if lm["order"] is not None else t.clone()).contiguous()
+
+        def u8(a):
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+            return (t != 0).to(device="cuda", dtype=torch.uint8).reshape(-1)
+
+        lm["target"] = take(target, lambda a: _f64(a, (3,)), "targets")
+        lm["valid"] = take(valid, u8, "validity flags")
+        lm["conf"] = take(conf, lambda a: _f64(a, ()), "confidences")
+        if lm["target"] is None:
+            raise ValueError("landmark targets are required")
+
+    def clear_landmarks(self):
+        self._lm = None
+
+    def landmark_active(self):
+        """uint8 (L,), the caller's order: 1 where the landmark was active in the last build that added the term."""
+        lm = self._lm
+        if lm is None:
+            raise ValueError("set_landmarks first")
+        out = torch.empty_like(lm["active"])
+        if lm["order"] is not None:
+            out[lm["order"]] = lm["active"]
+        return out
+
+    def _landmark_pair_keys(self):
+        """Node-pair keys a * N + b of every landmark tuple (what the block pattern has to contain), or None."""
+        lm = self._lm
+        if lm is None or lm["L"] == 0:
+            return None
+        tup = torch.unique_consecutive(lm["nbr"], dim=0).long()
+        return (tup[:, :, None] * self.N + tup[:, None, :]).reshape(-1)
+
+    def _build_landmark_plan(self, keys):
+        """The landmarks' data plan against the pattern `keys` (which row_ptr / col describe): dfh_gn_plan_count / _build on their
+        sorted tuples, as for samples.  Returns whether every node pair of every landmark tuple is a block of the pattern."""
+        lm = self._lm
+        if lm is None or lm["L"] == 0:
+            return True
+        if lm["plan_keys"] is keys:                   # (planned against this very pattern, and covered by it)
+            return True
+        N, k, L, dev = self.N, self.knn, lm["L"], "cuda"
+        tile = int(self.lib.dfh_gn_tile_samples())
+        n_tiles = (L + tile - 1) // tile
+        nbr = lm["nbr"]
+        if lm["packed"] and not _lib.opt_on("py_plan_torch"):
+            tile_off = torch.empty(n_tiles + 1, dtype=torch.int32, device=dev)
+            n_rows_d = torch.empty(1, dtype=torch.int32, device=dev)
+            _lib.check(self.lib.dfh_gn_plan_count(nbr.data_ptr(), L, k, tile_off.data_ptr(), n_rows_d.data_ptr(), current_stream_ptr()),
+                       "dfh_gn_plan_count")
+            R = int(n_rows_d.item())
+            if R * k * k >= 2 ** 31:
+                raise ValueError("too many landmark runs for 32-bit plan entries")
+            plan = {"run_id": torch.empty(L, dtype=torch.int32, device=dev), "row_first": torch.empty(R, dtype=torch.int32, device=dev),
+                    "blk_ptr": torch.empty(self.B + 1, dtype=torch.int32, device=dev),
+                    "blk_ent": torch.empty(R * k * k, dtype=torch.int32, device=dev),
+                    "node_ptr": torch.empty(N + 1, dtype=torch.int32, device=dev), "node_ent": torch.empty(R * k, dtype=torch.int32, device=dev)}
+            unc = torch.empty(1, dtype=torch.int32, device=dev)
+            nbytes = self.lib.dfh_gn_plan_workspace_bytes(R, k)
+            ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+            _lib.check(self.lib.dfh_gn_plan_build(nbr.data_ptr(), L, k, N, tile_off.data_ptr(), R, self.row_ptr.data_ptr(), self.col.data_ptr(),
+                                                  self.B, plan["run_id"].data_ptr(), plan["row_first"].data_ptr(), plan["blk_ptr"].data_ptr(),
+                                                  plan["blk_ent"].data_ptr(), plan["node_ptr"].data_ptr(), plan["node_ent"].data_ptr(),
+                                                  unc.data_ptr(), ws.data_ptr(), ws.numel() * 8, current_stream_ptr()), "dfh_gn_plan_build")
+            covered = int(unc.item()) == 0
+        else:
+            head = torch.ones(L, dtype=torch.bool, device=dev)
+            head[1:] = (nbr[1:] != nbr[:-1]).any(dim=1)
+            head[::tile] = True                       # a row never spans two tiles
+            tup = nbr[head].long()
+            R = int(tup.shape[0])
+            if R * k * k >= 2 ** 31:
+                raise ValueError("too many landmark runs for 32-bit plan entries")
+            (bp, be, npt, nent), _, cov = self._csr_lists(tup, keys)
+            plan = {"run_id": torch.cumsum(head, 0, dtype=torch.int32).sub_(1), "row_first": torch.nonzero(head).reshape(-1).to(torch.int32),
+                    "blk_ptr": bp, "blk_ent": be, "node_ptr": npt, "node_ent": nent}
+            covered = bool(cov)
+        plan["n_rows"] = R
+        ne = int(self.lib.dfh_gn_partial_doubles(k))
+        plan["partial"] = torch.empty(R * ne + 2 * n_tiles + R, dtype=torch.float64, device=dev)   # rows | {cost, 0} per tile | live flag per row
+        lm["plan"] = plan
+        lm["plan_keys"] = keys if covered else None
+        return covered
+
+    def _landmark_term(self):
+        """The landmark term as a dfh_gn_landmarks, or None while there is none to add (no landmarks, or landmark_weight 0)."""
+        lm = self._lm
+        if lm is None or lm["L"] == 0 or float(self.landmark_weight) == 0.0:
+            return None
+        if self._pattern is None:
+            self._build_pattern()
+        t, pl = self._lm_s, lm["plan"]
+        t.pos, t.nbr, t.weights, t.target = lm["pos"].data_ptr(), lm["nbr"].data_ptr(), lm["wts"].data_ptr(), lm["target"].data_ptr()
+        t.valid = 0 if lm["valid"] is None else lm["valid"].data_ptr()
+        t.conf = 0 if lm["conf"] is None else lm["conf"].data_ptr()
+        t.n, t.weight, t.huber_delta, t.max_dist = lm["L"], float(self.landmark_weight), float(self.landmark_huber), float(self.landmark_max_dist)
+        t.run_id, t.n_rows, t.partial = pl["run_id"].data_ptr(), pl["n_rows"], pl["partial"].data_ptr()
+        t.blk_ptr, t.blk_ent = pl["blk_ptr"].data_ptr(), pl["blk_ent"].data_ptr()
+        t.node_ptr, t.node_ent = pl["node_ptr"].data_ptr(), pl["node_ent"].data_ptr()
+        t.active_out = lm["active"].data_ptr()
+        return t
+
+    def _add_landmarks(self, lw_dq, upper=True):
+        """The landmark term added to the system of the build that has just been queued (dfh_gn_add_landmarks)."""
+        t = self._landmark_term()
+        if t is not None:
+            _lib.check(self.lib.dfh_gn_add_landmarks(self._problem(lw_dq, upper=upper), t, current_stream_ptr()), "dfh_gn_add_landmarks")
+
+    # -- samples-----------------------------------------------------------------------------
     def set_samples(self, pos, nrm, nbr=None, weights=None, sort=True, knn_bricks=None):
         pos, nrm = _f64(pos, (3,)), _f64(nrm, (3,))
         if pos.shape[0] != nrm.shape[0]:
@@ -454,11 +621,15 @@ class WarpSolver:
             if self.pcg_ws.numel() * 8 < nbytes:
                 self.pcg_ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device="cuda")
             covered = self._build_plan(old, reg=False, overlap=overlap)
+            covered = self._build_landmark_plan(old) and covered         # (the landmarks' tuples against the current pattern too)
             if (_dist.all_ranks(covered) if self.distributed else covered):
                 self._pattern = True
                 return
             if self.S > 0:
                 new.append(self._pair_keys_of_rows())
+            lm_keys = self._landmark_pair_keys()
+            if lm_keys is not None:
+                new.append(lm_keys)
             new.append(old)
         elif self.S > 0:
             # distinct node tuples only (the pattern is a function of the tuples, not of the samples)
@@ -468,6 +639,9 @@ class WarpSolver:
                 tup = torch.unique(self.snbr, dim=0).long()
             new.append((tup[:, :, None] * N + tup[:, None, :]).reshape(-1))
         if old is None:
+            lm_keys = self._landmark_pair_keys()
+            if lm_keys is not None:
+                new.append(lm_keys)
             new.append(torch.arange(N, device="cuda", dtype=torch.int64) * (N + 1))      # diagonal
             if self.node_nbr is not None:
                 i = torch.arange(N, device="cuda", dtype=torch.int64)[:, None].expand(N, k)
@@ -522,6 +696,7 @@ class WarpSolver:
         nbytes = self.lib.dfh_pcg_workspace_bytes(N, self.pcg_iters)
         self.pcg_ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device="cuda")
         self._build_plan(keys)
+        self._build_landmark_plan(keys)
         self._pattern = True
 
     def _build_plan(self, keys, reg=True, overlap=()):
@@ -785,6 +960,8 @@ class WarpSolver:
         reg_here = (not self.distributed) or _dist.world()[0] == 0
         t = self._volume_term(live, band, max_dist, min_grad, value_to_vox)
         _lib.check(self.lib.dfh_gn_build_volume(self._problem(lw_dq, rw, huber, reg=reg_here), t, current_stream_ptr()), "dfh_gn_build_volume")
+        if reg_here:
+            self._add_landmarks(lw_dq)
         self._allreduce_system()
 
     def iterate_volume(self, live, lw_dq, rw, band, max_dist=0.0, huber=0.0, lm_abs=0.0, lm_rel=0.0, n_iters=1, n_global=0,
@@ -800,7 +977,8 @@ class WarpSolver:
             self._build_pattern()
         one_call = (live.dtype == torch.float32 and self.S > 0 and not _lib.opt_on("py_gn_atomic") and
                     not _lib.opt_on("py_gn_no_fused_assoc") and not _lib.opt_on("py_gn_no_fused_iter") and
-                    not (self.distributed and (_dist.world()[1] > 1 or self.force_collective)))
+                    not (self.distributed and (_dist.world()[1] > 1 or self.force_collective)) and
+                    self._landmark_term() is None)        # (the landmark term has no one-call volume entry: the per-call sequence)
         per_call = one_call and _lib.opt_on("py_gn_iter_per_call")
         if not one_call or per_call:
             for _ in range(int(n_global)):
@@ -830,6 +1008,8 @@ class WarpSolver:
             raise ValueError("the atomic build (py_gn_atomic) has no Huber weights")
         _lib.check(self.lib.dfh_gn_build(self._problem(lw_dq, rw, huber, reg=reg_here, plan=not atomic, upper=False), None,
                                          current_stream_ptr()), "dfh_gn_build")
+        if reg_here:                              # (the landmarks are not sharded either: the regulariser's rank adds them)
+            self._add_landmarks(lw_dq, upper=False)
         self._allreduce_system()                  # no-op on one GPU; samples are sharded by slab
 
     def build_associated(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist=0.0, huber=0.0, normals=None,
@@ -850,6 +1030,8 @@ class WarpSolver:
             _lib.check(self.lib.dfh_gn_build_gated(prob, frame, gate, current_stream_ptr()), "dfh_gn_build_gated")
         else:
             _lib.check(self.lib.dfh_gn_build(prob, frame, current_stream_ptr()), "dfh_gn_build")
+        if reg_here:
+            self._add_landmarks(lw_dq)
         self._allreduce_system()
 
     def iterate_associated(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist=0.0, huber=0.0, lm_abs=0.0, lm_rel=0.0,
@@ -864,9 +1046,11 @@ class WarpSolver:
             self._build_pattern()
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
         gate = self._gate(normals, normal_cos, frame)
+        lmt = self._landmark_term()                   # (with landmarks: dfh_gn_solve_landmarks, the ungated depth term only)
         one_call = (frame.depth_dtype == _lib.F32 and self.S > 0 and not _lib.opt_on("py_gn_atomic") and
                     not _lib.opt_on("py_gn_no_fused_assoc") and not _lib.opt_on("py_gn_no_fused_iter") and
-                    not (self.distributed and (_dist.world()[1] > 1 or self.force_collective)))
+                    not (self.distributed and (_dist.world()[1] > 1 or self.force_collective)) and
+                    not (lmt is not None and gate is not None))
         per_call = one_call and _lib.opt_on("py_gn_iter_per_call")
         if not one_call or per_call:
             for _ in range(int(n_global)):                # the rigid mode first (global_step): one twist for all nodes
@@ -884,6 +1068,8 @@ class WarpSolver:
         for _ in range(int(n_iters) if per_call else 1):
             if gate is not None:
                 _lib.check(self.lib.dfh_gn_solve_gated(prob, frame, gate, sp, current_stream_ptr()), "dfh_gn_solve_gated")
+            elif lmt is not None:
+                _lib.check(self.lib.dfh_gn_solve_landmarks(prob, frame, lmt, sp, current_stream_ptr()), "dfh_gn_solve_landmarks")
             else:
                 _lib.check(self.lib.dfh_gn_solve(prob, frame, sp, current_stream_ptr()), "dfh_gn_solve")
 

@@ -564,6 +564,53 @@ int dfh_gn_build_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame,
 int dfh_gn_solve_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate,
                        const dfh_gn_solve_params *params, void *stream);
 
+/* The landmark term: point-to-point rows for feature correspondences (opt-in: the calls above know nothing of it).  The data rows
+ * n'.(x' - c) cannot see motion inside the surface; a landmark ties a canonical point p to a live 3-D target c with all three
+ * components of x' - c (DynamicFusion section 6, VolumeDeform's sparse term).  The reference has no counterpart (its matches feed
+ * its one point-to-plane term, core/fusion.py:282-285, 444-473).  Everything is fp64, operation by operation in this order, no
+ * contraction.  For landmark l with its knn nodes nbr[l][.] and static blend weights weights[l][.] (knn = the problem's):
+ *  1. x' = the landmark warped exactly as dfh_gn_associate warps a sample: b^ = the normalised static blend of its node DQs,
+ *     x' = dqb_warp(lw_dq, f32(dqb_warp(b^, f32(p)))).
+ *  2. d_a = x'_a - c_a (a = 0, 1, 2);  q = (d_0*d_0 + d_1*d_1) + d_2*d_2.
+ *  3. s2 = weight * conf[l] (conf == NULL: 1).  The landmark is ACTIVE iff valid[l] != 0 (valid == NULL: 1), s2 > 0, q < +inf (a NaN
+ *     fails both) and (max_dist <= 0 or q <= max_dist*max_dist).  An inactive landmark adds nothing.
+ *  4. vector Huber on |d|: if huber_delta > 0 and q > huber_delta*huber_delta: n = sqrt(q), obj = s2*huber_delta*(n - 0.5*huber_delta),
+ *     sc = sqrt(s2)*sqrt(huber_delta/n); otherwise obj = 0.5*s2*q, sc = sqrt(s2).
+ *  5. three rows, a = 0, 1, 2: residual sc*d_a, Jacobian sc*J_a, J_a = the data row's gradient (oracle/gn_np.py
+ *     data_residual_jacobian) with the warped normal replaced by the constant axis e_a and its normal-rotation (H) term dropped:
+ *     U = pure(vec(rl* e_a rl)), g_r = -2 (U r^ P + U d^), g_d = 2 U r^, then the same projection off b^, the same division by
+ *     |b|_8 and the same per-node products.
+ *  6. vals += J^T J, rhs += J^T r, cost_count[0] += sum of obj; cost_count[1] (the valid SAMPLES) is left alone.  Node pairs that
+ *     are no block of the pattern are dropped silently, as for samples.
+ * Landmarks arrive sorted by node tuple; their plan is the data plan's (dfh_gn_plan_count / dfh_gn_plan_build on the landmarks' nbr
+ * against the problem's pattern), `partial` sized as dfh_gn_problem.partial is.  No floating-point atomics: the same bits every
+ * run.  Restated in tests/landmark_np.py.
+ * dfh_gn_add_landmarks: adds the term to the system any build left in the problem (reads node_dq, lw_dq, knn, the pattern and
+ * blk_upper; adds to vals / rhs / cost_count).  dfh_gn_solve_landmarks: dfh_gn_solve (the ungated depth term) with the term added
+ * after every build, the rigid-mode steps' builds included -- the same bits as the separate calls; frame == NULL: the builds use
+ * the problem's corr / valid.  DFH_E_BADARG (before any HIP call): what dfh_gn_build / dfh_gn_solve refuse, a null struct, n < 0, with
+ * n > 0 a null pos / nbr / weights / target / run_id / partial / blk_ptr / node_ptr (or, with n_rows > 0, blk_ent / node_ent) or
+ * n_rows < 1, weight negative or not finite, huber_delta negative or NaN, max_dist NaN.  n == 0 or weight == 0: DFH_OK, nothing is
+ * launched by the term and the system is left as it is. */
+typedef struct dfh_gn_landmarks {
+    const double *pos;            /* n x 3 canonical positions (index space), sorted by node tuple */
+    const int *nbr;               /* n x knn */
+    const double *weights;        /* n x knn static blend weights */
+    const double *target;         /* n x 3 live targets (index space) */
+    const unsigned char *valid;   /* n, may be NULL (all valid) */
+    const double *conf;           /* n, may be NULL (all 1) */
+    int n;
+    double weight, huber_delta, max_dist;
+    const int *run_id;            /* the landmarks' plan, laid out as dfh_gn_problem's data plan */
+    int n_rows;
+    double *partial;
+    const int *blk_ptr, *blk_ent, *node_ptr, *node_ent;
+    unsigned char *active_out;    /* n, may be NULL: 1 iff the landmark was active (step 3) */
+} dfh_gn_landmarks;
+int dfh_gn_add_landmarks(const dfh_gn_problem *problem, const dfh_gn_landmarks *landmarks, void *stream);
+int dfh_gn_solve_landmarks(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_landmarks *landmarks,
+                           const dfh_gn_solve_params *params, void *stream);
+
 /* Multi-GPU solve: what travels in the per-iteration all-reduce.  `system` = {J^T J blocks (n_blocks x 36) | J^T r (6 n_nodes) |
  * cost, count} as the builds write it; J^T J is symmetric, so only the blocks with col >= row are packed (then J^T r and
  * {cost, count}): (36 n_upper + 6 n_nodes + 2) doubles in `packed`, about 55 % of the system.  row_of[b] / col[b]: block b's
