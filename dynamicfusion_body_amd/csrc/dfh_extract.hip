@@ -37,7 +37,7 @@ __device__ __forceinline__ bool band_sample(const VolT *__restrict__ T, const Vo
     const double gy = yh > yl ? ((double)T[x * sx + yh * sy + z] - (double)T[x * sx + yl * sy + z]) / (double)(yh - yl) : 0.0;
     const double gz = zh > zl ? ((double)T[x * sx + y * sy + zh] - (double)T[x * sx + y * sy + zl]) / (double)(zh - zl) : 0.0;
     const double n = sqrt((gx * gx + gy * gy) + gz * gz);
-    if (!(n > 1e-6)) return false;
+    if (!(n > 1e-6) || !isfinite(n)) return false;       // finite and > 1e-6: a NaN or infinite neighbour yields no sample
     if (pos) {
         const double nx = gx / n, ny = gy / n, nz = gz / n;
         nrm[0] = nx; nrm[1] = ny; nrm[2] = nz;
@@ -141,7 +141,7 @@ __device__ __forceinline__ bool band_pack_eval(const BandPack &k, const ExtractP
     const double gy = k.dy > 0 ? ((double)k.yp[j] - (double)k.ym[j]) / (double)k.dy : 0.0;
     const double gz = zh > zl ? ((double)tzh - (double)tzl) / (double)(zh - zl) : 0.0;
     const double n = sqrt((gx * gx + gy * gy) + gz * gz);
-    if (!(n > 1e-6)) return false;
+    if (!(n > 1e-6) || !isfinite(n)) return false;       // finite and > 1e-6: a NaN or infinite neighbour yields no sample
     if (pos) {
         const double nx = gx / n, ny = gy / n, nz = gz / n;
         nrm[0] = nx; nrm[1] = ny; nrm[2] = nz;

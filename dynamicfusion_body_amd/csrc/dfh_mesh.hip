@@ -645,7 +645,7 @@ __global__ __launch_bounds__(256) void mc_relabel_kernel(int *__restrict__ faces
     if (s < nslots) faces[s] = (int)newid[faces[s]];
 }
 
-static bool mc_params(const int res[3], int step, double level, McParams &p) {
+static void mc_params(const int res[3], int step, double level, McParams &p) {
     p.Y = res[1]; p.Z = res[2]; p.s = step; p.level = level;
     p.NX = (res[0] + step - 1) / step; p.NY = (res[1] + step - 1) / step; p.NZ = (res[2] + step - 1) / step;
     p.nseg = (p.NZ + kMcBlock - 1) / kMcBlock;
@@ -655,7 +655,6 @@ static bool mc_params(const int res[3], int step, double level, McParams &p) {
     if ((double)lo > level) lo = nextafterf(lo, -HUGE_VALF);
     p.lo_f = lo;
     p.eq_f = (double)(float)level == level ? (float)level : NAN;
-    return true;
 }
 
 struct McWorkspace {
@@ -702,7 +701,7 @@ int dfh_mc_count(const void *vol, int vol_dtype, const int res[3], int step, dou
     DFH_REQUIRE(level == level, "dfh_mc_count: level is NaN");
     DFH_REQUIRE(workspace_bytes >= dfh_mc_workspace_bytes(res, step), "dfh_mc_count: workspace too small");
     McParams p;
-    DFH_REQUIRE(mc_params(res, step, level, p), "dfh_mc_count: more than 65535 lattice planes");
+    mc_params(res, step, level, p);
     const McWorkspace w = mc_workspace(p, workspace);
     hipStream_t s = (hipStream_t)stream;
     const long ncount = (long)((p.nty + kMcBlock / 64 - 1) / (kMcBlock / 64)) * p.NX;
@@ -732,7 +731,7 @@ int dfh_mc_emit(const void *vol, int vol_dtype, const int res[3], int step, doub
     DFH_REQUIRE(cap_verts <= (long)kMcBaseMask, "dfh_mc_emit: more than 2^29-1 vertices");
     DFH_REQUIRE((cap_verts == 0 || (verts && normals)) && (cap_faces == 0 || faces), "dfh_mc_emit: null output");
     McParams p;
-    DFH_REQUIRE(mc_params(res, step, level, p), "dfh_mc_emit: more than 65535 lattice planes");
+    mc_params(res, step, level, p);
     DFH_REQUIRE(n_active_tiles <= p.ntiles, "dfh_mc_emit: n_active_tiles exceeds the tile count");
     const McWorkspace w = mc_workspace(p, workspace);
     const long nrows = n_active_tiles >= 0 ? n_active_tiles : p.ntiles;          // < 0: visit every row, no list

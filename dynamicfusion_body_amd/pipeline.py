@@ -62,7 +62,7 @@ def extract_surface_samples_torch(T, Wt, band, x0=0, max_samples=None):
     gz = diff(iz, Z, lambda a: Tf[ix, iy, a])
     g = torch.stack([gx, gy, gz], dim=1)
     nrm = g.norm(dim=1, keepdim=True)
-    ok = nrm[:, 0] > 1e-6
+    ok = (nrm[:, 0] > 1e-6) & torch.isfinite(nrm[:, 0])          # finite and > 1e-6: a NaN or infinite neighbour yields no sample
     idx, g, nrm = idx[ok], g[ok], nrm[ok]
     n = g / nrm
     pos = idx.to(torch.float64)

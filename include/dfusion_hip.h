@@ -689,10 +689,16 @@ int dfh_gn_global_step(const double *vals, int n_blocks, const double *rhs, int 
                        void *scratch, size_t scratch_bytes, void *stream);
 
 /* ---- surface samples for the solve (stand-in for marching cubes, core/fusion.py:554-568) -----------
- * Every band voxel (w > 0, |T| < band; T in voxel units as fuseDepths stores it) whose TSDF gradient
- * (central differences inside the slab, one-sided at its faces) is non-zero yields one sample: position
- * = voxel centre - T * gradient / (|gradient| * max(|gradient|, 1)) (one Newton step, never longer than |T|; global index space, plane 0 of the buffer is global plane x0), normal n =
- * gradient / |gradient|.  Samples come out in voxel order, deterministically.
+ * Every band voxel (w > 0, |T| < band, both comparisons strict and false for NaN; T in voxel units as fuseDepths stores it)
+ * whose TSDF gradient g has a length |g| that is finite and > 1e-6 yields one sample.  Everything in fp64, no fused
+ * multiply-add, operations in the order written (restated in numpy by tests/extract_np.py):
+ *  - g_a = (T[hi] - T[lo]) / (hi - lo) along each axis a, with lo = max(i - 1, 0) and hi = min(i + 1, n - 1) inside the slab
+ *    (central differences, one-sided at its faces), and g_a = 0 on an axis that is one voxel thick;
+ *  - |g| = sqrt((gx gx + gy gy) + gz gz).  A NaN or infinite neighbour makes |g| NaN or infinite: no sample, so no
+ *    non-finite number reaches the outputs (|T| < band keeps T itself finite);
+ *  - normal n = g / |g|; position = voxel centre - (T / max(|g|, 1)) n (one Newton step, never longer than |T|; global index
+ *    space: plane 0 of the buffer is global plane x0, which is added to the centre before the step is subtracted).
+ * Samples come out in voxel order, deterministically.
  *   dfh_surface_count : per-block counts + exclusive scan into `workspace`, *total_out (device) = count
  *   dfh_surface_emit  : writes min(total, capacity) samples (n x 3 fp64 each); uses the same workspace.  capacity < total:
  *                       an even subsample in voxel order (sample i is kept iff it is the first with slot floor(i * capacity /
