@@ -79,6 +79,11 @@ class Nodes(ctypes.Structure):
     _fields_ = [("pos", _vp), ("dq", _vp), ("w", _vp), ("n_nodes", _int), ("knn", _int)]
 
 
+class ColorVolume(ctypes.Structure):
+    """dfh_color_volume: the float32 (r, g, b, wc) packs of a slab."""
+    _fields_ = [("rgbw", _vp), ("slab", Slab)]
+
+
 class DepthPrepParams(ctypes.Structure):
     """dfh_depth_prep_params: the maps, camera, filter tables and thresholds of one dfh_depth_prep call (depth: a host array the
     caller keeps alive; spatial, range_lut: device float32)."""
@@ -110,7 +115,7 @@ _landmarks_p = ctypes.POINTER(Landmarks)
 STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams, "dfh_slab": Slab,
            "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes,
            "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams,
-           "dfh_gn_normal_gate": NormalGate, "dfh_gn_landmarks": Landmarks}
+           "dfh_gn_normal_gate": NormalGate, "dfh_gn_landmarks": Landmarks, "dfh_color_volume": ColorVolume}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -215,6 +220,9 @@ _SIGNATURES = {
     "dfh_pool_features_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long]),
     "dfh_pool_features": (_int, [_vp, _vp, ctypes.c_long, _int, ctypes.c_long, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dfh_pool_features_tile": (_int, [_c_int_p]),
+    "dfh_integrate_color": (_int, [ctypes.POINTER(ColorVolume), _volume_p, ctypes.POINTER(DepthViews), ctypes.POINTER(_vp),
+                                   ctypes.POINTER(Nodes), _c_double_p, _dbl, _dbl, _dbl, _dbl, _vp, ctypes.c_size_t, _int, _vp]),
+    "dfh_sample_colors": (_int, [ctypes.POINTER(ColorVolume), _vp, ctypes.c_long, _vp, _vp, _vp]),
 }
 
 _lib = None

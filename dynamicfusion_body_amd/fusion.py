@@ -63,6 +63,7 @@ class Fusion:
         self._tsdf_host = tsdf                   # uploaded on first use (ctor works without a GPU)
         self._workspace = None
         self._workspace_key = None
+        self._C = None                           # the colour volume (kernels.color_volume): set by the calls given colour images
 
     # ------------------------------------------------------------------ volumes
     def _ensure_volumes(self):
@@ -142,13 +143,17 @@ class Fusion:
                                 np.asarray(self._lw, dtype=np.float64), self._tdist, wmax,
                                 workspace=self._workspace, rebuild_candidates=rebuild)
 
-    def updateTSDF_depths(self, depths, lws, wmax=100.0, weight="node_distance", scale=1.0, center=np.zeros(3)):
+    def updateTSDF_depths(self, depths, lws, wmax=100.0, weight="node_distance", scale=1.0, center=np.zeros(3), colors=None,
+                          color_band=1.5):
         """The canonical update straight from the frame's depth maps (K1w, dfh_integrate_depth_dqb): every canonical voxel is
         warped through the DQB warp field and `_lw` as in updateTSDF, projected into each map as in fuseDepths, and the
         projective signed distance is averaged in -- DynamicFusion's surface fusion, without the live volume updateTSDF
         resamples.  Needs the intrinsics of InitializeCanonicalSpace(..., K=K); depth maps follow fuseDepths' dtype rule
         (float32 on the device unless a float64 map is not float32-exact: then every map travels as float64).
-        weight: "node_distance" = updateTSDF's running average (core/fusion.py:180-190), "unit" = fuseDepths'."""
+        weight: "node_distance" = updateTSDF's running average (core/fusion.py:180-190), "unit" = fuseDepths'.
+        colors: one uint8 (H, W, 3) / (H, W, 4) image per depth map; after the update they are averaged into the colour volume
+        `_C` (kernels.integrate_color: the same nodes, `_lw` and workspace) on the voxels within color_band voxels of the
+        canonical surface, and write_canonical_mesh writes vertex colours."""
         if getattr(self, '_K', None) is None:
             raise ValueError('updateTSDF_depths needs the intrinsics: call InitializeCanonicalSpace(..., K=K) first')
         depths, lws = list(depths), list(lws)
@@ -156,6 +161,8 @@ class Fusion:
             raise ValueError('length of camera matrix array must equal that of depth maps')
         if weight not in kernels.WARPED_WEIGHTS:
             raise ValueError("weight must be one of %s, not %r" % (sorted(kernels.WARPED_WEIGHTS), weight))
+        if colors is not None and len(colors) != len(depths):
+            raise ValueError('one colour image per depth map')
         lws = [np.asarray(m, dtype=np.float64) for m in lws]
         for m in lws:
             if m.shape != (3, 4):
@@ -183,6 +190,13 @@ class Fusion:
         kernels.integrate_depth_dqb(self._T, self._Wt, ds, self._K, self._Kinv, lws, scale, center, self._tdist, pos, dq, w,
                                     self._knn, np.asarray(self._lw, dtype=np.float64), wmax=wmax, weight=weight,
                                     tsdf_res=res[0], workspace=self._workspace, rebuild_candidates=rebuild)
+        if colors is not None:
+            if self._C is None:
+                self._C = kernels.color_volume(res)
+            kernels.integrate_color(self._C, self._T, self._Wt, ds, colors, self._K, self._Kinv, lws, scale, center, self._tdist,
+                                    color_band, pos, dq, w, self._knn, np.asarray(self._lw, dtype=np.float64), tsdf_res=res[0],
+                                    workspace=self._workspace,
+                                    stored_indices=kernels.dqb_has_indices(self._workspace, res, self._knn, len(pos)))
 
     # ------------------------------------------------------------------ A5 (single-point helpers)
     def _gather_nodes(self, locations, dqs):
@@ -535,6 +549,12 @@ class Fusion:
     def write_canonical_mesh(self, path, filename):
         """Reference core/fusion.py:577-587: index-space OBJ, `v` / `vn` / `f a b c` (1-based)."""
         self._ensure_volumes()
+        if self._C is not None:          # vertex colours (not in the reference): the colour volume sampled at the vertices
+            verts, faces, normals, values = _mesh.marching_cubes(self._T, None, 1)
+            rgb, valid = kernels.sample_colors(self._C, verts.double())
+            self._write_mesh_file(os.path.join(path, filename), verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(),
+                                  _mesh.obj_colors(rgb.cpu().numpy(), valid.cpu().numpy(), len(verts)))
+            return
         verts, faces, normals, values = _mesh.marching_cubes(self._T, None, 1, as_numpy=True)
         self._write_mesh_file(os.path.join(path, filename), verts, faces, normals)
 
@@ -544,9 +564,12 @@ class Fusion:
         return verts, faces, normals
 
     @staticmethod
-    def _write_mesh_file(fpath, verts, faces, normals):
+    def _write_mesh_file(fpath, verts, faces, normals, rgb=None):
         with open(fpath, 'w') as f:
-            f.write("".join('v %f %f %f\n' % (v[0], v[1], v[2]) for v in verts))
+            if rgb is None:
+                f.write("".join('v %f %f %f\n' % (v[0], v[1], v[2]) for v in verts))
+            else:
+                f.write("".join('v %f %f %f %f %f %f\n' % (v[0], v[1], v[2], c[0], c[1], c[2]) for v, c in zip(verts, rgb)))
             f.write("".join('vn %f %f %f\n' % (n[0], n[1], n[2]) for n in normals))
             f.write("".join('f %d %d %d\n' % (t[0] + 1, t[1] + 1, t[2] + 1) for t in faces))
 
@@ -585,13 +608,18 @@ class Fusion:
         tsdfw[...] = Wt.cpu().numpy()
         return (tsdf, tsdfw)
 
-    def InitializeCanonicalSpace(self, tsdf=None, depths=None, lws=None, K=None, tsdf_size=256, scale=1.0, center=np.zeros(3)):
+    def InitializeCanonicalSpace(self, tsdf=None, depths=None, lws=None, K=None, tsdf_size=256, scale=1.0, center=np.zeros(3),
+                                 colors=None, color_band=1.5):
         """The canonical volume from a given TSDF or from depth maps, then the initial mesh and deformation graph: what the
         reference's method of this name sets out to do (core/fusion.py:73-99; at HEAD it reads an undefined `tsdf.shape`, calls a
         free `fuseDepths` and iterates `len(depths)`).  From depth maps: the volume starts at +tdist with weight 0
         (core/fusion.py:80, core/fusion_dm.py:100-101) and the views are fused in order in ONE sweep of the volume
         (dfh_integrate_depth with all the views: the same bits as one fuseDepths call per view, FusionDM.compute_live_tsdf's loop,
-        core/fusion_dm.py:166-170).  scale / center: FusionDM.fuseDepths' voxel -> world map (defaults as there)."""
+        core/fusion_dm.py:166-170).  scale / center: FusionDM.fuseDepths' voxel -> world map (defaults as there).
+        colors (with depths): one uint8 image per depth map, averaged into a fresh colour volume `_C` with no warp on the voxels
+        within color_band voxels of the surface (kernels.integrate_color)."""
+        if colors is not None and (depths is None or len(colors) != len(depths)):
+            raise ValueError('colors needs depths, one colour image per depth map')
         if tsdf is not None:
             if not _is_tensor(tsdf) and (type(tsdf) is not np.ndarray or tsdf.ndim != 3):
                 raise ValueError('Only 3D numpy array is accepted as tsdf')
@@ -618,6 +646,11 @@ class Fusion:
             ds = [to_device(d if _is_tensor(d) else np.asarray(d), dtype=ddt) for d in depths]
             kernels.integrate_depth_views(self._T, self._Wt, ds, self._K, self._Kinv, [np.asarray(m, dtype=np.float64) for m in lws],
                                           scale, center, self._tdist, fresh=float(self._tdist))
+            self._C = None
+            if colors is not None and len(ds) > 0:
+                self._C = kernels.color_volume((R, R, R))
+                kernels.integrate_color(self._C, self._T, self._Wt, ds, colors, self._K, self._Kinv,
+                                        [np.asarray(m, dtype=np.float64) for m in lws], scale, center, self._tdist, color_band)
         else:
             raise ValueError('InitializeCanonicalSpace needs a tsdf, or depths, lws and K')
         if K is not None and getattr(self, '_K', None) is None:

@@ -44,6 +44,7 @@ class FusionDM:
         self._vol_dtype = torch_dtype(volume_dtype)
         self._T = None          # device volumes, allocated lazily (ctor must work without a GPU)
         self._Wt = None
+        self._C = None          # the colour volume (kernels.color_volume): set by the calls that are given colour images
         self._lw = np.array([1, 0, 0, 0, 0, 0, 0, 0], dtype=np.float32)
 
         K = np.asarray(K, dtype=np.float64)
@@ -266,6 +267,12 @@ class FusionDM:
         """OBJ file of the canonical surface in world coordinates; reference core/fusion_dm.py:339-354
         (level 0, step 1, degenerate faces dropped; `v` / `vn` / `f a//a b//b c//c`, 1-based)."""
         self._ensure_volumes()
+        if self._C is not None:          # vertex colours (not in the reference): the colour volume sampled at the vertices
+            verts, faces, normals, values = _mesh.marching_cubes(self._T, 0.0, 1)
+            rgb, valid = kernels.sample_colors(self._C, verts.double())
+            _mesh.write_obj(os.path.join(path, filename), verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), ind=self._IND,
+                            colors=rgb.cpu().numpy(), valid=valid.cpu().numpy())
+            return
         verts, faces, normals, values = _mesh.marching_cubes(self._T, 0.0, 1, as_numpy=True)
         _mesh.write_obj(os.path.join(path, filename), verts, faces, normals, ind=self._IND)
 
@@ -347,12 +354,20 @@ class FusionDM:
         return np.average(np.array(avgs), axis=0), float(np.average(np.array(stds)))
 
     def compute_live_tsdf(self, depths, lws, UseAutoAlignment=False, useICP=False, outputMesh=False,
-                          as_numpy=True, mesh_path='.'):
+                          as_numpy=True, mesh_path='.', colors=None, color_band=1.5):
         """Fuse a set of depth maps into a fresh volume; reference core/fusion_dm.py:95-178.
         The volume stays on the GPU across views; `as_numpy=False` returns the CUDA
-        tensors instead of downloading them."""
+        tensors instead of downloading them.
+        colors (not in the reference): one uint8 (H, W, 3) / (H, W, 4) image per depth map; after the sweep they are averaged
+        into a fresh colour volume `_C` (kernels.integrate_color, no warp) on the voxels within color_band voxels of the surface,
+        and write_canonical_mesh writes vertex colours.  Without colours `_C` is None."""
         if len(depths) != len(lws):
             raise ValueError('length of camera matrix array Ks must equal that of depth maps')   # :96-97
+        if colors is not None:
+            if useICP:
+                raise ValueError('colors cannot be fused with useICP=True: every view gets a rigid alignment of its own there')
+            if len(colors) != len(depths):
+                raise ValueError('one colour image per depth map')
         if self.depth_prep is not None and len(depths) > 0:          # (the single-map fuseDepths stays raw: the reference's meaning)
             depths = self.depth_prep(depths, self._Kinv, want_normals=False)[0]
         avg = np.array([-0.03, -0.43, -5.6], dtype='float32')       # :106-107
@@ -398,6 +413,13 @@ class FusionDM:
                     self._depthidx = idx
                     self.fuseDepths(dev[idx], lws[idx], T, Wt, scale=12 * std / res, center=avg)
             self._T, self._Wt = T, Wt
+        self._C = None
+        if colors is not None:
+            self._C = kernels.color_volume(tuple(self._T.shape))
+            for idx in range(len(dev)):                             # (one call per view: the maps may differ in shape or dtype)
+                kernels.integrate_color(self._C, self._T, self._Wt, [dev[idx]], [colors[idx]], self._K, self._Kinv,
+                                        [np.asarray(lws[idx], dtype=np.float64)], 12 * std / res, avg, self._tdist, color_band,
+                                        tsdf_res=self._tsdf_res)
         if outputMesh:                                              # :174-176
             np.save(os.path.join(mesh_path, 'tsdf_temp'), self._T.cpu().numpy())     # the reference's `np.save('tsdf_temp', self._tsdf)` (:175), in mesh_path
             self.write_canonical_mesh(mesh_path, 'test.obj')

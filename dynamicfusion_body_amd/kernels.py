@@ -347,6 +347,141 @@ def integrate_depth_dqb(T, Wt, depths, K, Kinv, lws, scale, center, tdist, node_
     return T, Wt
 
 
+def color_volume(res, x_range=None, device=None):
+    """K17: a zero-filled colour volume for planes `x_range` (default: all) of a `res` grid: float32 (x1-x0, Y, Z, 4), one
+    (r, g, b, wc) pack per voxel, r g b running means in [0, 255], wc = 0: never coloured.  Always float32."""
+    require_gpu()
+    x0, x1 = (0, res[0]) if x_range is None else x_range
+    return torch.zeros((int(x1) - int(x0), int(res[1]), int(res[2]), 4), dtype=torch.float32, device=device or "cuda")
+
+
+def dqb_has_indices(workspace, res, knn, n_nodes, x_range=None):
+    """True when `workspace` (a dqb_workspace) has the per-voxel node-index region that integrate_color(stored_indices=True)
+    reads: the rule of dfh_integrate_depth_dqb / dfh_integrate_color."""
+    lib = _lib.load()
+    sl = _lib.slab(res, x_range)
+    cached = lib.dfh_dqb_workspace_bytes_cached(sl, int(knn), int(n_nodes), 1)
+    return cached > lib.dfh_dqb_workspace_bytes(sl) and workspace.numel() * workspace.element_size() >= cached and \
+        not _lib.opt_on("k3_no_cache")
+
+
+def _color_volume(C, res, x_range):
+    x0, x1 = (0, res[0]) if x_range is None else x_range
+    want = (int(x1) - int(x0), int(res[1]), int(res[2]), 4)
+    if not (isinstance(C, torch.Tensor) and C.is_cuda and C.dtype == torch.float32 and C.is_contiguous()):
+        raise ValueError("the colour volume must be a contiguous float32 CUDA tensor")
+    if tuple(C.shape) != want:
+        raise ValueError("colour volume shape %s does not match slab %s of grid %s" % (tuple(C.shape), want, tuple(res)))
+    return _lib.ColorVolume(C.data_ptr(), _lib.slab(res, x_range))
+
+
+def color_images(colors, shape=None, device=None):
+    """(H, W, 3) or (H, W, 4) uint8 images (numpy or tensors) as contiguous (H, W, 4) RGBX CUDA tensors; the fourth byte is
+    padding (zero when added here, kept when given).  shape: the (H, W) every image must have."""
+    out = []
+    for c in colors:
+        t = c if isinstance(c, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(c))
+        if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] not in (3, 4):
+            raise ValueError("a colour image must be (H, W, 3) or (H, W, 4) uint8")
+        if shape is not None and tuple(t.shape[:2]) != tuple(shape):
+            raise ValueError("colour image of %s pixels for a depth map of %s" % (tuple(t.shape[:2]), tuple(shape)))
+        out.append(t)
+    require_gpu()
+    res = []
+    for t in out:
+        t = t.to(device=device or "cuda")
+        if t.shape[2] == 3:
+            t = torch.cat([t, torch.zeros_like(t[:, :, :1])], dim=2)
+        res.append(t.contiguous())
+    return res
+
+
+def integrate_color(C, T, Wt, depths, colors, K, Kinv, lws, scale, center, tdist, band, node_pos=None, node_dq=None, node_w=None,
+                    knn=None, lw_dq=None, wmax=100.0, band_sd=None, tsdf_res=None, res=None, x_range=None, workspace=None,
+                    stored_indices=False):
+    """K17 = colour images averaged into the colour volume C through the warp field (dfh_integrate_color).  Only voxels in the
+    canonical band (Wt > 0, |T| <= band, T's units) are touched; such a voxel is warped by integrate_depth_dqb's chain (no nodes:
+    it stays where it is), projected into each depth map, and where it lies within band_sd (depth units; default band * |scale|)
+    of the measured surface the pixel's colour enters the voxel's running mean.  T, Wt are read only.
+    colors: one (H, W, 3) / (H, W, 4) uint8 image per depth map.  More than 16 views are taken 16 at a time.  With nodes,
+    `workspace` is a dqb_workspace whose candidate lists are current (None: one is allocated and its lists built);
+    stored_indices=True reads the node indices a rebuilding fuse_volume_dqb / integrate_depth_dqb call stored in it."""
+    depths, lws, colors = list(depths), list(lws), list(colors)
+    if len(depths) != len(lws):
+        raise ValueError('length of camera matrix array must equal that of depth maps')
+    if len(colors) != len(depths):
+        raise ValueError("one colour image per depth map: %d images for %d maps" % (len(colors), len(depths)))
+    given = [a is not None for a in (node_pos, node_dq, node_w, knn, lw_dq)]
+    if any(given) and not all(given):
+        raise ValueError("node_pos, node_dq, node_w, knn and lw_dq go together")
+    for d in depths:
+        if not (isinstance(d, torch.Tensor) and d.dim() == 2):
+            raise ValueError("depth must be a contiguous 2-D CUDA tensor")
+        if d.shape != depths[0].shape or d.dtype != depths[0].dtype:
+            raise ValueError("all depth maps of one call must have the same shape and dtype")
+    if stored_indices and (not given[0] or workspace is None):
+        raise ValueError("stored_indices needs nodes and the workspace that holds the indices")
+    require_gpu()
+    lib = _lib.load()
+    vol, tsdf_res = _volume(T, Wt, res, x_range, tsdf_res)
+    cvol = _color_volume(C, vol.slab.res, (vol.slab.x0, vol.slab.x1))
+    for d in depths:
+        _check_depth(d)
+    if vol.slab.x1 == vol.slab.x0 or not depths:
+        return C
+    H, W = depths[0].shape
+    colors = color_images(colors, (H, W), T.device)
+    nodes, lw8, ws_ptr, ws_bytes = None, None, 0, 0
+    if given[0]:
+        P, Q, Wn = _node_tensors(node_pos, node_dq, node_w)
+        if workspace is None:
+            workspace = dqb_workspace(vol.slab.res, (vol.slab.x0, vol.slab.x1))
+            dqb_build_candidates(workspace, vol.slab.res, P, knn, (vol.slab.x0, vol.slab.x1))
+        nodes = _lib.Nodes(P.data_ptr(), Q.data_ptr(), Wn.data_ptr(), int(P.shape[0]), int(knn))
+        lw8 = _lib.darr(lw_dq, 8)
+        ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    if band_sd is None:
+        band_sd = float(band) * abs(float(scale))
+    for i in range(0, len(depths), 16):
+        dd, ll, cc = depths[i:i + 16], lws[i:i + 16], colors[i:i + 16]
+        n = len(dd)
+        ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dd])
+        cptrs = (ctypes.c_void_p * n)(*[c.data_ptr() for c in cc])
+        lw = _lib.darr(np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in ll]), 12 * n)
+        views = _lib.DepthViews(n, ptrs, dtype_code(dd[0]), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), lw, float(scale),
+                                _lib.darr(np.asarray(center, dtype=np.float64), 3), tsdf_res)
+        rc = lib.dfh_integrate_color(cvol, vol, views, cptrs, nodes, lw8, float(tdist), float(band), float(band_sd), float(wmax),
+                                     ws_ptr, ws_bytes, 1 if stored_indices else 0, current_stream_ptr())
+        _lib.check(rc, "dfh_integrate_color")
+    return C
+
+
+def sample_colors(C, points, x_range=None, res=None):
+    """K17: the colour volume sampled at `points` ((n, 3) fp64, global index space; numpy or CUDA), trilinear over the coloured
+    corners (dfh_sample_colors): (rgb float32 (n, 3), valid bool (n,)).  C holds planes `x_range` of a grid whose first extent is
+    res[0] (default: C is the whole grid)."""
+    require_gpu()
+    lib = _lib.load()
+    if not (isinstance(C, torch.Tensor) and C.dim() == 4):
+        raise ValueError("the colour volume must be a contiguous float32 CUDA tensor")
+    if res is None:
+        res = (C.shape[0] if x_range is None else None, C.shape[1], C.shape[2])
+        if res[0] is None:
+            raise ValueError("a slab's colour volume needs the grid's res")
+    cvol = _color_volume(C, res, x_range)
+    P = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(points, dtype=np.float64)))
+    P = P.to(device=C.device, dtype=torch.float64).contiguous()
+    if P.dim() != 2 or P.shape[1] != 3:
+        raise ValueError("points must be (n, 3)")
+    n = int(P.shape[0])
+    rgb = torch.empty((n, 3), dtype=torch.float32, device=C.device)
+    valid = torch.empty((n,), dtype=torch.uint8, device=C.device)
+    if n:
+        _lib.check(lib.dfh_sample_colors(cvol, P.data_ptr(), n, rgb.data_ptr(), valid.data_ptr(), current_stream_ptr()),
+                   "dfh_sample_colors")
+    return rgb, valid.bool()
+
+
 def depth_prep_tile():
     """(rows, columns) of the output tile a workgroup of the depth-preprocessing kernel owns (dfh_depth_prep_tile; no launch)."""
     hw = (ctypes.c_int * 2)()

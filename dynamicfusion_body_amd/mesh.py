@@ -92,10 +92,25 @@ class marching_cubes_begin:
         return verts, faces, normals, values
 
 
-def write_obj(fpath, verts, faces, normals, ind=None):
+def obj_colors(colors, valid, n_verts):
+    """The r g b columns of an OBJ file's coloured vertex rows: colors ((n, 3), values in [0, 255]) rounded (rint) and clamped to
+    a uint8, over 255; rows that are not `valid` ((n,) bool; None: all) or not finite are 0.5 grey."""
+    rgb = np.asarray(colors, dtype=np.float64).reshape(-1, 3)
+    if len(rgb) != n_verts:
+        raise ValueError("%d colours for %d vertices" % (len(rgb), n_verts))
+    ok = np.ones(len(rgb), dtype=bool) if valid is None else np.asarray(valid, dtype=bool).reshape(-1)
+    ok = ok & np.all(np.isfinite(rgb), axis=1)
+    rgb = np.clip(np.rint(np.where(ok[:, None], rgb, 0.0)), 0, 255).astype(np.uint8) / 255.0
+    return np.where(ok[:, None], rgb, 0.5)
+
+
+def write_obj(fpath, verts, faces, normals, ind=None, colors=None, valid=None):
     """The reference's OBJ layout (core/fusion_dm.py:339-354): `v x y z` rows, then `vn`, then
     `f a//a b//b c//c` with 1-based indices, `%f` formatting; `ind` (4x4) maps index space to world
-    (`self._IND`: rotation applied to normals, rotation + translation to vertices)."""
+    (`self._IND`: rotation applied to normals, rotation + translation to vertices).
+    colors ((n, 3), values in [0, 255]; not in the reference): the vertex rows become `v x y z r g b`, the widespread
+    vertex-colour extension, r g b = the value rounded (rint) and clamped to a uint8, over 255.  Vertices that are not `valid`
+    ((n,) bool; default: all) are written as 0.5 grey.  Without colours the file is what it always was."""
     verts = np.asarray(verts, dtype=np.float64)
     normals = np.asarray(normals, dtype=np.float64)
     faces = np.asarray(faces)
@@ -105,7 +120,11 @@ def write_obj(fpath, verts, faces, normals, ind=None):
         verts = verts @ rot.T + trans
         normals = normals @ rot.T
     with open(fpath, "w") as f:
-        f.write("".join("v %f %f %f\n" % (v[0], v[1], v[2]) for v in verts))
+        if colors is None:
+            f.write("".join("v %f %f %f\n" % (v[0], v[1], v[2]) for v in verts))
+        else:
+            rgb = obj_colors(colors, valid, len(verts))
+            f.write("".join("v %f %f %f %f %f %f\n" % (v[0], v[1], v[2], c[0], c[1], c[2]) for v, c in zip(verts, rgb)))
         f.write("".join("vn %f %f %f\n" % (n[0], n[1], n[2]) for n in normals))
         f.write("".join("f %d//%d %d//%d %d//%d\n" % (a + 1, a + 1, b + 1, b + 1, c + 1, c + 1) for a, b, c in faces))
 
@@ -126,6 +145,23 @@ def read_obj(fpath):
                 F.append([int(x.split("/")[0]) for x in t[1:4]])
     return (np.array(V, dtype=np.float64).reshape(-1, 3), np.array(F, dtype=np.int64).reshape(-1, 3),
             np.array(N, dtype=np.float64).reshape(-1, 3))
+
+
+def read_obj_colors(fpath):
+    """The r g b columns of an OBJ file's `v x y z r g b` rows: (n, 3) float64 in [0, 1], or None when the file's vertex rows
+    carry no colours; text parsing only."""
+    C, plain = [], 0
+    with open(fpath) as f:
+        for line in f:
+            t = line.split()
+            if t and t[0] == "v":
+                if len(t) >= 7:
+                    C.append([float(x) for x in t[4:7]])
+                else:
+                    plain += 1
+    if not C or plain:
+        return None
+    return np.array(C, dtype=np.float64).reshape(-1, 3)
 
 
 def _view_table(K, lws):

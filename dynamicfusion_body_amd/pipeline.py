@@ -181,8 +181,10 @@ class SlabFrame:
     sample_source = "band"   # set_sample_source(): where refresh_samples() takes the solve's samples from
 
     def __init__(self, K, scale, center, res, tdist_vox, node_pos, node_w, knn=4, pcg_iters=10, band=4.0, volume_dtype=torch.float32,
-                 distributed=True, solve_mode="auto", depth_prep=None, normal_gate=None):
-        """normal_gate: None, or the smallest cosine between a sample's warped normal and the live normal of the pixel it is matched
+                 distributed=True, solve_mode="auto", depth_prep=None, normal_gate=None, color_band=None):
+        """color_band: None, or the half-width in voxels of the canonical band that takes colour: a number allocates the colour
+        volume `self.C` of this rank's slab (kernels.color_volume) and step(colors=...) fuses each frame's colour images into it.
+        normal_gate: None, or the smallest cosine between a sample's warped normal and the live normal of the pixel it is matched
         to that still gives a correspondence (the normal gate of the depth data term, WarpSolver.associate_depth; 0.5 = 60 degrees):
         step() then passes this frame's live normal maps to the rigid-mode steps and the node iterations.  It needs depth_prep
         (where the normal maps come from) and data_term="depth"; step(normal_gate=...) overrides it per call.  The normal maps are a
@@ -216,6 +218,10 @@ class SlabFrame:
         self.live = torch.empty_like(self.T)
         self.live_w = torch.empty_like(self.T)
         self.band, self.knn = float(band), int(knn)
+        self.color_band = None if color_band is None else float(color_band)
+        if self.color_band is not None and not self.color_band > 0.0:
+            raise ValueError("color_band must be None or > 0, got %r" % (color_band,))
+        self.C = None if self.color_band is None else kernels.color_volume((R, R, R), (self.a, self.b))
         # (replicated / undecided: the solver itself runs no collective; a decision for "sharded" switches it on)
         self.fs = FrameSolver(K, scale, center, R / 2, knn=knn, pcg_iters=pcg_iters,
                               distributed=self.distributed and self.ws > 1 and solve_mode == "sharded")
@@ -450,6 +456,19 @@ class SlabFrame:
                                          node_w=sv.node_w)
         return _mesh.render(verts, faces, normals, self.K, lws, H, W, scale=self.scale, center=self.center, half=self.R / 2)
 
+    def colored_mesh(self):
+        """The canonical mesh with vertex colours: marching cubes of T at level 0 and the colour volume sampled at its vertices
+        (kernels.sample_colors) -> (verts, faces, normals, rgb (n, 3) float32 in [0, 255], valid (n,) bool).  Single rank only, as
+        render_live."""
+        if self.ws > 1:
+            raise ValueError("colored_mesh extracts one rank's whole grid; the %d-rank slab partition is not supported" % self.ws)
+        if self.C is None:
+            raise ValueError("no colour volume: construct the frame with color_band")
+        from . import mesh as _mesh
+        verts, faces, normals, _ = _mesh.marching_cubes(self.T, 0.0, 1)
+        rgb, valid = kernels.sample_colors(self.C, verts.double())
+        return verts, faces, normals, rgb, valid
+
     def visible_samples(self, lws, H, W, stride=1, max_samples=None):
         """The visible-surface samples of the loop's current live model in the views `lws`: render_live's mesh, warp and
         K / scale / center / half -- marching cubes of T at level 0, warped by the solver's node field, rasterised -- and, for every
@@ -499,8 +518,13 @@ class SlabFrame:
     def step(self, depth, lw_cam, gn_iters=10, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.5, stage_ms=None,
              update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None,
              data_term="depth", global_built=None, update="volume", update_weight="node_distance", graph_sampler="host",
-             normal_gate=_KEEP):
-        """normal_gate: this call's normal gate (a cosine, or None for none) instead of the constructor's; see there.
+             normal_gate=_KEEP, colors=None):
+        """colors: None, or one uint8 (H, W, 3) / (H, W, 4) image per depth map of this frame: right after the TSDF update of
+        either `update` route, and before the warp field decays, they are averaged into `self.C` through the field the update used
+        (kernels.integrate_color on this rank's slab, with the update's workspace and its stored node indices where the buffer
+        has them) -- colour and geometry see the same field.  Needs the constructor's color_band.  The call reads T, Wt, the maps
+        and the nodes and writes only `self.C`; without colours the frame issues the calls it always did.
+        normal_gate: this call's normal gate (a cosine, or None for none) instead of the constructor's; see there.
         update: how the canonical slab takes the frame in.  "volume" = the reference's two stages: the live volume fused from
         the depth maps (K1) is resampled through the warp field (K3, kernels.fuse_volume_dqb; the warp gathers across slab faces,
         so several ranks all-gather the live volume).  "depth" = DynamicFusion's surface fusion (K1w,
@@ -541,6 +565,8 @@ class SlabFrame:
         gate_cos = self.normal_gate if normal_gate is SlabFrame._KEEP else self._check_normal_gate(normal_gate, self.depth_prep)
         if gate_cos is not None and data_term != "depth":
             raise ValueError("normal_gate is the depth data term's: data_term must be 'depth'")
+        if colors is not None and self.color_band is None:
+            raise ValueError("step(colors=...) needs the constructor's color_band: there is no colour volume")
         if not self.has_graph:
             raise ValueError("no deformation graph yet: call construct_graph() first")
         need_live = update == "volume" or data_term == "volume"       # (update="depth" fuses the maps themselves)
@@ -562,6 +588,10 @@ class SlabFrame:
         lw_list = list(lw_cam) if isinstance(depth, (list, tuple)) else [lw_cam]
         if len(depth_list) != len(lw_list):
             raise ValueError('length of camera matrix array must equal that of depth maps')
+        if colors is not None:
+            colors = list(colors) if isinstance(colors, (list, tuple)) else [colors]
+            if len(colors) != len(depth_list):
+                raise ValueError('one colour image per depth map: %d images for %d maps' % (len(colors), len(depth_list)))
         if self.depth_prep is not None:
             shape = (len(depth_list),) + tuple(depth_list[0].shape)
             if self._prep_out is None or tuple(self._prep_out[0].shape) != shape or self._prep_out[0].device != depth_list[0].device:
@@ -645,6 +675,12 @@ class SlabFrame:
                                         weight=update_weight, tsdf_res=R, res=(R, R, R), x_range=(self.a, self.b),
                                         workspace=self.ws_dqb, rebuild_candidates=self._first)
         self._first = False
+        if colors is not None:                 # through the field the update used: before it decays
+            kernels.integrate_color(self.C, self.T, self.Wt, depth_list, colors, self.K, self.Kinv, lw_list, self.scale, self.center,
+                                    self.tdist_world, self.color_band, sv.node_pos, sv.node_dq, sv.node_w, self.knn, self.ident_lw,
+                                    tsdf_res=R, res=(R, R, R), x_range=(self.a, self.b), workspace=self.ws_dqb,
+                                    stored_indices=kernels.dqb_has_indices(self.ws_dqb, (R, R, R), self.knn, int(sv.node_pos.shape[0]),
+                                                                           (self.a, self.b)))
         # the warp field decays towards the identity once the TSDF update has used it (solve.relax_twists: every node's rotation
         # vector and translation scaled by `relax`).  Fusion.updateTSDF writes most of the motion into the canonical volume every
         # frame, and without a term that pulls a node back the field random-walks over hundreds of frames

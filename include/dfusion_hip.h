@@ -948,6 +948,58 @@ int dfh_pool_features(const int *vid, const float *feat, long n_pixels, int dim,
  * that walk; for tests that put sizes on those edges. */
 int dfh_pool_features_tile(int tile[4]);
 
+/* ---- K17  colour: a per-voxel colour volume fused through the warp field, colours sampled onto mesh vertices -----------------
+ * No reference counterpart (the reference reconstructs geometry only).  The colour volume C is float32 [x][y][z][4] over a slab's
+ * planes [x0, x1), z fastest, one aligned 16-byte pack (r, g, b, wc) per voxel: r, g, b running means in [0, 255], wc the colour
+ * weight (0 = never coloured).  It is float32 whatever the TSDF volume's dtype.  A colour image belongs to one depth map and has
+ * its H x W: uint8 [v][u][4], bytes R, G, B, X (X is ignored): a pixel is one dword.
+ *
+ * dfh_integrate_color.  cvol->slab must equal vol->slab; vol is only read.  Everything is fp64 without contraction.  For every
+ * voxel i = (x, y, z) of the slab:
+ *  1. canonical gate, before anything else: t = T[i], w = w[i], read in the volume's dtype and widened to double; the voxel is
+ *     live iff w > 0 and fabs(t) <= band_vox (a NaN fails).  A voxel that is not live is not warped, not projected, and its C is
+ *     neither read nor written.
+ *  2. position: nodes == NULL: q = i exactly.  Otherwise q is K1w's q (dfh_integrate_depth_dqb above), bit for bit: the knn nearest
+ *     nodes (searched in the brick's candidate list, or the stored indices, clamped to n_nodes - 1), the Gaussian weights, b^ and
+ *     q = dqb_warp(lw_dq, float32(dqb_warp(b^, i))).
+ *  3. for every view 0 .. n_views-1 in turn, K1w's chain:
+ *       pos  = scale*(q - tsdf_res/2) + center
+ *       lpos = lw*[pos,1];  (u,v) = (K*lpos)_{0,1}/(K*lpos)_2, skipped if (K*lpos)_2 == 0
+ *       visible iff 0<=u<W-1 and 0<=v<H-1;  (ui, vi) = (rint(u), rint(v)) (round-half-even)
+ *       z = -depth[vi][ui], valid iff z>0; a z*u or z*v that is not finite passes nothing
+ *       sd = (Kinv*(z*[u,v,1]))_2 - lpos_2;  passes iff sd > -tdist   (tdist in the depth maps' units)
+ *     then the view gate fabs(sd) <= band_sd (the occlusion and free-space test, in the depth maps' units).  A view that passes
+ *     reads pix = color[view][vi][ui] and updates
+ *       c_a <- (float)(((double)c_a * (double)wc + (double)pix_a) / ((double)wc + 1.0))   for a = r, g, b
+ *       wc  <- (float)min((double)wc + 1.0, wmax)
+ *     every stored component rounded to float32 after every view: n_views views in one call equal n_views one-view calls bit for bit.
+ *  4. C[i] is loaded once, when the first view passes, and stored once, only if a view passed.
+ * workspace (with nodes): the buffer of dfh_fuse_volume_dqb / dfh_integrate_depth_dqb.  This call never builds candidate lists and
+ * never stores indices: the lists must have been built for these node positions, this knn and this slab by
+ * dfh_dqb_build_candidates or by a rebuilding dfh_fuse_volume_dqb / dfh_integrate_depth_dqb call on the same buffer;
+ * use_stored_indices != 0 reads the index region those calls filled (the buffer must have one).  Nothing in the workspace is
+ * written: the weight region is not touched and the library's note of which dfh_fuse_volume_dqb path wrote it stays.
+ * DFH_E_BADARG before any HIP call for what dfh_integrate_depth_dqb refuses of its volume, views and (when given) nodes, and: a
+ * null cvol, rgbw, color or color[v]; cvol->slab != vol->slab; band_vox or band_sd not > 0 (NaN refused, +inf allowed); wmax < 1;
+ * nodes and lw_dq not both null or both non-null; with nodes a workspace smaller than dfh_dqb_workspace_bytes(); use_stored_indices
+ * without nodes or with a buffer that has no index region.  An empty slab or n_views == 0: DFH_OK, no launch.
+ *
+ * dfh_sample_colors: the colour of n points (device fp64 n x 3, GLOBAL index space), e.g. mesh vertices.  Per point p:
+ *  - invalid (rgb = 0, valid = 0) if a coordinate is not finite or lies outside [0, res_a - 1];
+ *  - i0_a = min((int)floor(p_a), res_a - 2), clamped at 0 for res_a == 1; f_a = p_a - i0_a;
+ *  - the eight corners in the order (dx, dy, dz) = 000, 001, 010, ..., 111; a corner's trilinear weight tw = (wx*wy)*wz, each
+ *    factor (1 - f_a) or f_a; a corner counts only if it lies in the grid, its plane in [x0, x1), and its wc > 0;
+ *  - S = sum tw, rgb_a = (float)((sum tw*c_a) / S), both sums fp64, sequential in corner order; S == 0: invalid.
+ * rgb_out: n x 3 float32; valid_out: n uint8.  DFH_E_BADARG before any HIP call: a null cvol, a bad slab, n < 0 or >= 2^31, with
+ * n > 0 a null points, rgb_out or valid_out, or a null rgbw with a non-empty slab.  n == 0: DFH_OK, no launch. */
+typedef struct dfh_color_volume { float *rgbw; dfh_slab slab; } dfh_color_volume;
+int dfh_integrate_color(const dfh_color_volume *cvol, const dfh_volume *vol, const dfh_depth_views *views,
+                        const void *const *color /* HOST array of n_views device pointers */, const dfh_nodes *nodes /* NULL: no warp */,
+                        const double lw_dq[8] /* NULL iff nodes == NULL */, double tdist, double band_vox, double band_sd, double wmax,
+                        void *workspace, size_t workspace_bytes, int use_stored_indices, void *stream);
+int dfh_sample_colors(const dfh_color_volume *cvol, const double *points, long n, float *rgb_out, unsigned char *valid_out,
+                      void *stream);
+
 #ifdef __cplusplus
 }
 #endif
