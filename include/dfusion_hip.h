@@ -766,7 +766,12 @@ int dfh_mc_reorder(const float *verts_in, const float *normals_in, const float *
  * dfh_render_raster clears the key buffer of `workspace` (dfh_render_workspace_bytes(n_views, H, W, n_faces) bytes: the keys
  * and the list of triangles whose box exceeds 64 pixels, which a second launch rasterises workgroup by workgroup) and fills it;
  * dfh_render_resolve reads it and writes the maps (same mesh, views and map as the raster call).  Both only enqueue on
- * `stream`; K / lw / center are host arrays read during the call. */
+ * `stream`; K / lw / center are host arrays read during the call.
+ * Workspace layout (each part starts 16-byte aligned): first the keys, n_views x H x W uint64, indexed [view][v][u]; then ONE
+ * uint32, the number of listed (triangle, view) pairs, i.e. those that draw and whose clamped box exceeds 64 pixels; then the
+ * list, up to n_views x n_faces uint32 entries view * n_faces + face in no particular order.  dfh_render_raster resets the
+ * count and the keys on every call, so a workspace may be reused as it is; after the call the count and the list can be read
+ * back (tests/test_gpu_raster_edges.py does, to see which path drew a triangle). */
 size_t dfh_render_workspace_bytes(int n_views, int H, int W, long n_faces);
 int dfh_render_raster(const double *verts, long n_verts, const int *faces, long n_faces, int n_views, const double *K, const double *lw,
                       int H, int W, double scale, const double center[3], double half, double znear, void *workspace,
