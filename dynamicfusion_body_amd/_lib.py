@@ -105,6 +105,15 @@ class Landmarks(ctypes.Structure):
                 ("node_ent", _vp), ("active_out", _vp)]
 
 
+class Photometric(ctypes.Structure):
+    """dfh_gn_photometric: the colour-consistency term -- samples sorted by node tuple with reference intensities, the views' colour
+    images (a host array of device pointers), their plan and the term's settings."""
+    _fields_ = [("pos", _vp), ("nbr", _vp), ("weights", _vp), ("ref", _vp), ("valid", _vp), ("conf", _vp), ("n", _int),
+                ("weight", _dbl), ("huber_delta", _dbl), ("max_diff", _dbl), ("band_sd", _dbl), ("color", _vp),
+                ("run_id", _vp), ("n_rows", _int), ("partial", _vp), ("blk_ptr", _vp), ("blk_ent", _vp), ("node_ptr", _vp),
+                ("node_ent", _vp), ("active_out", _vp), ("view_out", _vp), ("resid_out", _vp)]
+
+
 _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
@@ -112,10 +121,12 @@ _volume_p = ctypes.POINTER(Volume)
 _term_p = ctypes.POINTER(VolumeTerm)
 _gate_p = ctypes.POINTER(NormalGate)
 _landmarks_p = ctypes.POINTER(Landmarks)
+_photo_p = ctypes.POINTER(Photometric)
 STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_params": SolveParams, "dfh_slab": Slab,
            "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes,
            "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams,
-           "dfh_gn_normal_gate": NormalGate, "dfh_gn_landmarks": Landmarks, "dfh_color_volume": ColorVolume}
+           "dfh_gn_normal_gate": NormalGate, "dfh_gn_landmarks": Landmarks, "dfh_color_volume": ColorVolume,
+           "dfh_gn_photometric": Photometric}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -165,6 +176,8 @@ _SIGNATURES = {
     "dfh_gn_solve_gated": (_int, [_problem_p, _frame_p, _gate_p, ctypes.POINTER(SolveParams), _vp]),
     "dfh_gn_add_landmarks": (_int, [_problem_p, _landmarks_p, _vp]),
     "dfh_gn_solve_landmarks": (_int, [_problem_p, _frame_p, _landmarks_p, ctypes.POINTER(SolveParams), _vp]),
+    "dfh_gn_add_photometric": (_int, [_problem_p, _frame_p, _photo_p, _vp]),
+    "dfh_gn_solve_photometric": (_int, [_problem_p, _frame_p, _landmarks_p, _photo_p, ctypes.POINTER(SolveParams), _vp]),
     "dfh_gn_global_sampled_gated": (_int, [_problem_p, _frame_p, _gate_p, _int, _dbl, _int, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
     "dfh_gn_pack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),
     "dfh_gn_unpack_upper": (_int, [_vp, _vp, _vp, _vp, _int, _int, _int, _vp, _vp]),

@@ -407,6 +407,29 @@ int gn_gather_launch(int knn, const double *partial, const double *live, int n_r
 // The landmark term added to the problem's system (dfh_landmarks.hip); both structs are checked by the caller.
 int gn_add_landmarks_impl(const dfh_gn_problem &q, const dfh_gn_landmarks &l, void *stream);
 
+// ... and of a photometric term with its frame (dfh_gn_photometric; `fused`: the frame also feeds a fused build)
+inline int check_photometric(const char *what, const dfh_gn_photometric *t, const dfh_gn_frame *f, bool fused) {
+    DFH_REQUIRE(t, "%s: null photometric term", what);
+    const int rc = check_frame(what, f, fused);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(t->n >= 0, "%s: negative photo sample count", what);
+    DFH_REQUIRE(t->weight >= 0.0 && t->weight < __builtin_huge_val(), "%s: photometric weight negative or not finite", what);
+    DFH_REQUIRE(t->huber_delta >= 0.0, "%s: photometric huber_delta negative or NaN", what);
+    DFH_REQUIRE(t->max_diff == t->max_diff, "%s: photometric max_diff is NaN", what);
+    DFH_REQUIRE(t->band_sd > 0.0, "%s: photometric band_sd must be > 0", what);
+    DFH_REQUIRE(t->color, "%s: null colour image array", what);
+    for (int v = 0; v < f->n_views; ++v) DFH_REQUIRE(t->color[v], "%s: colour image %d is null", what, v);
+    if (t->n > 0) {
+        DFH_REQUIRE(t->pos && t->nbr && t->weights && t->ref, "%s: null photo sample pointer", what);
+        DFH_REQUIRE(t->n_rows >= 1 && t->run_id && t->partial && t->blk_ptr && t->blk_ent && t->node_ptr && t->node_ent,
+                    "%s: null photometric plan array", what);
+    }
+    return DFH_OK;
+}
+
+// The photometric term added to the problem's system (dfh_photometric.hip); the structs are checked by the caller.
+int gn_add_photometric_impl(const dfh_gn_problem &q, const dfh_gn_frame &f, const dfh_gn_photometric &t, void *stream);
+
 inline GatedAssocArgs gated_assoc_args(const dfh_gn_problem &p, const dfh_gn_frame &f, const dfh_gn_normal_gate &g, bool cull) {
     GatedAssocArgs ga;
     static_cast<AssocArgs &>(ga) = assoc_args(p, f, cull);

@@ -1286,8 +1286,9 @@ int dfh_debug_gather_trace(unsigned long long *out) {
 
 // The body of dfh_gn_solve / dfh_gn_solve_volume: the problem, its plan and the association's arguments are checked by the caller.
 // lm (optional): a checked landmark term, added to the system after every build (dfh_gn_solve_landmarks); NULL: none.
+// ph (optional): a checked photometric term with its frame pf, added after the landmark term (dfh_gn_solve_photometric); NULL: none.
 static int gn_solve_impl(const char *what, const dfh_gn_problem &q, const BuildAssoc &ba, const dfh_gn_solve_params *params, void *stream,
-                         const dfh_gn_landmarks *lm = nullptr) {
+                         const dfh_gn_landmarks *lm = nullptr, const dfh_gn_photometric *ph = nullptr, const dfh_gn_frame *pf = nullptr) {
     using namespace dfh;
     DFH_REQUIRE(params, "%s: null params", what);
     const dfh_gn_solve_params &sp = *params;
@@ -1300,6 +1301,7 @@ static int gn_solve_impl(const char *what, const dfh_gn_problem &q, const BuildA
     for (int g = 0; g < sp.n_global; ++g) {
         rc = gn_build_impl(q, ba, stream);
         if (rc == DFH_OK && lm) rc = gn_add_landmarks_impl(q, *lm, stream);
+        if (rc == DFH_OK && ph) rc = gn_add_photometric_impl(q, *pf, *ph, stream);
         if (rc != DFH_OK) return rc;
         rc = dfh_gn_global_step(q.vals, q.n_blocks, q.rhs, q.n_nodes, sp.global_lm, q.node_dq, sp.global_xi_out, sp.global_scratch,
                                 sp.global_scratch_bytes, stream);
@@ -1313,6 +1315,7 @@ static int gn_solve_impl(const char *what, const dfh_gn_problem &q, const BuildA
         bool zeroed = false;
         rc = gn_build_impl(q, ba, stream, on(opt().gn_iter_own_clear) ? nullptr : zbegin, zcount, &zeroed);
         if (rc == DFH_OK && lm) rc = gn_add_landmarks_impl(q, *lm, stream);
+        if (rc == DFH_OK && ph) rc = gn_add_photometric_impl(q, *pf, *ph, stream);
         if (rc != DFH_OK) return rc;
         rc = pcg_solve_impl(q.row_ptr, q.col, q.vals, q.rhs, q.n_nodes, sp.pcg_iters, sp.lm_abs, sp.lm_rel, sp.x_out, sp.pcg_workspace,
                             sp.pcg_workspace_bytes, q.node_dq, sp.step, stream, zeroed);
@@ -1343,6 +1346,20 @@ int dfh_gn_solve_landmarks(const dfh_gn_problem *problem, const dfh_gn_frame *fr
     if (!frame) return gn_solve_impl(what, *problem, BuildAssoc{nullptr, nullptr}, params, stream, landmarks);
     const AssocArgs aa = assoc_args(*problem, *frame, true);
     return gn_solve_impl(what, *problem, BuildAssoc{&aa, nullptr}, params, stream, landmarks);
+}
+
+int dfh_gn_solve_photometric(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_landmarks *landmarks,
+                             const dfh_gn_photometric *photo, const dfh_gn_solve_params *params, void *stream) {
+    using namespace dfh;
+    if (!photo) return landmarks ? dfh_gn_solve_landmarks(problem, frame, landmarks, params, stream) : dfh_gn_solve(problem, frame, params, stream);
+    const char *what = "dfh_gn_solve_photometric";
+    int rc = check_problem(what, problem, true);
+    if (rc == DFH_OK) rc = check_photometric(what, photo, frame, true);
+    if (rc == DFH_OK && landmarks) rc = check_landmarks(what, landmarks);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(problem->blk_ptr, "dfh_gn_solve_photometric: null blk_ptr (the solve needs a plan)");
+    const AssocArgs aa = assoc_args(*problem, *frame, true);
+    return gn_solve_impl(what, *problem, BuildAssoc{&aa, nullptr}, params, stream, landmarks, photo, frame);
 }
 
 int dfh_gn_solve_gated(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_normal_gate *gate,

@@ -102,6 +102,23 @@ class FrameSolver:
         sv = self.solver
         return sv._lm is not None and sv._lm["L"] > 0 and float(sv.landmark_weight) != 0.0
 
+    def set_photometric(self, ref, valid=None, conf=None, weight=1e-3, huber=0.0, max_diff=0.0, band_sd=float("inf"), presorted=False):
+        """The photometric term of the solve (WarpSolver.set_photometric): a reference intensity `ref` (0..255) per sample, compared
+        with the colour images a gn_iteration / global_iteration is given (colors=) as one row per sample of weight `weight`
+        (x conf), with the Huber delta `huber` and the gate `max_diff` on |I - ref| (intensity units) and the depth gate `band_sd` on
+        |sd| (the depth maps' units).  Until clear_photometric(), new samples or a new graph."""
+        sv = self.solver
+        sv.photo_weight, sv.photo_huber, sv.photo_max_diff, sv.photo_band_sd = float(weight), float(huber), float(max_diff), float(band_sd)
+        sv.set_photometric(ref, valid=valid, conf=conf, presorted=presorted)
+
+    def clear_photometric(self):
+        self.solver.clear_photometric()
+
+    def photometric_active(self):
+        """True while the builds that are given colour images add a photometric term."""
+        sv = self.solver
+        return sv._ph is not None and sv.S > 0 and float(sv.photo_weight) != 0.0
+
     def set_canonical(self, T, Wt, band=1.0, x0=0, max_samples=None, knn_bricks=None):
         """knn_bricks: see solve.sample_knn (candidate lists of the K3 workspace: the samples' node search skips its
         per-workgroup bounding-box pass)."""
@@ -110,29 +127,34 @@ class FrameSolver:
         return pos.shape[0]
 
     def gn_iteration(self, depth, lw_cam, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.0, n_iters=1, n_global=0, global_lm=0.1,
-                     normals=None, normal_cos=0.5):
+                     normals=None, normal_cos=0.5, colors=None):
         """associate -> build (+ all-reduce) -> PCG -> twist update, n_iters times; asynchronous.  depth / lw_cam may be lists
         (several live views: every sample associates with the view in which it lies closest to the observed surface).
         n_global: that many rigid-mode steps first (global_iteration), in the same library call on one GPU.
-        normals / normal_cos: the normal gate of WarpSolver.associate_depth ((V, H, W, 3) float32 live normal maps; None: none)."""
+        normals / normal_cos: the normal gate of WarpSolver.associate_depth ((V, H, W, 3) float32 live normal maps; None: none).
+        colors: one colour image per depth map: every build adds the photometric term (set_photometric)."""
+        kw = {} if colors is None else {"colors": colors}
         self.solver.iterate_associated(depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.half, self.lw, rw, max_dist, huber,
                                        lm_abs, lm_rel, n_iters=n_iters, n_global=n_global, global_lm=global_lm, normals=normals,
-                                       normal_cos=normal_cos)
+                                       normal_cos=normal_cos, **kw)
 
     def global_iteration(self, depth, lw_cam, rw=5.0, max_dist=2.0, huber=0.0, lm_rel=0.1, n_iters=1, built=False, stride=1,
-                         normals=None, normal_cos=0.5):
+                         normals=None, normal_cos=0.5, colors=None):
         """The rigid mode alone -- one twist shared by all nodes -- n_iters times; asynchronous.  Worth several node iterations where
         the live frame has moved as a whole: ten truncated PCG iterations hardly touch that mode.  Default: straight from the
         samples (WarpSolver.global_sampled: data rows only, two short launches a step); built=True: from the built normal
         equations, regulariser included (associate -> build (+ all-reduce) -> WarpSolver.global_step).
-        normals / normal_cos: the normal gate of WarpSolver.associate_depth, on either route."""
+        normals / normal_cos: the normal gate of WarpSolver.associate_depth, on either route.
+        colors: built=True only: the builds add the photometric term (the sampled steps read data rows only and refuse them)."""
+        if not built and colors is not None:
+            raise ValueError("colors= needs built=True: the sampled rigid-mode steps read the data rows only")
         if not built:
             self.solver.global_sampled(depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.half, self.lw, max_dist, huber, lm_rel,
                                        n_steps=n_iters, stride=stride, normals=normals, normal_cos=normal_cos)
             return
         for _ in range(int(n_iters)):
             self.solver.build_associated(depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.half, self.lw, rw, max_dist, huber,
-                                         normals, normal_cos)
+                                         normals, normal_cos, **({} if colors is None else {"colors": colors}))
             self.solver.global_step(lm_rel)
 
     def gn_iteration_volume(self, live, band, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.0, n_iters=1, min_grad=0.5,
@@ -181,8 +203,16 @@ class SlabFrame:
     sample_source = "band"   # set_sample_source(): where refresh_samples() takes the solve's samples from
 
     def __init__(self, K, scale, center, res, tdist_vox, node_pos, node_w, knn=4, pcg_iters=10, band=4.0, volume_dtype=torch.float32,
-                 distributed=True, solve_mode="auto", depth_prep=None, normal_gate=None, color_band=None):
-        """color_band: None, or the half-width in voxels of the canonical band that takes colour: a number allocates the colour
+                 distributed=True, solve_mode="auto", depth_prep=None, normal_gate=None, color_band=None, photo_weight=0.0,
+                 photo_huber=0.0, photo_max_diff=0.0, photo_band_sd=None):
+        """photo_weight: > 0 switches the photometric term of the solve on (FrameSolver.set_photometric); it needs color_band.  After
+        every sample refresh the samples' reference intensities are the luma of the colour volume at their canonical positions
+        (kernels.sample_colors; samples the volume has no colour for get no row), and the next step(colors=...) compares them with
+        that frame's colour images in every build of its solve (the depth data term) -- before the images are fused, which is
+        step()'s order anyway.  While it is on, the rigid-mode steps come from the built system, as with landmarks.  photo_huber /
+        photo_max_diff: the Huber delta and the gate on |I - ref| in intensity units (0: none); photo_band_sd: the depth gate on |sd|
+        in the depth maps' units (default color_band * |scale|, the colour fusion's).  Single rank only.
+        color_band: None, or the half-width in voxels of the canonical band that takes colour: a number allocates the colour
         volume `self.C` of this rank's slab (kernels.color_volume) and step(colors=...) fuses each frame's colour images into it.
         normal_gate: None, or the smallest cosine between a sample's warped normal and the live normal of the pixel it is matched
         to that still gives a correspondence (the normal gate of the depth data term, WarpSolver.associate_depth; 0.5 = 60 degrees):
@@ -222,6 +252,16 @@ class SlabFrame:
         if self.color_band is not None and not self.color_band > 0.0:
             raise ValueError("color_band must be None or > 0, got %r" % (color_band,))
         self.C = None if self.color_band is None else kernels.color_volume((R, R, R), (self.a, self.b))
+        self.photo_weight, self.photo_huber, self.photo_max_diff = float(photo_weight), float(photo_huber), float(photo_max_diff)
+        if not self.photo_weight >= 0.0:
+            raise ValueError("photo_weight must be >= 0, got %r" % (photo_weight,))
+        if self.photo_weight > 0.0 and self.ws > 1:
+            raise ValueError("the photometric term (photo_weight > 0) is single-rank only: %d ranks" % self.ws)
+        if self.photo_weight > 0.0 and self.color_band is None:
+            raise ValueError("photo_weight > 0 needs color_band: the reference intensities come from the colour volume")
+        self.photo_band_sd = None if photo_band_sd is None else float(photo_band_sd)
+        self.photo_active = None                 # after a step() whose solve had colour rows: uint8 per sample of that solve (the
+                                                 # solver's order then), 1 = the row was active in its last build
         # (replicated / undecided: the solver itself runs no collective; a decision for "sharded" switches it on)
         self.fs = FrameSolver(K, scale, center, R / 2, knn=knn, pcg_iters=pcg_iters,
                               distributed=self.distributed and self.ws > 1 and solve_mode == "sharded")
@@ -354,6 +394,28 @@ class SlabFrame:
         return N
 
     def refresh_samples(self):
+        """_refresh_samples, then (photo_weight > 0) the new samples' reference intensities from the colour volume."""
+        n = self._refresh_samples()
+        self._refresh_photo()
+        return n
+
+    def _refresh_photo(self):
+        """The photometric term's reference intensities for the solver's current samples: the luma of the colour volume at their
+        canonical positions, valid where the volume has colour.  Nothing while photo_weight is 0."""
+        if not self.photo_weight > 0.0:
+            return
+        sv = self.fs.solver
+        if sv.S == 0:
+            sv.clear_photometric()
+            return
+        rgb, valid = kernels.sample_colors(self.C, sv.spos)
+        rgb = rgb.double()
+        ref = (77.0 * rgb[:, 0] + 150.0 * rgb[:, 1] + 29.0 * rgb[:, 2]) / 256.0
+        band_sd = self.color_band * abs(self.scale) if self.photo_band_sd is None else self.photo_band_sd
+        self.fs.set_photometric(ref, valid=valid, weight=self.photo_weight, huber=self.photo_huber, max_diff=self.photo_max_diff,
+                                band_sd=band_sd, presorted=True)
+
+    def _refresh_samples(self):
         """Samples of this slab.  Normals are central differences of T, also across the slab faces: the
         neighbours' face planes come as a halo whose weight is 0 (they feed gradients, never samples), so the
         union over ranks is exactly the whole-grid sample set."""
@@ -634,6 +696,10 @@ class SlabFrame:
         # then the node iterations (one host call: nothing between their launches depends on the host)
         ng = self.GLOBAL_ITERS if global_iters is None else int(global_iters)
         lm_on = self.fs.landmarks_active()     # (landmarks: the rigid-mode steps from the built system, which holds their rows)
+        photo_kw = {}
+        if colors is not None and self.photo_weight > 0.0 and data_term == "depth" and self.fs.photometric_active():
+            photo_kw = {"colors": colors[:nd]}   # (the colour rows likewise: they are compared with the views the solve reads)
+            lm_on = True
         live_full = None
         if data_term == "volume":
             # the solve reads the live volume: the side stream (which has overlapped the plan's launches) joins here, and the
@@ -658,7 +724,7 @@ class SlabFrame:
                                      stride=self.GLOBAL_STRIDE if global_stride is None else int(global_stride), **gate_kw)
         if data_term == "depth":
             self.fs.gn_iteration(solve_depth, solve_lw, rw=rw, lm_abs=lm_abs, lm_rel=lm_rel, max_dist=max_dist, huber=huber, n_iters=gn_iters,
-                                 n_global=ng if lm_on else 0, global_lm=global_lm, **gate_kw)
+                                 n_global=ng if lm_on else 0, global_lm=global_lm, **gate_kw, **photo_kw)
         mark("solve")
         if not joined:
             torch.cuda.current_stream().wait_stream(self._side)
@@ -696,11 +762,13 @@ class SlabFrame:
         mark("tsdf_update")
         if self.sample_source == "visible":              # this frame's cameras and map size: the prediction for the next frame
             self._src_lws, self._src_size = lw_list, (int(depth.shape[0]), int(depth.shape[1]))
+        self.photo_active = sv._ph["active"] if photo_kw and sv._ph is not None else None      # (the refresh replaces the term's arrays)
         n = self.refresh_samples()
         mark("samples")
         self.fs.solver.check_status(completed_only=True)   # the sample count's read-back has synchronised: a timed-out PCG raises here
         if update_graph:
             if self.update_graph(sampler=graph_sampler):
                 n = self.fs.solver.S
+                self._refresh_photo()              # (a new graph dropped the term with its plan)
             mark("graph")
         return n

@@ -302,6 +302,8 @@ class WarpSolver:
                   depth maps, or association against a live TSDF volume
     set_landmarks()  optional point-to-point rows (canonical points with live 3-D targets: feature matches), added to every
                   build while landmark_weight != 0
+    set_photometric()  optional colour-consistency rows of the samples themselves (a reference intensity per sample against the
+                  frame's colour images), added to every build that is given colors= while photo_weight != 0
     step()        one iteration: build -> PCG -> twist update (asynchronous)
     """
 
@@ -325,6 +327,15 @@ class WarpSolver:
         self.landmark_weight = 0.0
         self.landmark_huber = 0.0
         self.landmark_max_dist = 0.0
+        # the photometric term (set_photometric; off while photo_weight is 0 and in every call without colors=): weight of a
+        # sample's colour row, the delta of the Huber loss on |I - ref| and the gate on it (intensity units, 0..255; 0: none), and
+        # the depth gate |sd| <= photo_band_sd that decides whether a view sees the sample (the depth maps' units)
+        self._ph_s = _lib.Photometric()
+        self._ph = None
+        self.photo_weight = 0.0
+        self.photo_huber = 0.0
+        self.photo_max_diff = 0.0
+        self.photo_band_sd = float("inf")
         if _dist.ranks_share_a_gpu():                 # (whether or not THIS solver runs collectives: ADVICE round 2)
             # several processes time-share this GPU (a rehearsal of the multi-GPU job on one card): co-residency of the
             # persistent PCG's workgroups is not guaranteed across processes -> two launches per iteration, no grid barrier
@@ -357,6 +368,114 @@ class WarpSolver:
         self._pattern = None
         self._pattern_keys = None
         self._lm = None                               # (landmarks hold node tuples of the old graph)
+        self._ph = None                               # (and the photometric term's samples are planned against it)
+
+    # -- the photometric term ----------------------------------------------------------------
+    def set_photometric(self, ref, valid=None, conf=None, presorted=False):
+        """The photometric term's reference intensities (dfh_gn_photometric): ref (S,) in 0..255, one per sample in the order the
+        samples were handed to set_samples (it follows their permutation); valid (S,): 0 drops a sample's row; conf (S,): per-sample
+        confidence multiplying photo_weight.  The photo samples ARE the solver's samples: their nbr, weights and data plan are
+        used, no second sort and no second plan; only the scratch rows are the term's own.  The term is added by every build that
+        is given colour images (colors=) while photo_weight != 0; set_samples and set_graph clear it.  presorted: the arrays are
+        already in the solver's own order (that of spos), e.g. computed from it."""
+        def take(a, conv, what):
+            if a is None:
+                return None
+            t = conv(a)
+            if t.shape[0] != self.S:
+                raise ValueError("photometric %s disagree with the samples in length" % what)
+            return (t[self._order_index()] if self.order is not None and not presorted else t.clone()).contiguous()
+
+        def u8(a):
+            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+            return (t != 0).to(device="cuda", dtype=torch.uint8).reshape(-1)
+
+        if ref is None:
+            raise ValueError("reference intensities are required")
+        S = self.S
+        self._ph = {"ref": take(ref, lambda a: _f64(a, ()), "reference intensities"), "valid": take(valid, u8, "validity flags"),
+                    "conf": take(conf, lambda a: _f64(a, ()), "confidences"), "partial": None,
+                    "active": torch.zeros(S, dtype=torch.uint8, device="cuda"),
+                    "view": torch.full((S,), -1, dtype=torch.int32, device="cuda"),
+                    "resid": torch.zeros(S, dtype=torch.float64, device="cuda")}
+
+    def clear_photometric(self):
+        self._ph = None
+
+    def _photo_out(self, name):
+        ph = self._ph
+        if ph is None:
+            raise ValueError("set_photometric first")
+        if self.order is None:
+            return ph[name].clone()
+        out = torch.empty_like(ph[name])
+        out[self._order_index()] = ph[name]
+        return out
+
+    def photometric_active(self):
+        """uint8 (S,), the order of set_samples' arguments: 1 where the sample's colour row was active in the last build that added
+        the term."""
+        return self._photo_out("active")
+
+    def photometric_residuals(self):
+        """float64 (S,), the order of set_samples' arguments: the unscaled I - ref of the last build that added the term, 0 where
+        the row was inactive."""
+        return self._photo_out("resid")
+
+    def photometric_views(self):
+        """int32 (S,), the order of set_samples' arguments: the view each active row read its intensity from, -1 where inactive."""
+        return self._photo_out("view")
+
+    def _photo_term(self, colors, frame):
+        """The photometric term as a dfh_gn_photometric for the frame `frame` (a filled dfh_gn_frame) and its colour images, or None
+        while there is none to add (no set_photometric, no samples, photo_weight 0, no colours)."""
+        ph = self._ph
+        if ph is None or colors is None or self.S == 0 or float(self.photo_weight) == 0.0:
+            return None
+        if self.distributed and _dist.world()[1] > 1:
+            raise ValueError("the photometric term is single-rank only: the samples' colour rows are not sharded")
+        from . import kernels
+        colors = list(colors) if isinstance(colors, (list, tuple)) else [colors]
+        if len(colors) != frame.n_views:
+            raise ValueError("one colour image per depth map: %d images for %d maps" % (len(colors), frame.n_views))
+        imgs = kernels.color_images(colors, shape=(frame.H, frame.W))
+        if self._pattern is None:
+            self._build_pattern()
+        if getattr(self, "partial", None) is None or getattr(self, "blk_ptr", None) is None:
+            raise ValueError("the photometric term needs the planned build (the samples' data plan)")
+        if ph["partial"] is None or ph["partial"].numel() != self.partial.numel():
+            ph["partial"] = torch.empty_like(self.partial)        # the term's own scratch rows | {cost, 0} per tile | live flags
+        ph["images"] = imgs
+        ph["cptrs"] = (ctypes.c_void_p * len(imgs))(*[int(t.data_ptr()) for t in imgs])
+        t = self._ph_s
+        t.pos, t.nbr, t.weights, t.ref = self.spos.data_ptr(), self.snbr.data_ptr(), self.swts.data_ptr(), ph["ref"].data_ptr()
+        t.valid = 0 if ph["valid"] is None else ph["valid"].data_ptr()
+        t.conf = 0 if ph["conf"] is None else ph["conf"].data_ptr()
+        t.n, t.weight, t.huber_delta = self.S, float(self.photo_weight), float(self.photo_huber)
+        t.max_diff, t.band_sd = float(self.photo_max_diff), float(self.photo_band_sd)
+        t.color = ctypes.cast(ph["cptrs"], ctypes.c_void_p)
+        t.run_id, t.n_rows, t.partial = self.run_id.data_ptr(), self.n_rows, ph["partial"].data_ptr()
+        t.blk_ptr, t.blk_ent = self.blk_ptr.data_ptr(), self.blk_ent.data_ptr()
+        t.node_ptr, t.node_ent = self.node_ptr.data_ptr(), self.node_ent.data_ptr()
+        t.active_out, t.view_out, t.resid_out = ph["active"].data_ptr(), ph["view"].data_ptr(), ph["resid"].data_ptr()
+        return t
+
+    def _photo_frame(self, frame):
+        """build() / build_volume() have no frame of their own: frame = build_associated's leading arguments (depth, K, Kinv, lw_cam,
+        scale, center, half)."""
+        if frame is None:
+            raise ValueError("colors= needs frame=(depth, K, Kinv, lw_cam, scale, center, half): the views the images belong to")
+        depth, K, Kinv, lw_cam, scale, center, half = frame
+        return self._frame(depth, lw_cam, K, Kinv, scale, center, half, 0.0)
+
+    def _add_photometric(self, lw_dq, frame, colors, upper=True):
+        """The photometric term added to the system of the build that has just been queued (dfh_gn_add_photometric)."""
+        if colors is None or self._ph is None:
+            return
+        t = self._photo_term(colors, frame)
+        if t is not None:
+            _lib.check(self.lib.dfh_gn_add_photometric(self._problem(lw_dq, upper=upper), frame, t, current_stream_ptr()),
+                       "dfh_gn_add_photometric")
 
     # -- landmarks ---------------------------------------------------------------------------
     def set_landmarks(self, pos, target, conf=None, valid=None, nbr=None, weights=None):
@@ -553,6 +672,7 @@ class WarpSolver:
         self.corr = torch.empty((self.S, 3), dtype=torch.float64, device="cuda")
         self.valid = torch.zeros(self.S, dtype=torch.uint8, device="cuda")
         self._pattern = None
+        self._ph = None                               # (reference intensities belong to the samples they were set for)
 
     def _sort_samples_device(self, pos, nrm, nbr, weights):
         """dfh_gn_sort_samples: the samples in the (stable) order of their node tuples; sets order and _tuple_key."""
@@ -948,20 +1068,22 @@ class WarpSolver:
         t = self._volume_term(live, band, max_dist, min_grad, value_to_vox)
         _lib.check(self.lib.dfh_gn_associate_volume(self._problem(lw_dq), t, current_stream_ptr()), "dfh_gn_associate_volume")
 
-    def build_volume(self, live, lw_dq, rw, band, max_dist=0.0, huber=0.0, min_grad=0.5, value_to_vox=1.0):
+    def build_volume(self, live, lw_dq, rw, band, max_dist=0.0, huber=0.0, min_grad=0.5, value_to_vox=1.0, colors=None, frame=None):
         """associate_volume + build in one launch sequence (dfh_gn_build_volume): same corr / valid, same system, bit for bit;
-        float32 live volumes and the planned build only (otherwise the two calls are made)."""
+        float32 live volumes and the planned build only (otherwise the two calls are made).  colors / frame: see build()."""
         _check_live(live)
         if self._pattern is None:
             self._build_pattern()
         if (live.dtype != torch.float32 or self.S == 0 or _lib.opt_on("py_gn_atomic") or _lib.opt_on("py_gn_no_fused_assoc")):
             self.associate_volume(live, lw_dq, band, max_dist, min_grad, value_to_vox)
-            return self.build(lw_dq, rw, huber)
+            return self.build(lw_dq, rw, huber, colors=colors, frame=frame)
         reg_here = (not self.distributed) or _dist.world()[0] == 0
         t = self._volume_term(live, band, max_dist, min_grad, value_to_vox)
         _lib.check(self.lib.dfh_gn_build_volume(self._problem(lw_dq, rw, huber, reg=reg_here), t, current_stream_ptr()), "dfh_gn_build_volume")
         if reg_here:
             self._add_landmarks(lw_dq)
+        if colors is not None and self._ph is not None:
+            self._add_photometric(lw_dq, self._photo_frame(frame), colors)
         self._allreduce_system()
 
     def iterate_volume(self, live, lw_dq, rw, band, max_dist=0.0, huber=0.0, lm_abs=0.0, lm_rel=0.0, n_iters=1, n_global=0,
@@ -996,8 +1118,10 @@ class WarpSolver:
             _lib.check(self.lib.dfh_gn_solve_volume(prob, t, sp, current_stream_ptr()), "dfh_gn_solve_volume")
 
     # -- iteration ---------------------------------------------------------------------------
-    def build(self, lw_dq, rw, huber=0.0):
-        """J^T J (block-sparse), J^T r and the cost 0.5*|computef|^2 at the current node DQs."""
+    def build(self, lw_dq, rw, huber=0.0, colors=None, frame=None):
+        """J^T J (block-sparse), J^T r and the cost 0.5*|computef|^2 at the current node DQs.  colors: the colour images of a live
+        frame, one per view: adds the photometric term (set_photometric) after the landmark term; this build has no frame of its
+        own, so frame = (depth, K, Kinv, lw_cam, scale, center, half), build_associated's leading arguments."""
         if self._pattern is None:
             self._build_pattern()
         # data rows are sharded with the samples; the regularisation rows (one per node pair) are
@@ -1010,20 +1134,23 @@ class WarpSolver:
                                          current_stream_ptr()), "dfh_gn_build")
         if reg_here:                              # (the landmarks are not sharded either: the regulariser's rank adds them)
             self._add_landmarks(lw_dq, upper=False)
+        if colors is not None and self._ph is not None:
+            self._add_photometric(lw_dq, self._photo_frame(frame), colors, upper=False)
         self._allreduce_system()                  # no-op on one GPU; samples are sharded by slab
 
     def build_associated(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist=0.0, huber=0.0, normals=None,
-                         normal_cos=0.5):
+                         normal_cos=0.5, colors=None):
         """associate_depth + build in one launch sequence (dfh_gn_build with a frame): same corr / valid, same system, bit
         for bit; float32 depth maps and the planned build only (otherwise the two calls are made).  normals / normal_cos: the
-        normal gate of associate_depth (dfh_gn_build_gated)."""
+        normal gate of associate_depth (dfh_gn_build_gated).  colors: one colour image per depth map: adds the photometric term
+        (set_photometric) after the landmark term."""
         if self._pattern is None:
             self._build_pattern()
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
         gate = self._gate(normals, normal_cos, frame)
         if (frame.depth_dtype != _lib.F32 or self.S == 0 or _lib.opt_on("py_gn_atomic") or _lib.opt_on("py_gn_no_fused_assoc")):
             self.associate_depth(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, max_dist, normals, normal_cos)
-            return self.build(lw_dq, rw, huber)
+            return self.build(lw_dq, rw, huber, colors=colors, frame=(depth, K, Kinv, lw_cam, scale, center, half))
         reg_here = (not self.distributed) or _dist.world()[0] == 0
         prob = self._problem(lw_dq, rw, huber, reg=reg_here)
         if gate is not None:
@@ -1032,33 +1159,37 @@ class WarpSolver:
             _lib.check(self.lib.dfh_gn_build(prob, frame, current_stream_ptr()), "dfh_gn_build")
         if reg_here:
             self._add_landmarks(lw_dq)
+        self._add_photometric(lw_dq, frame, colors)
         self._allreduce_system()
 
     def iterate_associated(self, depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist=0.0, huber=0.0, lm_abs=0.0, lm_rel=0.0,
-                           n_iters=1, n_global=0, global_lm=0.1, normals=None, normal_cos=0.5):
+                           n_iters=1, n_global=0, global_lm=0.1, normals=None, normal_cos=0.5, colors=None):
         """n_global rigid-mode steps (build_associated + global_step each), then n_iters GN iterations (build_associated +
         solve_update each).  On one GPU (no all-reduce between the halves) they are ONE call, dfh_gn_solve: the iterations are
         queued back to back without returning to Python, and in each the clearing of the solve's workspace rides in the data-row
         launch -- the same bits as separate calls.  option py_gn_iter_per_call: one dfh_gn_solve call per iteration.
         normals / normal_cos: the normal gate of associate_depth in every build (dfh_gn_solve_gated; the py_gn_* options steer the
-        gated sequences as they steer the ungated ones, and all of them leave the same bits)."""
+        gated sequences as they steer the ungated ones, and all of them leave the same bits).
+        colors: one colour image per depth map: every build adds the photometric term (set_photometric; dfh_gn_solve_photometric on
+        the one-call path, with the landmark term beside it where both are set)."""
         if self._pattern is None:
             self._build_pattern()
         frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
         gate = self._gate(normals, normal_cos, frame)
         lmt = self._landmark_term()                   # (with landmarks: dfh_gn_solve_landmarks, the ungated depth term only)
+        pht = self._photo_term(colors, frame)         # (with colour rows: dfh_gn_solve_photometric, likewise)
         one_call = (frame.depth_dtype == _lib.F32 and self.S > 0 and not _lib.opt_on("py_gn_atomic") and
                     not _lib.opt_on("py_gn_no_fused_assoc") and not _lib.opt_on("py_gn_no_fused_iter") and
                     not (self.distributed and (_dist.world()[1] > 1 or self.force_collective)) and
-                    not (lmt is not None and gate is not None))
+                    not ((lmt is not None or pht is not None) and gate is not None))
         per_call = one_call and _lib.opt_on("py_gn_iter_per_call")
         if not one_call or per_call:
             for _ in range(int(n_global)):                # the rigid mode first (global_step): one twist for all nodes
-                self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber, normals, normal_cos)
+                self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber, normals, normal_cos, colors)
                 self.global_step(global_lm)
             if not one_call:
                 for _ in range(int(n_iters)):
-                    self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber, normals, normal_cos)
+                    self.build_associated(depth, K, Kinv, lw_cam, scale, center, half, lw_dq, rw, max_dist, huber, normals, normal_cos, colors)
                     self.solve_update(lm_abs, lm_rel)
                 return
             frame = self._frame(depth, lw_cam, K, Kinv, scale, center, half, max_dist)
@@ -1068,6 +1199,8 @@ class WarpSolver:
         for _ in range(int(n_iters) if per_call else 1):
             if gate is not None:
                 _lib.check(self.lib.dfh_gn_solve_gated(prob, frame, gate, sp, current_stream_ptr()), "dfh_gn_solve_gated")
+            elif pht is not None:
+                _lib.check(self.lib.dfh_gn_solve_photometric(prob, frame, lmt, pht, sp, current_stream_ptr()), "dfh_gn_solve_photometric")
             elif lmt is not None:
                 _lib.check(self.lib.dfh_gn_solve_landmarks(prob, frame, lmt, sp, current_stream_ptr()), "dfh_gn_solve_landmarks")
             else:

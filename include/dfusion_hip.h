@@ -611,6 +611,79 @@ int dfh_gn_add_landmarks(const dfh_gn_problem *problem, const dfh_gn_landmarks *
 int dfh_gn_solve_landmarks(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_landmarks *landmarks,
                            const dfh_gn_solve_params *params, void *stream);
 
+/* The photometric term: one colour-consistency row per sample (opt-in: the calls above know nothing of it).  The data rows
+ * n'.(x' - c) cannot see motion inside the surface, and landmarks need feature matches the caller has to bring; an RGB-D frame's
+ * colour images constrain the tangential motion densely (VolumeDeform, KillingFusion): a canonical point with a reference
+ * intensity ref (the luma of the colour volume, dfh_sample_colors) should project onto a live pixel of that intensity.  The
+ * reference has no counterpart (it reconstructs geometry only).  Everything is fp64, operation by operation in this order, no
+ * contraction.  For photo sample l with its knn nodes nbr[l][.] and static blend weights weights[l][.] (knn = the problem's), a
+ * frame (the packed views, K, Kinv, scale, center, half; its max_dist is not read) and the views' colour images color[v] (K17's
+ * format: uint8 [v][u][4] R, G, B, X of the depth maps' H x W, a HOST array of n_views device pointers as dfh_integrate_color takes):
+ *  1. x' = the sample warped exactly as dfh_gn_landmarks step 1: x' = dqb_warp(lw_dq, f32(dqb_warp(b^, f32(p)))).
+ *  2. for every view 0 .. n_views-1 in turn, the association's chain:
+ *       pos  = scale*(x' - half) + center
+ *       lpos = lw*[pos,1]  (l_i = ((lw_i0*pos_0 + lw_i1*pos_1) + lw_i2*pos_2) + lw_i3)
+ *       (a, b, c) = K*lpos  (each (K_i0*l_0 + K_i1*l_1) + K_i2*l_2);  skipped if c == 0;  u = a/c, v = b/c  (IEEE divisions)
+ *       visible iff 0 <= u < W-1 and 0 <= v < H-1 (a NaN fails)
+ *       z = -depth[rint(v)][rint(u)] (round-half-even), valid iff z > 0; a z*u or z*v that is not finite passes nothing
+ *       sd = ((Kinv_20*(z*u) + Kinv_21*(z*v)) + Kinv_22*(z*1.0)) - l_2;  the view PASSES iff fabs(sd) <= band_sd (a NaN fails)
+ *  3. the sample's view is the passing view with the smallest fabs(sd): a view replaces the best so far iff its fabs(sd) is
+ *     strictly smaller (the best starts at +inf), so ties go to the lowest index.
+ *  4. intensity in that view: a pixel's Y = (double)(77*R + 150*G + 29*B) / 256.0 (exact);  i0 = (int)floor(u), j0 = (int)floor(v),
+ *     fu = u - i0, fv = v - j0;  Y00 = Y[j0][i0], Y10 = Y[j0][i0+1], Y01 = Y[j0+1][i0], Y11 = Y[j0+1][i0+1];
+ *       I  = (1-fv)*((1-fu)*Y00 + fu*Y10) + fv*((1-fu)*Y01 + fu*Y11)
+ *       Iu = (1-fv)*(Y10-Y00) + fv*(Y11-Y01)
+ *       Iv = (1-fu)*(Y01-Y00) + fu*(Y11-Y10)
+ *     Iu, Iv are the exact derivatives of the bilinear interpolant inside the cell: no gradient image, no second pass.
+ *  5. r = I - ref[l];  s2 = weight * conf[l] (conf == NULL: 1).  The sample is ACTIVE iff valid[l] != 0 (valid == NULL: 1), s2 > 0, a
+ *     view passed, fabs(r) < +inf (a NaN ref fails) and (max_diff <= 0 or fabs(r) <= max_diff).  Scalar Huber on |r| (delta in
+ *     intensity units), K16 step 4 with q = r*r: if huber_delta > 0 and q > huber_delta*huber_delta: n = sqrt(q),
+ *     obj = s2*huber_delta*(n - 0.5*huber_delta), sc = sqrt(s2)*sqrt(huber_delta/n); otherwise obj = 0.5*s2*q, sc = sqrt(s2).
+ *  6. the image gradient pulled back to index space, with R the 3x3 part of the view's lw:
+ *       du_j = (K_0j - u*K_2j)/c,  dv_j = (K_1j - v*K_2j)/c,  h_j = Iu*du_j + Iv*dv_j          (j = 0, 1, 2: d I / d lpos)
+ *       g_i  = scale*((h_0*R_0i + h_1*R_1i) + h_2*R_2i)                                        (i = 0, 1, 2: d I / d x')
+ *     one row: residual sc*r, Jacobian sc*J, J = the landmark term's axis row (dfh_gn_landmarks step 5) with the axis e_a replaced
+ *     by the vector g: U = pure(vec(rl* g rl)), then the same g_r, g_d, projection off b^, division by |b|_8 and per-node
+ *     products.  g is held constant while the row is differentiated -- the Gauss-Newton linearisation of I(x'(xi)): the pixel, the
+ *     cell and the view are not differentiated.
+ *  7. vals += J^T J, rhs += J^T r, cost_count[0] += sum of obj; cost_count[1] (the valid SAMPLES) is left alone.  Node pairs that
+ *     are no block of the pattern are dropped silently, as for samples.
+ * The samples arrive sorted by node tuple with a plan laid out as dfh_gn_problem's data plan (the solver's own samples bring the
+ * data plan itself; only `partial`, sized as dfh_gn_problem.partial is, must be the term's own).  No floating-point atomics: the
+ * same bits every run.  Outputs (each may be NULL): active_out[l] = 1 iff active; view_out[l] = the sample's view, -1 when
+ * inactive; resid_out[l] = the unscaled r, 0 when inactive.  Restated in tests/photometric_np.py.
+ * dfh_gn_add_photometric: adds the term to the system any build left in the problem (reads node_dq, lw_dq, knn, the pattern and
+ * blk_upper; adds to vals / rhs / cost_count); depth maps of either dtype.  dfh_gn_solve_photometric: dfh_gn_solve_landmarks'
+ * schedule with the photometric term added after every build (after the landmark term where both are given), the rigid-mode
+ * steps' builds included -- the same bits as the separate calls.  landmarks == NULL: no landmark term.  photo == NULL: the call
+ * sequence of dfh_gn_solve_landmarks (of dfh_gn_solve when landmarks == NULL too); with photo the frame is required (DFH_F32 maps).
+ * DFH_E_BADARG (before any HIP call): what dfh_gn_build / dfh_gn_solve refuse, a null struct, n < 0, with n > 0 a null pos / nbr /
+ * weights / ref / run_id / partial / blk_ptr / node_ptr (or, with n_rows > 0, blk_ent / node_ent) or n_rows < 1, weight negative or
+ * not finite, huber_delta negative or NaN, max_diff NaN, band_sd not > 0 (NaN refused, +inf allowed), a null frame (or one
+ * dfh_gn_associate refuses), a null color or color[v].  n == 0 or weight == 0: DFH_OK, nothing is launched by the term and the
+ * system is left as it is. */
+typedef struct dfh_gn_photometric {
+    const double *pos;            /* n x 3 canonical positions (index space), sorted by node tuple */
+    const int *nbr;               /* n x knn */
+    const double *weights;        /* n x knn static blend weights */
+    const double *ref;            /* n reference intensities (0..255) */
+    const unsigned char *valid;   /* n, may be NULL (all valid) */
+    const double *conf;           /* n, may be NULL (all 1) */
+    int n;
+    double weight, huber_delta, max_diff, band_sd;
+    const void *const *color;     /* HOST array of frame->n_views device pointers to H x W RGBX images */
+    const int *run_id;            /* the samples' plan, laid out as dfh_gn_problem's data plan */
+    int n_rows;
+    double *partial;
+    const int *blk_ptr, *blk_ent, *node_ptr, *node_ent;
+    unsigned char *active_out;    /* n, may be NULL */
+    int *view_out;                /* n, may be NULL */
+    double *resid_out;            /* n, may be NULL */
+} dfh_gn_photometric;
+int dfh_gn_add_photometric(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_photometric *photo, void *stream);
+int dfh_gn_solve_photometric(const dfh_gn_problem *problem, const dfh_gn_frame *frame, const dfh_gn_landmarks *landmarks,
+                             const dfh_gn_photometric *photo, const dfh_gn_solve_params *params, void *stream);
+
 /* Multi-GPU solve: what travels in the per-iteration all-reduce.  `system` = {J^T J blocks (n_blocks x 36) | J^T r (6 n_nodes) |
  * cost, count} as the builds write it; J^T J is symmetric, so only the blocks with col >= row are packed (then J^T r and
  * {cost, count}): (36 n_upper + 6 n_nodes + 2) doubles in `packed`, about 55 % of the system.  row_of[b] / col[b]: block b's
