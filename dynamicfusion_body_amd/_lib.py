@@ -114,6 +114,20 @@ class Photometric(ctypes.Structure):
                 ("node_ent", _vp), ("active_out", _vp), ("view_out", _vp), ("resid_out", _vp)]
 
 
+class RGBDView(ctypes.Structure):
+    """dfh_rgbd_view: one view's calibration for dfh_rgbd_ingest -- raw depth camera, colour camera, depth -> colour transform."""
+    _fields_ = [("fd", _dbl * 4), ("kd", _dbl * 5), ("fc", _dbl * 4), ("kc", _dbl * 5), ("T_dc", _dbl * 12)]
+
+
+class RGBDIngestParams(ctypes.Structure):
+    """dfh_rgbd_ingest_params: the raw maps and images (host arrays of device pointers the caller keeps alive), the output
+    pinhole, the decode range, the occlusion test's settings and the views' calibration (a host array)."""
+    _fields_ = [("n_views", _int), ("raw_depth", ctypes.POINTER(_vp)), ("raw_color", ctypes.POINTER(_vp)),
+                ("Hd", _int), ("Wd", _int), ("Hc", _int), ("Wc", _int), ("C", _int),
+                ("fx", _dbl), ("fy", _dbl), ("cx", _dbl), ("cy", _dbl), ("depth_scale", _dbl), ("z_min", _dbl), ("z_max", _dbl),
+                ("occl_tol", _dbl), ("max_splat", _int), ("sample", _int), ("views", ctypes.POINTER(RGBDView))]
+
+
 _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
@@ -126,7 +140,7 @@ STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_param
            "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes,
            "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams,
            "dfh_gn_normal_gate": NormalGate, "dfh_gn_landmarks": Landmarks, "dfh_color_volume": ColorVolume,
-           "dfh_gn_photometric": Photometric}
+           "dfh_gn_photometric": Photometric, "dfh_rgbd_view": RGBDView, "dfh_rgbd_ingest_params": RGBDIngestParams}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -236,6 +250,9 @@ _SIGNATURES = {
     "dfh_integrate_color": (_int, [ctypes.POINTER(ColorVolume), _volume_p, ctypes.POINTER(DepthViews), ctypes.POINTER(_vp),
                                    ctypes.POINTER(Nodes), _c_double_p, _dbl, _dbl, _dbl, _dbl, _vp, ctypes.c_size_t, _int, _vp]),
     "dfh_sample_colors": (_int, [ctypes.POINTER(ColorVolume), _vp, ctypes.c_long, _vp, _vp, _vp]),
+    "dfh_rgbd_ingest": (_int, [ctypes.POINTER(RGBDIngestParams), _vp, _vp, _vp, _vp, _vp]),
+    "dfh_rgbd_ingest_workspace_bytes": (ctypes.c_size_t, [_int, _int, _int]),
+    "dfh_rgbd_ingest_tile": (_int, [_c_int_p]),
 }
 
 _lib = None

@@ -29,6 +29,8 @@ class Fusion:
                                  # the reference calls compute_correspondence(self.input, self._feature, self._sess, vertices, faces)
                                  # (core/fusion.py:280-281); with it setupCorrespondences(method='cnn') takes the reference's CNN branch
                                  # (descriptors.PooledDescriptors(feature_fn) is that function around a per-pixel feature network)
+    ingest = None                # an ingest.RGBDIngest: the same methods then take the sensor's RAW frames (uint16 depth maps, raw colour
+                                 # images) and run them through the stage first, in front of depth_prep; K must equal ingest.K
     depth_prep = None            # a depth_prep.DepthPrep: the methods that sweep a LIST of depth maps (InitializeCanonicalSpace from
                                  # maps, updateTSDF_depths) clean the list with it first; the single-map fuseDepths stays raw
 
@@ -172,6 +174,9 @@ class Fusion:
                 raise ValueError('depth map must be 2-D')
             if tuple(d.shape) != tuple(depths[0].shape):
                 raise ValueError('all depth maps of one call must have the same shape')
+        color_depths = None
+        if self.ingest is not None and depths:                       # raw frames in; the colour fusion reads the colour-only maps
+            depths, colors, color_depths = self.ingest.frame(depths, colors, K=self._K)
         if self.depth_prep is not None and depths:
             depths = self.depth_prep(depths, self._Kinv, want_normals=False)[0]
 
@@ -193,8 +198,8 @@ class Fusion:
         if colors is not None:
             if self._C is None:
                 self._C = kernels.color_volume(res)
-            kernels.integrate_color(self._C, self._T, self._Wt, ds, colors, self._K, self._Kinv, lws, scale, center, self._tdist,
-                                    color_band, pos, dq, w, self._knn, np.asarray(self._lw, dtype=np.float64), tsdf_res=res[0],
+            kernels.integrate_color(self._C, self._T, self._Wt, ds if color_depths is None else color_depths, colors, self._K,
+                                    self._Kinv, lws, scale, center, self._tdist, color_band, pos, dq, w, self._knn, np.asarray(self._lw, dtype=np.float64), tsdf_res=res[0],
                                     workspace=self._workspace,
                                     stored_indices=kernels.dqb_has_indices(self._workspace, res, self._knn, len(pos)))
 
@@ -636,6 +641,9 @@ class Fusion:
             self._T = torch.empty((R, R, R), dtype=self._vol_dtype, device="cuda")
             self._Wt = torch.empty_like(self._T)
             self._tsdf_host = None
+            color_depths = None
+            if self.ingest is not None and len(depths) > 0:
+                depths, colors, color_depths = self.ingest.frame(depths, colors, K=self._K)
             if self.depth_prep is not None and len(depths) > 0:
                 depths = self.depth_prep(depths, self._Kinv, want_normals=False)[0]
             # (the dtype rule of fuseDepths: float32 on the device unless a float64 map is not float32-exact -- then every map
@@ -649,8 +657,8 @@ class Fusion:
             self._C = None
             if colors is not None and len(ds) > 0:
                 self._C = kernels.color_volume((R, R, R))
-                kernels.integrate_color(self._C, self._T, self._Wt, ds, colors, self._K, self._Kinv,
-                                        [np.asarray(m, dtype=np.float64) for m in lws], scale, center, self._tdist, color_band)
+                kernels.integrate_color(self._C, self._T, self._Wt, ds if color_depths is None else color_depths, colors, self._K,
+                                        self._Kinv, [np.asarray(m, dtype=np.float64) for m in lws], scale, center, self._tdist, color_band)
         else:
             raise ValueError('InitializeCanonicalSpace needs a tsdf, or depths, lws and K')
         if K is not None and getattr(self, '_K', None) is None:

@@ -32,6 +32,8 @@ def _is_tensor(a):
 
 
 class FusionDM:
+    ingest = None                # an ingest.RGBDIngest: compute_live_tsdf then takes the sensor's RAW frames (uint16 depth maps, raw colour
+                                 # images) and runs them through the stage first, in front of depth_prep; set on an instance
     depth_prep = None            # a depth_prep.DepthPrep: compute_live_tsdf cleans its list of maps with it first; set on an instance
 
     def __init__(self, trunc_distance, K, tsdf_res=256, subsample_rate=5.0, knn=4, marching_cubes_step_size=3,
@@ -368,6 +370,9 @@ class FusionDM:
                 raise ValueError('colors cannot be fused with useICP=True: every view gets a rigid alignment of its own there')
             if len(colors) != len(depths):
                 raise ValueError('one colour image per depth map')
+        color_depths = None
+        if self.ingest is not None and len(depths) > 0:              # raw frames in; the colour fusion reads the colour-only maps
+            depths, colors, color_depths = self.ingest.frame(depths, colors, K=self._K)
         if self.depth_prep is not None and len(depths) > 0:          # (the single-map fuseDepths stays raw: the reference's meaning)
             depths = self.depth_prep(depths, self._Kinv, want_normals=False)[0]
         avg = np.array([-0.03, -0.43, -5.6], dtype='float32')       # :106-107
@@ -417,7 +422,8 @@ class FusionDM:
         if colors is not None:
             self._C = kernels.color_volume(tuple(self._T.shape))
             for idx in range(len(dev)):                             # (one call per view: the maps may differ in shape or dtype)
-                kernels.integrate_color(self._C, self._T, self._Wt, [dev[idx]], [colors[idx]], self._K, self._Kinv,
+                kernels.integrate_color(self._C, self._T, self._Wt, [dev[idx] if color_depths is None else color_depths[idx]],
+                                        [colors[idx]], self._K, self._Kinv,
                                         [np.asarray(lws[idx], dtype=np.float64)], 12 * std / res, avg, self._tdist, color_band,
                                         tsdf_res=self._tsdf_res)
         if outputMesh:                                              # :174-176

@@ -71,3 +71,73 @@ def read_warp_field(fname):
     """Files written by write_warp_field of THIS package (never unpickle untrusted files)."""
     with open(fname, 'rb') as f:
         return pickle.load(f)
+
+
+# ---- binary Netpbm: what a raw RGB-D capture can be stored in without an image library (ingest.RGBDIngest's inputs) ----
+def _netpbm_header(buf, magic, path):
+    """(width, height, maxval, offset of the raster) of a binary Netpbm file: whitespace-separated decimal fields, '#' comments to
+    the end of the line, ONE whitespace byte after maxval."""
+    if buf[:2] != magic:
+        raise ValueError('%s: not a binary %s file' % (path, magic.decode()))
+    pos, fields = 2, []
+    while len(fields) < 3:
+        while pos < len(buf) and (buf[pos:pos + 1].isspace() or buf[pos:pos + 1] == b'#'):
+            if buf[pos:pos + 1] == b'#':
+                while pos < len(buf) and buf[pos:pos + 1] not in (b'\n', b'\r'):
+                    pos += 1
+            else:
+                pos += 1
+        end = pos
+        while end < len(buf) and buf[end:end + 1].isdigit():
+            end += 1
+        if end == pos:
+            raise ValueError('%s: bad Netpbm header' % path)
+        fields.append(int(buf[pos:end]))
+        pos = end
+    if not buf[pos:pos + 1].isspace():
+        raise ValueError('%s: bad Netpbm header' % path)
+    return fields[0], fields[1], fields[2], pos + 1
+
+
+def read_pgm16(path):
+    """A binary PGM (P5) with maxval 256..65535 -> (H, W) uint16 (the samples are big-endian in the file)."""
+    with open(path, 'rb') as f:
+        buf = f.read()
+    w, h, maxval, off = _netpbm_header(buf, b'P5', path)
+    if not 255 < maxval <= 65535:
+        raise ValueError('%s: maxval %d is not a 16-bit PGM (256..65535)' % (path, maxval))
+    if len(buf) - off < 2 * w * h:
+        raise ValueError('%s: truncated raster' % path)
+    return np.frombuffer(buf, dtype='>u2', count=w * h, offset=off).reshape(h, w).astype(np.uint16)
+
+
+def write_pgm16(path, image):
+    """(H, W) uint16 -> binary PGM (P5), maxval 65535, big-endian samples."""
+    a = np.asarray(image)
+    if a.ndim != 2 or a.dtype != np.uint16:
+        raise ValueError('write_pgm16 takes an (H, W) uint16 array')
+    with open(path, 'wb') as f:
+        f.write(b'P5\n%d %d\n65535\n' % (a.shape[1], a.shape[0]))
+        f.write(a.astype('>u2').tobytes())
+
+
+def read_ppm(path):
+    """A binary PPM (P6) with maxval 255 -> (H, W, 3) uint8."""
+    with open(path, 'rb') as f:
+        buf = f.read()
+    w, h, maxval, off = _netpbm_header(buf, b'P6', path)
+    if maxval != 255:
+        raise ValueError('%s: maxval %d is not an 8-bit PPM' % (path, maxval))
+    if len(buf) - off < 3 * w * h:
+        raise ValueError('%s: truncated raster' % path)
+    return np.frombuffer(buf, dtype=np.uint8, count=3 * w * h, offset=off).reshape(h, w, 3).copy()
+
+
+def write_ppm(path, image):
+    """(H, W, 3) uint8 -> binary PPM (P6), maxval 255."""
+    a = np.asarray(image)
+    if a.ndim != 3 or a.shape[2] != 3 or a.dtype != np.uint8:
+        raise ValueError('write_ppm takes an (H, W, 3) uint8 array')
+    with open(path, 'wb') as f:
+        f.write(b'P6\n%d %d\n255\n' % (a.shape[1], a.shape[0]))
+        f.write(np.ascontiguousarray(a).tobytes())

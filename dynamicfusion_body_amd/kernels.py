@@ -569,3 +569,115 @@ def depth_prep(depths, Kinv, tables, max_jump, min_cos, mask=True, want_normals=
     if out is not None:
         torch.autograd.graph.increment_version(tuple(t for t in (clean, normals) if t is not None))
     return clean, normals
+
+
+def rgbd_ingest_tile():
+    """(rows, columns) of the output tile a workgroup of the RGB-D ingest kernels owns (dfh_rgbd_ingest_tile; no launch)."""
+    hw = (ctypes.c_int * 2)()
+    _lib.check(_lib.load().dfh_rgbd_ingest_tile(hw), "dfh_rgbd_ingest_tile")
+    return int(hw[0]), int(hw[1])
+
+
+def rgbd_ingest_workspace(n_views, Hc, Wc, device=None):
+    """The workspace of one rgbd_ingest call with colour: an int32 tensor of dfh_rgbd_ingest_workspace_bytes(); its first
+    n_views * Hc * Wc elements are the colour camera's z-buffer after the call (rgbd_ingest returns that view)."""
+    nbytes = _lib.load().dfh_rgbd_ingest_workspace_bytes(int(n_views), int(Hc), int(Wc))
+    if nbytes == 0:
+        raise ValueError("bad z-buffer size: %d views of %d x %d" % (n_views, Hc, Wc))
+    return torch.empty((nbytes + 7) // 8 * 2, dtype=torch.int32, device=device or "cuda")
+
+
+RGBD_SAMPLE = {"nearest": 0, "bilinear": 1}
+
+
+def rgbd_ingest(raw_depths, raw_colors, views, out_intrinsics, depth_scale=1e-3, z_min=0.0, z_max=0.0, occl_tol=0.0, max_splat=8,
+                sample="bilinear", want_color_depth=True, out=None, workspace=None):
+    """K19 = raw sensor frames to frame inputs in at most three launches (dfh_rgbd_ingest; semantics in include/dfusion_hip.h).
+    raw_depths: list of at most 16 (Hd, Wd) uint16 CUDA tensors (torch.uint16, or int16 holding the same bits), only read.
+    raw_colors: None, or one (Hc, Wc, 3) / (Hc, Wc, 4) uint8 CUDA tensor per depth map.  views: one record per map,
+    (fd[4], kd[5], fc[4], kc[5], T_dc[12]) -- 30 numbers, or a 5-tuple of those arrays -- or a ready (_lib.RGBDView * V) array.  out_intrinsics: (fx, fy, cx, cy) of the
+    pinhole the output maps are resampled to.
+    Returns (depth (V, Hd, Wd) float32, color (V, Hd, Wd, 4) uint8 or None, color_depth (V, Hd, Wd) float32 or None,
+    zbuf (V, Hc, Wc) int32 view of the workspace or None).
+    out=(depth, color, color_depth): write into these tensors instead of fresh ones (color_depth may be None: not produced).  The
+    kernels write through raw pointers, so the tensors' version counters are bumped here, as depth_prep does.
+    workspace: an rgbd_ingest_workspace(V, Hc, Wc) to reuse (default: a fresh one)."""
+    raw_depths = list(raw_depths)
+    V = len(raw_depths)
+    if V == 0:
+        raise ValueError("rgbd_ingest needs at least one depth map")
+    if V > 16:
+        raise ValueError("at most 16 views per call, got %d" % V)
+    u16 = tuple(t for t in (getattr(torch, "uint16", None), torch.int16) if t is not None)
+    for d in raw_depths:
+        if not (isinstance(d, torch.Tensor) and d.dim() == 2 and d.dtype in u16):
+            raise ValueError("a raw depth map must be a contiguous 2-D 16-bit integer CUDA tensor")
+        if d.shape != raw_depths[0].shape:
+            raise ValueError("all raw depth maps of one call must have the same shape")
+    colour = raw_colors is not None
+    if colour:
+        raw_colors = list(raw_colors)
+        if len(raw_colors) != V:
+            raise ValueError("one colour image per depth map: %d images for %d maps" % (len(raw_colors), V))
+        for c in raw_colors:
+            if not (isinstance(c, torch.Tensor) and c.dim() == 3 and c.dtype == torch.uint8 and c.shape[2] in (3, 4)):
+                raise ValueError("a raw colour image must be a contiguous (H, W, 3) or (H, W, 4) uint8 CUDA tensor")
+            if c.shape != raw_colors[0].shape:
+                raise ValueError("all raw colour images of one call must have the same shape")
+    if sample not in RGBD_SAMPLE:
+        raise ValueError("sample must be one of %s, not %r" % (sorted(RGBD_SAMPLE), sample))
+    if not (isinstance(views, ctypes.Array) and getattr(views, "_type_", None) is _lib.RGBDView):
+        views = list(views)
+    if len(views) != V:
+        raise ValueError("one calibration record per depth map: %d records for %d maps" % (len(views), V))
+    prepacked = isinstance(views, ctypes.Array) and getattr(views, "_type_", None) is _lib.RGBDView
+    recs = views if prepacked else (_lib.RGBDView * V)()
+    for r, v in zip(recs, () if prepacked else views):
+        a = np.concatenate([np.asarray(x, dtype=np.float64).reshape(-1) for x in v]) if isinstance(v, (tuple, list)) and len(v) == 5 \
+            else np.asarray(v, dtype=np.float64).reshape(-1)
+        if a.size != 30:
+            raise ValueError("a calibration record is fd[4], kd[5], fc[4], kc[5], T_dc[12]: 30 numbers, got %d" % a.size)
+        ctypes.memmove(ctypes.byref(r), np.ascontiguousarray(a).ctypes.data, 240)
+    fx, fy, cx, cy = (float(x) for x in np.asarray(out_intrinsics, dtype=np.float64).reshape(-1))
+    require_gpu()
+    lib = _lib.load()
+    for t in raw_depths + (raw_colors if colour else []):
+        if not (t.is_cuda and t.is_contiguous()):
+            raise ValueError("raw maps and images must be contiguous CUDA tensors")
+    dev = raw_depths[0].device
+    Hd, Wd = (int(n) for n in raw_depths[0].shape)
+    Hc, Wc, C = (int(n) for n in raw_colors[0].shape) if colour else (0, 0, 0)
+    if out is None:
+        depth = torch.empty((V, Hd, Wd), dtype=torch.float32, device=dev)
+        color = torch.empty((V, Hd, Wd, 4), dtype=torch.uint8, device=dev) if colour else None
+        cdepth = torch.empty((V, Hd, Wd), dtype=torch.float32, device=dev) if colour and want_color_depth else None
+    else:
+        depth, color, cdepth = out
+        for t, shape, dt in ((depth, (V, Hd, Wd), torch.float32), (color, (V, Hd, Wd, 4), torch.uint8), (cdepth, (V, Hd, Wd), torch.float32)):
+            if t is not None and not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == dt and t.is_contiguous() and
+                                      tuple(t.shape) == shape):
+                raise ValueError("out tensor must be a contiguous %s CUDA tensor of shape %s" % (dt, shape))
+        if depth is None or (colour and color is None):
+            raise ValueError("out needs a depth tensor, and a color tensor when colour images are given")
+        if not colour:
+            color = cdepth = None
+    zbuf = None
+    if colour:
+        nbytes = lib.dfh_rgbd_ingest_workspace_bytes(V, Hc, Wc)
+        if workspace is None:
+            workspace = rgbd_ingest_workspace(V, Hc, Wc, dev)
+        elif not (isinstance(workspace, torch.Tensor) and workspace.device == dev and workspace.is_contiguous() and
+                  workspace.numel() * workspace.element_size() >= nbytes):
+            raise ValueError("workspace must be a contiguous CUDA tensor of at least %d bytes" % nbytes)
+        zbuf = workspace.view(torch.int32)[:V * Hc * Wc].view(V, Hc, Wc)
+    dptrs = (ctypes.c_void_p * V)(*[d.data_ptr() for d in raw_depths])
+    cptrs = (ctypes.c_void_p * V)(*[c.data_ptr() for c in raw_colors]) if colour else None
+    prm = _lib.RGBDIngestParams(V, dptrs, cptrs, Hd, Wd, Hc, Wc, C, fx, fy, cx, cy, float(depth_scale), float(z_min), float(z_max),
+                                float(occl_tol), int(max_splat), RGBD_SAMPLE[sample], recs)
+    rc = lib.dfh_rgbd_ingest(prm, depth.data_ptr(), None if color is None else color.data_ptr(),
+                             None if cdepth is None else cdepth.data_ptr(), None if workspace is None or not colour else workspace.data_ptr(),
+                             current_stream_ptr())
+    _lib.check(rc, "dfh_rgbd_ingest")
+    if out is not None:
+        torch.autograd.graph.increment_version(tuple(t for t in (depth, color, cdepth) if t is not None))
+    return depth, color, cdepth, zbuf

@@ -204,8 +204,15 @@ class SlabFrame:
 
     def __init__(self, K, scale, center, res, tdist_vox, node_pos, node_w, knn=4, pcg_iters=10, band=4.0, volume_dtype=torch.float32,
                  distributed=True, solve_mode="auto", depth_prep=None, normal_gate=None, color_band=None, photo_weight=0.0,
-                 photo_huber=0.0, photo_max_diff=0.0, photo_band_sd=None):
-        """photo_weight: > 0 switches the photometric term of the solve on (FrameSolver.set_photometric); it needs color_band.  After
+                 photo_huber=0.0, photo_max_diff=0.0, photo_band_sd=None, ingest=None):
+        """ingest: an ingest.RGBDIngest, or None.  step() and integrate() then take the sensor's RAW frames -- uint16 depth maps,
+        one per calibrated view, and (step) the colour camera's raw images -- and run them through the stage first, in front of
+        depth_prep: its depth maps go to everything that read depth before, its registered colours with the depth maps that keep
+        only coloured pixels (`self.color_depth`) to the colour fusion.  The photometric term keeps the frame's depth maps and the
+        registered colours: a pixel without a valid colour reaches it as RGB 0, which is what photo_max_diff is for.  `K` must
+        equal ingest.K, the pinhole the stage resamples to.  The stage's outputs (`self.ingest_depth`, `self.ingest_color`,
+        `self.color_depth`) are rewritten in place by the next call.
+        photo_weight: > 0 switches the photometric term of the solve on (FrameSolver.set_photometric); it needs color_band.  After
         every sample refresh the samples' reference intensities are the luma of the colour volume at their canonical positions
         (kernels.sample_colors; samples the volume has no colour for get no row), and the next step(colors=...) compares them with
         that frame's colour images in every build of its solve (the depth data term) -- before the images are fused, which is
@@ -267,6 +274,11 @@ class SlabFrame:
                               distributed=self.distributed and self.ws > 1 and solve_mode == "sharded")
         if (node_pos is None) != (node_w is None):
             raise ValueError("node_pos and node_w come together (both None: construct_graph() builds the graph)")
+        self.ingest = ingest
+        if ingest is not None and not np.array_equal(self.K, np.asarray(ingest.K, dtype=np.float64)):
+            raise ValueError("K must equal ingest.K: the stage resamples every depth map to that pinhole")
+        self.ingest_depth = self.ingest_color = self.color_depth = None
+        self._ingest_out = None                  # the stage's output buffers, reused from frame to frame
         self.depth_prep = depth_prep
         self.normal_gate = self._check_normal_gate(normal_gate, depth_prep)
         self.clean_depth = self.live_normals = None
@@ -330,9 +342,33 @@ class SlabFrame:
             self.knn_bricks = ((R, R, R), (self.a, self.b), self.ws_dqb)
         self._first = True                               # K3 stores its per-voxel neighbourhoods again on the next call
 
+    def _ingest(self, raw_depths, raw_colors):
+        """The ingest stage on one frame's raw maps (and images): (list of depth maps, list of registered colour images or None,
+        list of colour-only depth maps or None), views of buffers the next call rewrites."""
+        V = len(raw_depths)
+        have = self._ingest_out
+        if have is None or have[0].shape[0] != V or (raw_colors is not None and have[1] is None):
+            have = None
+        d, c, cd = self.ingest(raw_depths, raw_colors, out=None if have is None else (have[0], have[1] if raw_colors is not None else None,
+                                                                                      have[2] if raw_colors is not None else None))
+        if have is None:
+            self._ingest_out = (d, c, cd)
+        self.ingest_depth, self.ingest_color, self.color_depth = d, c, cd
+        return [d[v] for v in range(V)], None if c is None else [c[v] for v in range(V)], None if cd is None else [cd[v] for v in range(V)]
+
     def integrate(self, depth, lw_cam):
-        """Fuse a depth map into this rank's canonical slab (initial frames)."""
+        """Fuse a depth map into this rank's canonical slab (initial frames).  With the constructor's ingest: `depth` is the
+        frame's raw uint16 maps, one per calibrated view, and lw_cam their extrinsics (lists; a single map for a one-view rig)."""
         R = self.R
+        if self.ingest is not None:
+            raw = list(depth) if isinstance(depth, (list, tuple)) else [depth]
+            lws = list(lw_cam) if isinstance(depth, (list, tuple)) else [lw_cam]
+            if len(raw) != len(lws):
+                raise ValueError('length of camera matrix array must equal that of depth maps')
+            for d, lw in zip(self._ingest(raw, None)[0], lws):
+                kernels.integrate_depth(self.T, self.Wt, d, self.K, self.Kinv, lw, self.scale, self.center, self.tdist_world,
+                                        tsdf_res=R, res=(R, R, R), x_range=(self.a, self.b))
+            return
         kernels.integrate_depth(self.T, self.Wt, depth, self.K, self.Kinv, lw_cam, self.scale, self.center, self.tdist_world,
                                 tsdf_res=R, res=(R, R, R), x_range=(self.a, self.b))
 
@@ -654,6 +690,11 @@ class SlabFrame:
             colors = list(colors) if isinstance(colors, (list, tuple)) else [colors]
             if len(colors) != len(depth_list):
                 raise ValueError('one colour image per depth map: %d images for %d maps' % (len(colors), len(depth_list)))
+        color_depth_list = None
+        if self.ingest is not None:               # raw frames in: everything below sees what it always saw
+            depth_list, reg, color_depth_list = self._ingest(depth_list, colors)
+            colors = reg if colors is not None else None
+            mark("ingest")
         if self.depth_prep is not None:
             shape = (len(depth_list),) + tuple(depth_list[0].shape)
             if self._prep_out is None or tuple(self._prep_out[0].shape) != shape or self._prep_out[0].device != depth_list[0].device:
@@ -742,7 +783,9 @@ class SlabFrame:
                                         workspace=self.ws_dqb, rebuild_candidates=self._first)
         self._first = False
         if colors is not None:                 # through the field the update used: before it decays
-            kernels.integrate_color(self.C, self.T, self.Wt, depth_list, colors, self.K, self.Kinv, lw_list, self.scale, self.center,
+            # (with ingest: the maps that keep only the pixels with a valid colour -- the stage's own, unfiltered by depth_prep)
+            kernels.integrate_color(self.C, self.T, self.Wt, depth_list if color_depth_list is None else color_depth_list, colors,
+                                    self.K, self.Kinv, lw_list, self.scale, self.center,
                                     self.tdist_world, self.color_band, sv.node_pos, sv.node_dq, sv.node_w, self.knn, self.ident_lw,
                                     tsdf_res=R, res=(R, R, R), x_range=(self.a, self.b), workspace=self.ws_dqb,
                                     stored_indices=kernels.dqb_has_indices(self.ws_dqb, (R, R, R), self.knn, int(sv.node_pos.shape[0]),

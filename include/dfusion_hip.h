@@ -1078,6 +1078,82 @@ int dfh_integrate_color(const dfh_color_volume *cvol, const dfh_volume *vol, con
 int dfh_sample_colors(const dfh_color_volume *cvol, const double *points, long n, float *rgb_out, unsigned char *valid_out,
                       void *stream);
 
+/* ---- K19  RGB-D ingest: raw depth and unregistered colour to frame inputs -----------------------------------------------------
+ * What a sensor delivers -- uint16 depth in device units through a distorted lens with its own intrinsics, and the image of a
+ * second, colour camera beside it -- becomes what every other entry point reads: per view an undistorted depth map through ONE
+ * output pinhole (negative depth, 0 = no measurement), the colour registered to the depth pixels (K17's RGBX, X = 255 where the
+ * colour is valid) and a depth map that keeps only the pixels that have a colour (K17's own `depths`).  A background pixel the
+ * colour camera cannot see must not take the foreground's colour: the colour camera's z-buffer is splatted with every depth
+ * pixel's projected rectangle and a pixel whose depth lies behind the buffer gets no colour.
+ * All arithmetic is fp64 with ONE rounding per operation (no contraction, IEEE division; rint rounds half to even), in the order
+ * written here, so that tests/ingest_np.py agrees bit for bit on every output and on the z-buffer.
+ *
+ * distort(x, y; k) with k = (k1, k2, p1, p2, k3), OpenCV's Brown-Conrady order:
+ *   r2 = x*x + y*y;  rad = 1 + r2*(k1 + r2*(k2 + r2*k3))
+ *   xd = x*rad + ((2*p1)*(x*y) + p2*(r2 + 2*(x*x)));   yd = y*rad + (p1*(r2 + 2*(y*y)) + (2*p2)*(x*y))
+ *   If all five coefficients are exactly 0 the function is the identity: it is skipped, not evaluated.
+ * ideal(a, b) = ((a - cx)/fx, (b - cy)/fy) with the OUTPUT intrinsics; a, b are pixel coordinates as doubles.
+ *
+ * A. Decode and rectify, per view and output pixel (i, j) (column, row) of the Hd x Wd output map:
+ *   (x, y) = ideal(i, j);  (xd, yd) = distort(x, y; kd);  us = fd[0]*xd + fd[2];  vs = fd[1]*yd + fd[3]      (fd = fx fy cx cy)
+ *   (si, sj) = (rint us, rint vs); inside iff 0 <= si <= Wd-1 and 0 <= sj <= Hd-1 (a NaN fails).  Nearest only: depth is never
+ *   interpolated across a discontinuity.   raw = raw_depth[sj][si];  z = (double)raw * depth_scale
+ *   valid iff inside, raw != 0, z >= z_min and (z_max <= 0 or z <= z_max);   depth_out = valid ? (float)(-z) : 0.0f
+ * B. Splat (colour given).  zbuf (n_views x Hc x Wc uint32) is filled with 0xffffffff by the call itself.  For every valid
+ *   pixel the three points (a, b) = (i, j), (i - 0.5, j - 0.5), (i + 0.5, j + 0.5), all at the pixel's z:
+ *     (x, y) = ideal(a, b);  P = (x*z, y*z, z);  Pc_r = ((T[r][0]*P_0 + T[r][1]*P_1) + T[r][2]*P_2) + T[r][3]   (T = T_dc, 3 x 4)
+ *     the pixel is skipped if any of the three Pc_2 is not > 0
+ *     (xc, yc) = (Pc_0/Pc_2, Pc_1/Pc_2);  (xcd, ycd) = distort(xc, yc; kc);  u = fc[0]*xcd + fc[2];  v = fc[1]*ycd + fc[3]
+ *   With (u1, v1), (u2, v2) of the two corners: skipped unless all four are finite;  a0 = rint(min(u1, u2)), a1 = rint(max(u1, u2)),
+ *   b0 = rint(min(v1, v2)), b1 = rint(max(v1, v2));  clipped: a0 = max(a0, 0), a1 = min(a1, Wc-1), b likewise with Hc;  cut:
+ *   a1 = min(a1, a0 + max_splat - 1), b1 = min(b1, b0 + max_splat - 1) (a bound on the work per pixel: a condition, not a
+ *   tuning knob);  skipped if a0 > a1 or b0 > b1.  key = the bit pattern of (float)Pc_2 of the centre (positive floats order as
+ *   unsigned integers);  zbuf[row][col] = min(zbuf[row][col], key) over rows b0..b1, columns a0..a1: a 32-bit integer atomic, so
+ *   the buffer does not depend on the order and is the same on every run.
+ * C. Gather (colour given), per valid pixel with the centre's (u, v, Pc_2) of B (a centre whose Pc_2 is not > 0 has no colour;
+ *   the corners play no part here):
+ *   inside iff 0 <= u < Wc-1 and 0 <= v < Hc-1 (a NaN fails: dfh_gn_photometric's visibility rule, so all four taps exist)
+ *   occluded iff (double)as_float(zbuf[rint v][rint u]) + occl_tol < (double)(float)Pc_2  (both sides through float32: a pixel
+ *   never occludes itself at occl_tol = 0; an untouched entry is a NaN and occludes nothing; occl_tol = +inf: no test)
+ *   sample == 1, bilinear: i0 = floor u, j0 = floor v, fu = u - i0, fv = v - j0, per channel with the taps as doubles
+ *     c = (1 - fv)*((1 - fu)*c[j0][i0] + fu*c[j0][i0+1]) + fv*((1 - fu)*c[j0+1][i0] + fu*c[j0+1][i0+1]);  byte = (int)rint(c)
+ *   sample == 0, nearest: the pixel [rint v][rint u]
+ *   color_out = R | G<<8 | B<<16 | 255<<24 where the pixel is valid, inside and not occluded, 0 elsewhere (K17 and K18 ignore X)
+ *   color_depth_out (may be NULL) = color_out != 0 ? depth_out : 0.0f
+ * At most three launches, all views in each; nothing is copied from or synchronised with the host.  The views' calibration
+ * travels as kernel arguments and is left, as a table, behind the z-buffer in the workspace for the launches that follow.
+ * zbuf: dfh_rgbd_ingest_workspace_bytes(n_views, Hc, Wc) bytes, 8-byte aligned (0: bad sizes); its first n_views*Hc*Wc dwords
+ * are the z-buffer after the call.  raw_color == NULL: only A runs; Hc, Wc, C, the colour side of the views, color_out,
+ * color_depth_out and zbuf are not read.
+ * DFH_E_BADARG before any HIP call: a null params, raw_depth, views or depth_out; n_views outside 1..16; a null raw_depth[v] or
+ * raw_color[v]; Hd or Wd < 2 or Hd*Wd >= 2^31; with colour the same of Hc, Wc, C not 3 or 4, a null color_out or zbuf, a zbuf not
+ * 8-byte aligned, a 4-channel image not 4-byte aligned; fx, fy, cx, cy not finite or fx, fy <= 0; any non-finite fd, kd, fc, kc,
+ * T_dc; fd[0], fd[1] <= 0; with colour fc[0], fc[1] <= 0; depth_scale not finite or <= 0; a NaN z_min or z_max; occl_tol negative
+ * or NaN; max_splat outside 1..16; sample not 0 or 1.
+ * dfh_rgbd_ingest_tile: the output tile (rows, columns) per workgroup, for tests that put image sizes on its edges. */
+typedef struct dfh_rgbd_view {
+    double fd[4], kd[5];          /* raw depth camera: fx fy cx cy; k1 k2 p1 p2 k3 */
+    double fc[4], kc[5];          /* colour camera */
+    double T_dc[12];              /* row-major 3 x 4, depth camera -> colour camera, in the units of z = raw * depth_scale */
+} dfh_rgbd_view;
+typedef struct dfh_rgbd_ingest_params {
+    int n_views;                  /* 1..16 */
+    const void *const *raw_depth; /* HOST array of n_views device pointers, Hd x Wd uint16 row-major */
+    const void *const *raw_color; /* HOST array of n_views device pointers, Hc x Wc x C uint8; NULL: no colour */
+    int Hd, Wd, Hc, Wc, C;        /* C: 3 | 4 */
+    double fx, fy, cx, cy;        /* the output pinhole every depth_out map is resampled to */
+    double depth_scale;           /* z = raw * depth_scale; finite, > 0 */
+    double z_min, z_max;          /* valid range of z; z_max <= 0: no upper bound */
+    double occl_tol;              /* >= 0, in the units of z */
+    int max_splat;                /* 1..16 */
+    int sample;                   /* 0 nearest | 1 bilinear */
+    const dfh_rgbd_view *views;   /* HOST array of n_views records */
+} dfh_rgbd_ingest_params;
+int dfh_rgbd_ingest(const dfh_rgbd_ingest_params *p, float *depth_out /* n_views x Hd x Wd */, void *color_out /* n_views x Hd x Wd dwords */,
+                    float *color_depth_out /* n_views x Hd x Wd, may be NULL */, void *zbuf, void *stream);
+size_t dfh_rgbd_ingest_workspace_bytes(int n_views, int Hc, int Wc);
+int dfh_rgbd_ingest_tile(int tile_hw[2]);
+
 #ifdef __cplusplus
 }
 #endif
