@@ -187,7 +187,15 @@ struct NoHook {
 // after_gathers(any_inside): called right after the depth gathers have been issued and before their values are used --
 // the place to issue further independent loads (the brick sweep starts its T / w loads there, one memory round trip
 // instead of two); any_inside = some voxel of the pack projects into the image.
-template <typename DepthT, int VEC, bool PINHOLE, bool STRIDED, bool LAZY = true, typename Hook = NoHook>
+// NEAR_BRANCH (pinhole only): the near-surface value -- the fp64 chain of a voxel with -tdist < sd <= tdist -- sits behind a REAL
+// branch.  Left to itself the compiler if-converts that chain: 11 vector instructions per voxel issued for every lane and
+// selected away, although only 0.65 % of the voxels of the 256^3 sweep are that near the surface and 19 in 20 of its waves hold
+// none.  The depth value is laundered through an empty asm, as exact_voxel_rare does with its coordinates, which keeps the chain
+// inside the branch.  Only the uncut gather-first walk asks for it: there it is 3-4 % of the launch; in the multi-view sweeps,
+// whose bricks survived the classification pass and lie round the surface, the same branch COSTS 3 %
+// (profiles/r20_k1_common_path.txt), and every other sweep keeps the compiler's form.  Same operations on the same operands
+// either way, hence the same bits.
+template <typename DepthT, int VEC, bool PINHOLE, bool STRIDED, bool LAZY = true, bool NEAR_BRANCH = false, typename Hook = NoHook>
 __device__ __forceinline__ bool view_pack(const IntegrateParams &p, const IntegrateParams *p_rare, const DepthT *__restrict__ depth, int x,
                                           int y, int z0, float (&ms)[VEC], bool (&upd)[VEC], Hook &&after_gathers = NoHook()) {
     constexpr int ZS = STRIDED ? 64 : 1;                 // z step between a lane's voxels
@@ -285,7 +293,9 @@ __device__ __forceinline__ bool view_pack(const IntegrateParams &p, const Integr
             ok = exact_voxel_rare<DepthT, PINHOLE, LAZY>(p_rare, depth, x, y, z0 + j * ZS, sd);
             m = (float)((sd < p.tdist ? sd : p.tdist) * p.inv_scale);
         } else if (ok & !freespace) {
-            double cz = -(double)dval[j];
+            DepthT dj = dval[j];
+            if (PINHOLE && NEAR_BRANCH) asm volatile("" : "+v"(dj));       // see NEAR_BRANCH above
+            double cz = -(double)dj;
             if (!PINHOLE) {
                 // u, v to ~1e-12 px from the folded map; only the value depends on them here
                 const double jf = (double)(j * ZS);
@@ -640,6 +650,7 @@ struct ColumnLane {
 // software-pipelined so that the wave never waits on it alone: brick i's T / w loads go out as soon as its decisions are made,
 // brick i+1 is projected and its gathers issued while they are in flight, and brick i is averaged and stored between the
 // issue of brick i+1's gathers and their use (view_pack's after_gathers hook).  Brick i+1's ms / upd are held across that wait.
+// This walk sweeps every brick of the grid, most of them far from the surface: its view_pack calls set NEAR_BRANCH.
 // The pinhole gather-first walk is held to 72 VGPRs, 7 waves per SIMD (left alone it takes 76: 6 waves, 3-4 % slower at 256^3;
 // a cap of 8 waves spills and is 30 % slower: profiles/r5_k1_experiments.txt).  The non-pinhole instances need ~110 VGPRs and
 // would spill under that cap: they keep the compiler's choice.
@@ -668,7 +679,7 @@ __global__ __launch_bounds__(256) DFH_K1_OCC void integrate_depth_column_kernel(
     if (GATHER_FIRST) {
         float ms[4];
         bool upd[4];
-        bool any = view_pack<DepthT, 4, PINHOLE, false>(p, p_rare, depth, p.x0 + c.xl, c.y, z0, ms, upd) && in_grid;
+        bool any = view_pack<DepthT, 4, PINHOLE, false, true, true>(p, p_rare, depth, p.x0 + c.xl, c.y, z0, ms, upd) && in_grid;
         // (t / w live inside one iteration and the last brick is finished after the loop: with t / w carried round the loop,
         // or the last brick finished inside it, the copies at its back edge waited for every outstanding access, stores included)
         while (alive) {
@@ -678,7 +689,7 @@ __global__ __launch_bounds__(256) DFH_K1_OCC void integrate_depth_column_kernel(
             alive &= alive - 1;
             float msn[4];
             bool updn[4];
-            const bool anyn = view_pack<DepthT, 4, PINHOLE, false>(p, p_rare, depth, p.x0 + c.xl, c.y, zn, msn, updn, [&](bool) {
+            const bool anyn = view_pack<DepthT, 4, PINHOLE, false, true, true>(p, p_rare, depth, p.x0 + c.xl, c.y, zn, msn, updn, [&](bool) {
                 if (any) {                               // brick i: average and store the updated packs
                     apply_pack<4>(tb, wb, ms, upd, p.wmax_f);
                     st_pack<NT>(tsdf + c.row + z0, tb);
