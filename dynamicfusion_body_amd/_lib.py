@@ -128,6 +128,16 @@ class RGBDIngestParams(ctypes.Structure):
                 ("occl_tol", _dbl), ("max_splat", _int), ("sample", _int), ("views", ctypes.POINTER(RGBDView))]
 
 
+class RaycastParams(ctypes.Structure):
+    """dfh_raycast_params: the volume (and colour volume), the views (lw, wl: host arrays the caller keeps alive), the march's
+    settings, the brick table and the device outputs of one dfh_raycast call."""
+    _fields_ = [("vol", ctypes.POINTER(Volume)), ("colors", ctypes.POINTER(ColorVolume)), ("n_views", _int), ("H", _int), ("W", _int),
+                ("K", _dbl * 9), ("Kinv", _dbl * 9), ("lw", _c_double_p), ("wl", _c_double_p),
+                ("scale", _dbl), ("center", _dbl * 3), ("half", _dbl), ("z_near", _dbl), ("z_far", _dbl), ("step", _dbl),
+                ("min_weight", _dbl), ("refine", _int), ("max_steps", _int), ("table", _vp), ("table_bytes", ctypes.c_size_t),
+                ("depth", _vp), ("normals", _vp), ("color", _vp), ("hit", _vp)]
+
+
 _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
@@ -140,7 +150,8 @@ STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_param
            "dfh_volume": Volume, "dfh_live": Live, "dfh_depth_views": DepthViews, "dfh_nodes": Nodes,
            "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams,
            "dfh_gn_normal_gate": NormalGate, "dfh_gn_landmarks": Landmarks, "dfh_color_volume": ColorVolume,
-           "dfh_gn_photometric": Photometric, "dfh_rgbd_view": RGBDView, "dfh_rgbd_ingest_params": RGBDIngestParams}
+           "dfh_gn_photometric": Photometric, "dfh_rgbd_view": RGBDView, "dfh_rgbd_ingest_params": RGBDIngestParams,
+           "dfh_raycast_params": RaycastParams}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -253,6 +264,9 @@ _SIGNATURES = {
     "dfh_rgbd_ingest": (_int, [ctypes.POINTER(RGBDIngestParams), _vp, _vp, _vp, _vp, _vp]),
     "dfh_rgbd_ingest_workspace_bytes": (ctypes.c_size_t, [_int, _int, _int]),
     "dfh_rgbd_ingest_tile": (_int, [_c_int_p]),
+    "dfh_raycast_table_bytes": (ctypes.c_size_t, [_slab_p]),
+    "dfh_raycast_table": (_int, [_volume_p, _vp, _vp]),
+    "dfh_raycast": (_int, [ctypes.POINTER(RaycastParams), _vp]),
 }
 
 _lib = None

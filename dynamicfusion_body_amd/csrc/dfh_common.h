@@ -68,7 +68,7 @@ constexpr int kGnTile = DFH_GN_TILE;
     X(k2_exact) X(k2_no_strided) X(k2_nt) X(k3_no_cache) X(k3_exact) X(k3_no_lds) X(k3_wg_per_cu) X(k3_tpb) X(k3_skip) X(plan_radix) X(rigid_atomic) X(gn_reg_own_launch) X(gn_reg_own_gather) \
     X(dbg_gather_part) X(pcg_wpb) X(pcg_multilaunch) X(pcg_spin_limit) X(pcg_one_xcd) X(gn_iter_own_clear) X(gn_gather_full) X(gn_no_view_cull)                                                            \
     X(py_plan_torch) X(py_allreduce_full) X(py_gn_atomic) X(py_gn_no_fused_assoc) X(py_gn_no_fused_iter) X(py_gn_iter_per_call) X(py_no_side_stream) X(py_no_host_scalars) \
-    X(k12_store) X(nd_path)
+    X(k12_store) X(nd_path) X(raycast_skip)
 struct Options {
 #define DFH_X(n) long n;
     DFH_OPTION_LIST(DFH_X)

@@ -511,6 +511,23 @@ class Fusion:
         half = self._T.shape[0] / 2.0
         return _mesh.render(verts, faces, normals, K, lws, H, W, scale=scale, center=center, half=half)
 
+    def render_canonical(self, lws, H, W, K=None, scale=1.0, center=np.zeros(3), **kw):
+        """The canonical volume ray-cast into the views `lws` (one 3x4 world->camera matrix or a list): a CANONICAL-space view, no
+        warp field is applied (the live-frame view of the warped model is render_live_frame).  Voxels are mapped to world by K1's
+        rule (scale, center, half = canonical resolution / 2).  K defaults to `_K`.  Returns kernels.raycast's result, with .color
+        when there is a colour volume; **kw goes to kernels.raycast."""
+        if K is None:
+            K = getattr(self, '_K', None)
+        if K is None:
+            raise ValueError('render_canonical needs the intrinsics: pass K or set _K')
+        K = np.asarray(K, dtype=np.float64)
+        self._ensure_volumes()
+        lws = [lws] if np.asarray(lws[0]).ndim == 1 else list(lws)
+        if self._C is not None:
+            kw.setdefault("colors", self._C)
+            kw.setdefault("want", ("depth", "normals", "color"))
+        return kernels.raycast(self._T, self._Wt, K, np.linalg.inv(K), lws, H, W, scale, center, tsdf_res=self._T.shape[0], **kw)
+
     def _write_back(self, sv):
         new_dq = sv.node_dq.cpu().numpy()
         for idx in range(len(self._nodes)):                                     # :400-403

@@ -252,6 +252,20 @@ class FusionDM:
         if self._verbose:
             print("Marching Cubes result: number of extracted vertices is %d" % (len(self._vertices)))
 
+    def render_model(self, lws, H, W, K=None, scale=1.0, center=np.zeros(3), **kw):
+        """KinectFusion's surface prediction (not in the reference): the canonical volume ray-cast into the views `lws` (one 3x4
+        world->camera matrix or a list), voxels mapped to world by K1's rule (scale, center, half = tsdf_res / 2) -- pass the
+        scale and center the volume was fused with.  K defaults to `_K`.  Returns kernels.raycast's result (.depth in the maps'
+        convention, .normals, and .color when there is a colour volume `_C`); **kw goes to kernels.raycast (step, min_weight,
+        refine, z_near, z_far, want, table, ...).  No mesh is built."""
+        K = self._K if K is None else np.asarray(K, dtype=np.float64)
+        self._ensure_volumes()
+        lws = [lws] if np.asarray(lws[0]).ndim == 1 else list(lws)
+        if self._C is not None:
+            kw.setdefault("colors", self._C)
+            kw.setdefault("want", ("depth", "normals", "color"))
+        return kernels.raycast(self._T, self._Wt, K, la.inv(K), lws, H, W, scale, center, tsdf_res=self._tsdf_res, **kw)
+
     def surface_samples(self, tsdf=None, band=1.0):
         """Dense alternative to the mesh vertices for the solve (not in the reference): every band
         voxel moved onto the zero level set along the TSDF gradient (csrc/dfh_extract.hip), with the

@@ -681,3 +681,129 @@ def rgbd_ingest(raw_depths, raw_colors, views, out_intrinsics, depth_scale=1e-3,
     if out is not None:
         torch.autograd.graph.increment_version(tuple(t for t in (depth, color, cdepth) if t is not None))
     return depth, color, cdepth, zbuf
+
+
+def raycast_table(T, res=None, x_range=None, out=None):
+    """K20: the brick table that lets raycast step over empty space (dfh_raycast_table): one uint8 per 8 x 8 x 8-cell brick of the
+    slab T holds, 1 = live (some voxel of the brick or of the one-voxel ring around it is not safely > 0), 0 = dead.  The table
+    describes T as it is NOW: rebuild it after T changes.  out: a uint8 CUDA tensor of at least the table's size to fill."""
+    if not (isinstance(T, torch.Tensor) and T.is_cuda and T.is_contiguous() and T.dim() == 3 and T.dtype in (torch.float32, torch.float64)):
+        raise ValueError("the volume must be a contiguous 3-D float32 or float64 CUDA tensor")
+    require_gpu()
+    lib = _lib.load()
+    vol, _ = _volume(T, T, res, x_range)
+    n = lib.dfh_raycast_table_bytes(vol.slab)
+    if out is None:
+        out = torch.empty((n,), dtype=torch.uint8, device=T.device)
+    elif not (isinstance(out, torch.Tensor) and out.device == T.device and out.dtype == torch.uint8 and out.is_contiguous() and
+              out.numel() >= n):
+        raise ValueError("out must be a contiguous uint8 CUDA tensor of at least %d elements" % n)
+    if n:
+        _lib.check(lib.dfh_raycast_table(vol, out.data_ptr(), current_stream_ptr()), "dfh_raycast_table")
+        torch.autograd.graph.increment_version((out,))
+    return out
+
+
+def raycast_inverse_views(lws):
+    """The camera -> world 3 x 4 matrices raycast passes beside `lws` (world -> camera 3 x 4 each): wl = [R^-1 | -R^-1 t], in
+    numpy float64.  The device inverts nothing; a caller that needs exact matrices passes its own through raycast(wls=)."""
+    out = []
+    for lw in lws:
+        m = np.asarray(lw, dtype=np.float64).reshape(3, 4)
+        ri = np.linalg.inv(m[:, :3])
+        out.append(np.concatenate([ri, -(ri @ m[:, 3:])], axis=1))
+    return out
+
+
+class RaycastResult:
+    """What raycast returns: .depth (V, H, W) float32 (negative depth, 0 = miss), .normals (V, H, W, 3) float32 (camera space,
+    facing the camera, zeros = none), .color (V, H, W, 4) uint8 (RGBX, X = 255 where valid), .hit (V, H, W, 3) float32 (index
+    space, NaN = miss); the ones not asked for are None."""
+    __slots__ = ("depth", "normals", "color", "hit")
+
+    def __init__(self, depth=None, normals=None, color=None, hit=None):
+        self.depth, self.normals, self.color, self.hit = depth, normals, color, hit
+
+
+# raycast_skip = -1, "the library decides": a call without a table builds one where the table build plus the skipping march
+# beat the plain march by more than the spread of either (profiles/r21_raycast.txt: measured at 256^3 with 3 x 640x480 rays and
+# at 512^3 with 8 x 1280x720).  Smaller volumes or fewer rays have not been measured: they march plainly.
+RAYCAST_SKIP_MIN_VOXELS = 256 ** 3
+RAYCAST_SKIP_MIN_RAYS = 640 * 480
+
+
+def raycast_builds_table(option, n_voxels, n_rays):
+    """Whether a raycast call that was given no table builds one: option raycast_skip 1 = always, 0 = never, -1 = by size."""
+    if option == 1:
+        return True
+    return option < 0 and n_voxels >= RAYCAST_SKIP_MIN_VOXELS and n_rays >= RAYCAST_SKIP_MIN_RAYS
+
+
+RAYCAST_OUTPUTS = {"depth": ((), torch.float32), "normals": ((3,), torch.float32), "color": ((4,), torch.uint8),
+                   "hit": ((3,), torch.float32)}
+
+
+def raycast(T, Wt, K, Kinv, lws, H, W, scale, center, tsdf_res=None, res=None, x_range=None, step=0.5, z_near=0.0, z_far=float("inf"),
+            min_weight=0.0, refine=1, max_steps=1 << 20, colors=None, table=None, want=("depth", "normals"), out=None, wls=None):
+    """K20 = the volume (T, Wt) seen from the cameras `lws` (world -> camera 3 x 4 each, any number: 16 per launch) through K:
+    a ray per pixel marched in steps of `step` voxels to the first + to - crossing of the trilinear TSDF, refined by `refine`
+    secant steps (dfh_raycast; semantics in include/dfusion_hip.h).  A sample counts only where all eight corners have
+    Wt >= min_weight (0: Wt is not read).  want: which of "depth", "normals", "color", "hit" to produce; "color" needs `colors`,
+    the slab's colour volume.  table: a raycast_table(T) to skip empty space with (same bits), the caller's to cache while T does
+    not change; None builds one here where that pays (raycast_builds_table: option raycast_skip 1 always, 0 never -- and a
+    given table is ignored --, unset by size) and marches plainly otherwise.  out: a RaycastResult whose tensors are written instead of fresh ones.
+    wls: the exact camera -> world matrices, if the caller has them (default raycast_inverse_views(lws)).  T, Wt, colors: only read."""
+    lws = list(lws)
+    V = len(lws)
+    if V == 0:
+        raise ValueError("raycast needs at least one view")
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(w not in RAYCAST_OUTPUTS for w in want):
+        raise ValueError("want must name some of %s, not %r" % (sorted(RAYCAST_OUTPUTS), want))
+    if "color" in want and colors is None:
+        raise ValueError("color wanted without a colour volume")
+    if wls is None:
+        wls = raycast_inverse_views(lws)
+    wls = list(wls)
+    if len(wls) != V:
+        raise ValueError("one inverse per view: %d for %d views" % (len(wls), V))
+    H, W = int(H), int(W)
+    require_gpu()
+    lib = _lib.load()
+    vol, tsdf_res = _volume(T, Wt, res, x_range, tsdf_res)
+    xr = (vol.slab.x0, vol.slab.x1)
+    cvol = _color_volume(colors, vol.slab.res, xr) if colors is not None else None
+    skip = _lib.get_option("raycast_skip")
+    n_vox = (xr[1] - xr[0]) * vol.slab.res[1] * vol.slab.res[2]
+    if table is None and n_vox and raycast_builds_table(skip, n_vox, V * H * W):
+        table = raycast_table(T, tuple(vol.slab.res), xr)
+    if table is not None and not (isinstance(table, torch.Tensor) and table.device == T.device and table.dtype == torch.uint8 and
+                                  table.is_contiguous()):
+        raise ValueError("table must be a contiguous uint8 CUDA tensor (raycast_table)")
+    result = RaycastResult() if out is None else out
+    for name in want:
+        tail, dt = RAYCAST_OUTPUTS[name]
+        t = getattr(result, name)
+        if t is None:
+            setattr(result, name, torch.empty((V, H, W) + tail, dtype=dt, device=T.device))
+        elif not (isinstance(t, torch.Tensor) and t.device == T.device and t.dtype == dt and t.is_contiguous() and
+                  tuple(t.shape) == (V, H, W) + tail):
+            raise ValueError("out.%s must be a contiguous %s CUDA tensor of shape %s" % (name, dt, (V, H, W) + tail))
+    cen = _lib.darr(np.asarray(center, dtype=np.float64), 3)
+    for i in range(0, V, 16):
+        n = min(16, V - i)
+        lw = _lib.darr(np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in lws[i:i + n]]), 12 * n)
+        wl = _lib.darr(np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in wls[i:i + n]]), 12 * n)
+        ptr = {}
+        for name in RAYCAST_OUTPUTS:
+            t = getattr(result, name) if name in want else None
+            ptr[name] = None if t is None else t.data_ptr() + i * t.stride(0) * t.element_size()
+        prm = _lib.RaycastParams(ctypes.pointer(vol), None if cvol is None else ctypes.pointer(cvol), n, H, W, _lib.darr(K, 9),
+                                 _lib.darr(Kinv, 9), lw, wl, float(scale), cen, float(tsdf_res) / 2.0, float(z_near), float(z_far),
+                                 float(step), float(min_weight), int(refine), int(max_steps),
+                                 None if table is None else table.data_ptr(), 0 if table is None else table.numel(),
+                                 ptr["depth"], ptr["normals"], ptr["color"], ptr["hit"])
+        _lib.check(lib.dfh_raycast(prm, current_stream_ptr()), "dfh_raycast")
+    if out is not None:
+        torch.autograd.graph.increment_version(tuple(getattr(result, name) for name in want))
+    return result

@@ -554,6 +554,46 @@ class SlabFrame:
                                          node_w=sv.node_w)
         return _mesh.render(verts, faces, normals, self.K, lws, H, W, scale=self.scale, center=self.center, half=self.R / 2)
 
+    _live_views = None       # (lws, H, W) of the last live sweep of step(): raycast_live's default views
+
+    def raycast_live(self, lws=None, H=None, W=None, **kw):
+        """The LIVE volume the last step() swept from its depth maps, ray-cast (kernels.raycast) into the views `lws` -- default:
+        that frame's own cameras and map size, so that `.depth` lines up with the frame's depth maps pixel for pixel and goes
+        straight into mesh.depth_error(rendered, observed, gate).  No mesh is built; no warp field is involved (the live volume
+        is in the live frame already).  Several ranks: every rank casts the all-gathered live volume (one collective per
+        call, two with min_weight > 0) and gets the same maps.  **kw goes to kernels.raycast.  Needs a step() that swept the live
+        volume (update="volume" or data_term="volume")."""
+        if self._live_views is None:
+            raise ValueError("no live volume yet: raycast_live needs a step() with update='volume' or data_term='volume'")
+        l0, H0, W0 = self._live_views
+        lws = l0 if lws is None else ([lws] if np.asarray(lws[0]).ndim == 1 else list(lws))
+        H, W = (H0 if H is None else int(H)), (W0 if W is None else int(W))
+        R = self.R
+        live, live_w = self.live, self.live_w
+        if self.ws > 1:
+            live = self.D.allgather_planes(self.live, R)
+            live_w = self.D.allgather_planes(self.live_w, R) if kw.get("min_weight", 0.0) > 0.0 else live
+        x_range = (self.a, self.b) if self.ws == 1 else None
+        return kernels.raycast(live, live_w, self.K, self.Kinv, lws, H, W, self.scale, self.center, tsdf_res=R, res=(R, R, R),
+                               x_range=x_range, **kw)
+
+    def raycast_canonical(self, K, lws, H, W, colors=True, **kw):
+        """A CANONICAL-space snapshot: the canonical volume T ray-cast as it is stored, with NO warp field applied -- this is not
+        a view of the live frame (that is render_live: the canonical mesh warped into the frame, K11).  Where the field is
+        near the identity the two look alike; where it is not, this shows the reference pose.  K: the intrinsics to cast
+        through (None: the frame's).  colors=True adds `.color` when the frame has a colour volume.  Single rank only: the ranks'
+        slab casts would need a merge of their depth maps, which is not implemented (ValueError).  **kw goes to kernels.raycast."""
+        if self.ws > 1:
+            raise ValueError("raycast_canonical casts one rank's whole grid; the %d-rank slab partition is not supported" % self.ws)
+        K = self.K if K is None else np.asarray(K, dtype=np.float64)
+        lws = [lws] if np.asarray(lws[0]).ndim == 1 else list(lws)
+        if colors and self.C is not None:
+            kw.setdefault("colors", self.C)
+            kw.setdefault("want", ("depth", "normals", "color"))
+        R = self.R
+        return kernels.raycast(self.T, self.Wt, K, np.linalg.inv(K), lws, H, W, self.scale, self.center, tsdf_res=R, res=(R, R, R),
+                               x_range=(self.a, self.b), **kw)
+
     def colored_mesh(self):
         """The canonical mesh with vertex colours: marching cubes of T at level 0 and the colour volume sampled at its vertices
         (kernels.sample_colors) -> (verts, faces, normals, rgb (n, 3) float32 in [0, 255], valid (n,) bool).  Single rank only, as
@@ -714,6 +754,7 @@ class SlabFrame:
             kernels.integrate_depth_views(self.live, self.live_w, depth_list, self.K, self.Kinv, lw_list, self.scale, self.center,
                                           self.tdist_world, tsdf_res=R, res=(R, R, R), x_range=(self.a, self.b), workspace=self.ws_views,
                                           fresh=self.tvox)          # (the fill of the live volume is part of the sweep)
+            self._live_views = (lw_list, int(depth.shape[0]), int(depth.shape[1]))
         # The solve reads the depth maps (projective association), not the live volume; the live volume depends on the depth maps
         # only and is first read by the TSDF update.  So the live-volume sweep (bandwidth-bound) runs on a side stream beside the
         # plan's launches AND the whole solve (bound by latency, ten waves per CU), and the streams join in front of the TSDF

@@ -1154,6 +1154,91 @@ int dfh_rgbd_ingest(const dfh_rgbd_ingest_params *p, float *depth_out /* n_views
 size_t dfh_rgbd_ingest_workspace_bytes(int n_views, int Hc, int Wc);
 int dfh_rgbd_ingest_tile(int tile_hw[2]);
 
+/* ---- K20  ray cast: depth, normal, colour and hit maps of a TSDF volume seen from up to 16 cameras ---------------------------
+ * KinectFusion's surface prediction (no reference counterpart: the reference shows its model only as a mesh).  The volume is only
+ * read.  All arithmetic is fp64 with ONE rounding per operation (no contraction, IEEE division and square root), in the order
+ * written here; float32 T / w / rgbw values are widened at load and every output is rounded once, at its store, so that
+ * tests/raycast_np.py agrees bit for bit.  a ? b : c below is a select: a comparison with a NaN is false.
+ *
+ * Grid: lo = (x0, 0, 0), hi = (x1 - 1, res_1 - 1, res_2 - 1): the region where a full trilinear cell of the slab exists.  A slab
+ * with hi_a < lo_a + 1 on some axis has no cell: every pixel is a miss.
+ * S(p), the value at an index-space point p (three doubles), K6v's standard trilinear cell (dfh_gn_associate_volume's axis order):
+ *   c_a = floor(p_a);  c_a = c_a >= lo_a ? c_a : lo_a;  c_a = c_a <= hi_a - 1 ? c_a : hi_a - 1;  f_a = p_a - c_a
+ *     (the clamp only matters for a p that rounding has put a few ulps outside [lo, hi], which then extrapolates by as much; it
+ *     also means that no p whatever, a NaN included, reads outside the slab)
+ *   u_ijk = (double)T[c + (i, j, k)];   d_jk.. : dz00 = u001 - u000, dz01 = u011 - u010, dz10 = u101 - u100, dz11 = u111 - u110
+ *   e00 = u000 + f_2*dz00, e01 = u010 + f_2*dz01, e10 = u100 + f_2*dz10, e11 = u110 + f_2*dz11
+ *   h0 = e00 + f_1*(e01 - e00), h1 = e10 + f_1*(e11 - e10);   t = h0 + f_0*(h1 - h0)
+ *   known iff min_weight == 0 (w is not read at all) or every one of the eight corners has (double)w >= min_weight.
+ * Per view v and pixel (y, x), X = (double)x, Y = (double)y:
+ *  1. ray.  rho_r = (Kinv[r][0]*X + Kinv[r][1]*Y) + Kinv[r][2];  d_r = (wl[r][0]*rho_0 + wl[r][1]*rho_1) + wl[r][2]*rho_2  (wl: the
+ *     view's camera -> world 3 x 4, the inverse of lw);  o_a = (wl[a][3] - center_a)/scale + half;  e_a = d_a/scale.  The ray is
+ *     parameterised by the depth value z (the third component of K*lpos, what a depth map stores negated): the camera point is
+ *     z*rho and the index point i(z)_a = o_a + z*e_a.  L = sqrt((e_0*e_0 + e_1*e_1) + e_2*e_2); a miss unless 0 < L < inf.
+ *  2. clip.  zlo = z_near, zhi = z_far; for a = 0, 1, 2: e_a == 0: a miss unless lo_a <= o_a <= hi_a (no division); otherwise
+ *     t1 = (lo_a - o_a)/e_a, t2 = (hi_a - o_a)/e_a, tn = t1 < t2 ? t1 : t2, tf = t1 < t2 ? t2 : t1, zlo = tn > zlo ? tn : zlo,
+ *     zhi = tf < zhi ? tf : zhi.  A miss unless zlo <= zhi.
+ *  3. samples.  dz = step/L;  n = floor((zhi - zlo)/dz);  kmax = n < max_steps ? (int)n : max_steps;  sample k = 0..kmax sits at
+ *     z_k = zlo + (double)k*dz (a product, never a running sum) and has (known_k, t_k) = S(i(z_k)).
+ *  4. walk, k ascending, with a previous sample that starts absent: a sample with known_k, t_k <= 0 and a previous sample is the
+ *     crossing: (za, ta) = the previous sample, (zb, tb) = (z_k, t_k), and the walk ends.  Otherwise the previous sample becomes
+ *     (z_k, t_k) if known_k and t_k > 0, and absent if not (an unknown sample, a NaN, or a value <= 0 with nothing in front of it:
+ *     a ray that starts behind the surface reports nothing until it has seen free space; a - to + transition is never a hit).
+ *     No crossing up to kmax: a miss.
+ *  5. root.  z* = za + (zb - za)*(ta/(ta - tb));  then `refine` times: (known, t) = S(i(z*)); unknown: stop; t > 0: (za, ta) =
+ *     (z*, t), otherwise (zb, tb) = (z*, t); z* recomputed by the same expression.
+ *  6. outputs, each (n_views, H, W, ...) and optional (not all NULL), with p = i(z*):
+ *     depth  float32: (float)(-z*); 0 on a miss (the maps' convention: it feeds every consumer of a depth map)
+ *     hit    float32 x 3: (float)p_a; on a miss the quiet NaN 0x7fc00000 three times
+ *     normals float32 x 3, K12's nh convention: for a = 0, 1, 2: g_a = S(p + unit_a) - S(p - unit_a); each of the six points q
+ *       must have lo_b <= q_b <= hi_b on all axes and be known, otherwise the normal is missing.  To camera space:
+ *       m_c = sg*((wl[0][c]*g_0 + wl[1][c]*g_1) + wl[2][c]*g_2), sg = scale > 0 ? 1 : -1;  l2 = (m_0*m_0 + m_1*m_1) + m_2*m_2;
+ *       missing unless 0 < l2 < inf;  nh = m / sqrt(l2) (three divisions);  c = (nh_0*(z* rho_0) + nh_1*(z* rho_1)) + nh_2*(z* rho_2);
+ *       c > 0: nh = -nh (the normal faces the camera).  Zeros on a miss or where the normal is missing.
+ *     color  uint8 x 4: dfh_sample_colors' rule at p (its own in-grid test, cell, corner order and sums; corners outside the slab
+ *       or with wc <= 0 do not count), per channel q = (sum tw*c_a)/S in fp64, byte = q > 0 ? (q >= 255 ? 255 : rint(q)) : 0
+ *       (half to even), X = 255; S == 0, outside, or a miss: 0, 0, 0, 0.
+ * One march launch serves all views; nothing is copied from or synchronised with the host.  K and lw are not read by the device
+ * (the ray needs Kinv and wl only); they travel with the call so that a caller describes a camera as it does everywhere else.
+ *
+ * Empty-space skipping.  dfh_raycast_table fills one byte per 8 x 8 x 8-cell brick of the slab (brick (b0, b1, b2) = cells
+ * [x0 + 8 b0, x0 + 8 b0 + 8) x [8 b1, ..) x [8 b2, ..); ceil((x1 - x0)/8) * ceil(res_1/8) * ceil(res_2/8) bytes, b2 fastest):
+ * 0 = dead, 1 = live.  A brick is dead iff every voxel its cells' corners touch, AND the one-voxel ring around them (voxels
+ * 8 b_a - 1 .. 8 b_a + 9 per axis, cut at the slab), holds a T with m > 0 and m > M * 2^-30, m and M the least and greatest of those
+ * values (a NaN makes the brick live).  With a table the march skips dead bricks without sampling and gives the SAME BITS as
+ * without (proof: csrc/dfh_raycast.hip); a table built for another volume state gives wrong images, it is the caller's to keep
+ * current.  table == NULL, or the option raycast_skip = 0: the plain march.
+ * DFH_E_BADARG before any HIP call: null params or volume; a bad slab; n_views outside 1..16; a null lw or wl; H or W < 1 or
+ * H*W >= 2^31; step not finite or <= 0; z_near not finite or < 0; z_far not > z_near (+inf allowed); min_weight negative or NaN;
+ * refine outside 0..8; max_steps < 1; scale 0 or not finite; all outputs NULL; color wanted without a colour volume, or with one
+ * whose slab is not the volume's; a table of fewer than dfh_raycast_table_bytes bytes.  A slab without a cell: DFH_OK, the
+ * outputs are filled with misses, no march is launched.  dfh_raycast_table: a null volume, T or table; a bad slab; an empty
+ * slab: DFH_OK, nothing written.  dfh_raycast_table_bytes: 0 for a bad or empty slab. */
+typedef struct dfh_raycast_params {
+    const dfh_volume *vol;
+    const dfh_color_volume *colors;   /* NULL: no colour volume */
+    int n_views;                      /* 1..16 */
+    int H, W;
+    double K[9], Kinv[9];             /* 3x3 row-major */
+    const double *lw;                 /* HOST, n_views x 12: world -> camera, as in dfh_depth_views */
+    const double *wl;                 /* HOST, n_views x 12: their inverses (camera -> world) */
+    double scale, center[3], half;    /* pos = scale*(i - half) + center */
+    double z_near, z_far;             /* in the depth maps' units; z_far may be +inf */
+    double step;                      /* index-space length between samples, in voxels */
+    double min_weight;                /* 0: w is not read */
+    int refine;                       /* 0..8 */
+    int max_steps;                    /* >= 1; values above 2^30 act as 2^30 */
+    const void *table;                /* DEVICE, dfh_raycast_table's; NULL: plain march */
+    size_t table_bytes;
+    float *depth;                     /* DEVICE outputs, any may be NULL, not all */
+    float *normals;
+    unsigned char *color;
+    float *hit;
+} dfh_raycast_params;
+size_t dfh_raycast_table_bytes(const dfh_slab *slab);
+int dfh_raycast_table(const dfh_volume *vol, void *table, void *stream);
+int dfh_raycast(const dfh_raycast_params *p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
