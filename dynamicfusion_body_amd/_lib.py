@@ -138,6 +138,15 @@ class RaycastParams(ctypes.Structure):
                 ("depth", _vp), ("normals", _vp), ("color", _vp), ("hit", _vp)]
 
 
+class IcpTrackParams(ctypes.Structure):
+    """dfh_icp_track_params: the live and model maps of one pyramid level (device float32), the level's camera, the poses T
+    (device, in and out), the gates, the solve's guards and the device outputs of one dfh_icp_track call."""
+    _fields_ = [("n_views", _int), ("H", _int), ("W", _int), ("live_depth", _vp), ("live_normals", _vp), ("model_depth", _vp),
+                ("model_normals", _vp), ("K", _dbl * 9), ("Kinv", _dbl * 9), ("T", _vp), ("max_dist", _dbl), ("min_cos", _dbl),
+                ("huber", _dbl), ("lm_rel", _dbl), ("n_iters", _int), ("min_count", _int), ("max_rot", _dbl), ("max_trans", _dbl),
+                ("stats", _vp), ("rows", _vp), ("scratch", _vp), ("scratch_bytes", ctypes.c_size_t)]
+
+
 _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
@@ -151,7 +160,7 @@ STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_param
            "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams,
            "dfh_gn_normal_gate": NormalGate, "dfh_gn_landmarks": Landmarks, "dfh_color_volume": ColorVolume,
            "dfh_gn_photometric": Photometric, "dfh_rgbd_view": RGBDView, "dfh_rgbd_ingest_params": RGBDIngestParams,
-           "dfh_raycast_params": RaycastParams}
+           "dfh_raycast_params": RaycastParams, "dfh_icp_track_params": IcpTrackParams}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -267,6 +276,9 @@ _SIGNATURES = {
     "dfh_raycast_table_bytes": (ctypes.c_size_t, [_slab_p]),
     "dfh_raycast_table": (_int, [_volume_p, _vp, _vp]),
     "dfh_raycast": (_int, [ctypes.POINTER(RaycastParams), _vp]),
+    "dfh_depth_halve": (_int, [ctypes.POINTER(_vp), _int, _int, _int, _int, _dbl, _vp, _vp]),
+    "dfh_icp_track_bytes": (ctypes.c_size_t, [_int]),
+    "dfh_icp_track": (_int, [ctypes.POINTER(IcpTrackParams), _vp]),
 }
 
 _lib = None

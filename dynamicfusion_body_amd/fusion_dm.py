@@ -266,6 +266,16 @@ class FusionDM:
             kw.setdefault("want", ("depth", "normals", "color"))
         return kernels.raycast(self._T, self._Wt, K, la.inv(K), lws, H, W, scale, center, tsdf_res=self._tsdf_res, **kw)
 
+    def track_frame(self, depths, lws_prev, tracker, scale=1.0, center=np.zeros(3), **kw):
+        """KinectFusion's pose estimation (not in the reference): the cameras of the depth maps `depths`, found by the
+        tracking.CameraTracker `tracker` from the priors `lws_prev` (one 3x4 world->camera matrix per map) against the canonical
+        volume, ray-cast by render_model into the prior cameras at every pyramid level's K (scale, center: the ones the volume
+        was fused with; **kw goes to the ray cast).  Returns CameraTracker.track's (lws, stats); nothing of the object changes."""
+        def model(lws, K, H, W):
+            r = self.render_model(lws, H, W, K=K, scale=scale, center=center, want=("depth", "normals"), **kw)
+            return r.depth, r.normals
+        return tracker.track(depths, lws_prev, model)
+
     def surface_samples(self, tsdf=None, band=1.0):
         """Dense alternative to the mesh vertices for the solve (not in the reference): every band
         voxel moved onto the zero level set along the TSDF gradient (csrc/dfh_extract.hip), with the

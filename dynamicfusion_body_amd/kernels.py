@@ -807,3 +807,92 @@ def raycast(T, Wt, K, Kinv, lws, H, W, scale, center, tsdf_res=None, res=None, x
     if out is not None:
         torch.autograd.graph.increment_version(tuple(getattr(result, name) for name in want))
     return result
+
+
+def depth_halve(depths, max_jump, out=None):
+    """K21 = one step of the depth pyramid for all maps of a frame in one launch (dfh_depth_halve; semantics in
+    include/dfusion_hip.h): every output pixel is the mean of the valid taps of its 2 x 2 block that lie within max_jump of the
+    block's first pixel, 0 where that pixel holds no measurement.  depths: a (V, H, W) CUDA tensor or a list of at most 16
+    (H, W) CUDA tensors of one shape and dtype (float32 / float64), only read.  Returns (V, H // 2, W // 2) float32."""
+    depths = list(depths)
+    if not depths:
+        raise ValueError("depth_halve needs at least one depth map")
+    if len(depths) > 16:
+        raise ValueError("at most 16 depth maps per call, got %d" % len(depths))
+    for d in depths:
+        if not (isinstance(d, torch.Tensor) and d.dim() == 2):
+            raise ValueError("depth must be a contiguous 2-D CUDA tensor")
+        if d.shape != depths[0].shape or d.dtype != depths[0].dtype:
+            raise ValueError("all depth maps of one call must have the same shape and dtype")
+    require_gpu()
+    lib = _lib.load()
+    for d in depths:
+        _check_depth(d)
+    V = len(depths)
+    H, W = (int(n) for n in depths[0].shape)
+    dev = depths[0].device
+    shape = (V, H // 2, W // 2)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif not (isinstance(out, torch.Tensor) and out.device == dev and out.dtype == torch.float32 and out.is_contiguous() and
+              tuple(out.shape) == shape):
+        raise ValueError("out must be a contiguous float32 CUDA tensor of shape %s" % (shape,))
+    ptrs = (ctypes.c_void_p * V)(*[d.data_ptr() for d in depths])
+    _lib.check(lib.dfh_depth_halve(ptrs, V, dtype_code(depths[0]), H, W, float(max_jump), out.data_ptr(), current_stream_ptr()),
+               "dfh_depth_halve")
+    torch.autograd.graph.increment_version((out,))
+    return out
+
+
+def icp_track_scratch(n_views, device=None):
+    """The workspace of icp_track for n_views views (dfh_icp_track_bytes; no initial state, reusable across calls)."""
+    require_gpu()
+    n = int(_lib.load().dfh_icp_track_bytes(int(n_views)))
+    if n == 0:
+        raise ValueError("icp_track takes 1..16 views per call, got %d" % n_views)
+    if device is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    return torch.empty(n // 8, dtype=torch.float64, device=device)
+
+
+def icp_track(live_depth, live_normals, model_depth, model_normals, K, Kinv, T, n_iters, max_dist=0.0, min_cos=0.0, huber=0.0,
+              lm_rel=0.0, min_count=6, max_rot=float("inf"), max_trans=float("inf"), want_rows=False, scratch=None):
+    """K21 = n_iters iterations of dense projective point-to-plane ICP for all views of one pyramid level (dfh_icp_track; semantics
+    in include/dfusion_hip.h), queued back to back: nothing is read back.  live_depth, model_depth: (V, H, W) float32 CUDA;
+    model_normals, live_normals: (V, H, W, 3) float32 CUDA (live_normals None: no normal gate).  T: (V, 3, 4) float64 CUDA, live
+    camera -> model camera, updated IN PLACE.  Returns (stats (V, n_iters, 40) float64: 29 sums | status | xi | 0, rows
+    (V, H, W, 8) float64 of the first iteration or None)."""
+    require_gpu()
+    lib = _lib.load()
+    if not (isinstance(live_depth, torch.Tensor) and live_depth.dim() == 3 and live_depth.is_cuda):
+        raise ValueError("live_depth must be a (V, H, W) CUDA tensor")
+    V, H, W = (int(n) for n in live_depth.shape)
+    dev = live_depth.device
+    for name, t, shape in (("live_depth", live_depth, (V, H, W)), ("model_depth", model_depth, (V, H, W)),
+                           ("model_normals", model_normals, (V, H, W, 3)), ("live_normals", live_normals, (V, H, W, 3))):
+        if t is None and name == "live_normals":
+            continue
+        if not (isinstance(t, torch.Tensor) and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and
+                tuple(t.shape) == shape):
+            raise ValueError("%s must be a contiguous float32 CUDA tensor of shape %s" % (name, shape))
+    if not (isinstance(T, torch.Tensor) and T.device == dev and T.dtype == torch.float64 and T.is_contiguous() and
+            tuple(T.shape) == (V, 3, 4)):
+        raise ValueError("T must be a contiguous float64 CUDA tensor of shape %s" % ((V, 3, 4),))
+    n_iters = int(n_iters)
+    if not 0 <= n_iters <= 64:
+        raise ValueError("n_iters must be 0..64, got %d" % n_iters)
+    if scratch is None:
+        scratch = icp_track_scratch(V, dev)
+    if not (isinstance(scratch, torch.Tensor) and scratch.device == dev and scratch.is_contiguous()):
+        raise ValueError("scratch must be a contiguous CUDA tensor (icp_track_scratch)")
+    stats = torch.empty((V, n_iters, 40), dtype=torch.float64, device=dev)
+    rows = torch.empty((V, H, W, 8), dtype=torch.float64, device=dev) if want_rows and n_iters > 0 else None
+    prm = _lib.IcpTrackParams(V, H, W, live_depth.data_ptr(), None if live_normals is None else live_normals.data_ptr(),
+                              model_depth.data_ptr(), model_normals.data_ptr(), _lib.darr(K, 9), _lib.darr(Kinv, 9), T.data_ptr(),
+                              float(max_dist), float(min_cos), float(huber), float(lm_rel), n_iters, int(min_count), float(max_rot),
+                              float(max_trans), stats.data_ptr() if n_iters else None, None if rows is None else rows.data_ptr(),
+                              scratch.data_ptr(), scratch.numel() * scratch.element_size())
+    _lib.check(lib.dfh_icp_track(prm, current_stream_ptr()), "dfh_icp_track")
+    if n_iters:
+        torch.autograd.graph.increment_version((T,))
+    return stats, rows

@@ -204,8 +204,16 @@ class SlabFrame:
 
     def __init__(self, K, scale, center, res, tdist_vox, node_pos, node_w, knn=4, pcg_iters=10, band=4.0, volume_dtype=torch.float32,
                  distributed=True, solve_mode="auto", depth_prep=None, normal_gate=None, color_band=None, photo_weight=0.0,
-                 photo_huber=0.0, photo_max_diff=0.0, photo_band_sd=None, ingest=None):
-        """ingest: an ingest.RGBDIngest, or None.  step() and integrate() then take the sensor's RAW frames -- uint16 depth maps,
+                 photo_huber=0.0, photo_max_diff=0.0, photo_band_sd=None, ingest=None, tracker=None, track_model="live"):
+        """tracker: a tracking.CameraTracker, or None.  step(track=True) then treats the given lw_cam as a PRIOR: the frame's depth
+        maps (after ingest and depth_prep) are aligned to the model as the prior cameras see it, and the tracked cameras replace
+        lw_cam before anything else reads it; they are kept in `self.tracked_lw`, the tracker's report in `self.track_stats` (a
+        lost view keeps its prior).  track_model: what the model is.  "live" = raycast_live: the previous frame's live volume --
+        it needs a previous step() that swept one, and works on several ranks: every rank casts the same gathered volume and the
+        tracker's sums are order-fixed, so every rank computes identical poses and no collective is added.  "mesh" = render_live:
+        the canonical model warped by the current field, single rank only; its rendered normals are not turned to face the
+        camera, so this model tracks without the normal-compatibility gate.  Views are tracked independently.
+        ingest: an ingest.RGBDIngest, or None.  step() and integrate() then take the sensor's RAW frames -- uint16 depth maps,
         one per calibrated view, and (step) the colour camera's raw images -- and run them through the stage first, in front of
         depth_prep: its depth maps go to everything that read depth before, its registered colours with the depth maps that keep
         only coloured pixels (`self.color_depth`) to the colour fusion.  The photometric term keeps the frame's depth maps and the
@@ -274,6 +282,10 @@ class SlabFrame:
                               distributed=self.distributed and self.ws > 1 and solve_mode == "sharded")
         if (node_pos is None) != (node_w is None):
             raise ValueError("node_pos and node_w come together (both None: construct_graph() builds the graph)")
+        if track_model not in ("live", "mesh"):
+            raise ValueError("track_model must be 'live' or 'mesh', got %r" % (track_model,))
+        self.tracker, self.track_model = tracker, track_model
+        self.tracked_lw = self.track_stats = None
         self.ingest = ingest
         if ingest is not None and not np.array_equal(self.K, np.asarray(ingest.K, dtype=np.float64)):
             raise ValueError("K must equal ingest.K: the stage resamples every depth map to that pinhole")
@@ -537,8 +549,8 @@ class SlabFrame:
         self.refresh_samples()
         return n_new
 
-    def render_live(self, lws, H, W):
-        """Depth / normal / face-id maps of the loop's current live model in the views `lws` (one 3x4 world->camera matrix or a
+    def render_live(self, lws, H, W, K=None):
+        """K: the intrinsics to render through (None: the frame's).  Depth / normal / face-id maps of the loop's current live model in the views `lws` (one 3x4 world->camera matrix or a
         list; one launch): marching cubes of the canonical volume T at level 0, warped by the solver's node field (node_pos /
         node_dq / node_w, each vertex's knn nearest nodes) and the loop's identity `lw`, rendered with this frame's K / scale /
         center / half (mesh.render).  Single rank only: with the volume cut into slabs the meshes would need halo planes and the
@@ -552,12 +564,13 @@ class SlabFrame:
             nbr, _ = sample_knn(verts, sv.node_pos, sv.node_w, self.knn)
             verts, normals = warp_points(verts, normals, self.ident_lw, nbr=nbr, node_dq=sv.node_dq, node_pos=sv.node_pos,
                                          node_w=sv.node_w)
-        return _mesh.render(verts, faces, normals, self.K, lws, H, W, scale=self.scale, center=self.center, half=self.R / 2)
+        return _mesh.render(verts, faces, normals, self.K if K is None else np.asarray(K, dtype=np.float64), lws, H, W, scale=self.scale,
+                            center=self.center, half=self.R / 2)
 
     _live_views = None       # (lws, H, W) of the last live sweep of step(): raycast_live's default views
 
-    def raycast_live(self, lws=None, H=None, W=None, **kw):
-        """The LIVE volume the last step() swept from its depth maps, ray-cast (kernels.raycast) into the views `lws` -- default:
+    def raycast_live(self, lws=None, H=None, W=None, K=None, **kw):
+        """K: the intrinsics to cast through (None: the frame's).  The LIVE volume the last step() swept from its depth maps, ray-cast (kernels.raycast) into the views `lws` -- default:
         that frame's own cameras and map size, so that `.depth` lines up with the frame's depth maps pixel for pixel and goes
         straight into mesh.depth_error(rendered, observed, gate).  No mesh is built; no warp field is involved (the live volume
         is in the live frame already).  Several ranks: every rank casts the all-gathered live volume (one collective per
@@ -574,7 +587,8 @@ class SlabFrame:
             live = self.D.allgather_planes(self.live, R)
             live_w = self.D.allgather_planes(self.live_w, R) if kw.get("min_weight", 0.0) > 0.0 else live
         x_range = (self.a, self.b) if self.ws == 1 else None
-        return kernels.raycast(live, live_w, self.K, self.Kinv, lws, H, W, self.scale, self.center, tsdf_res=R, res=(R, R, R),
+        K, Kinv = (self.K, self.Kinv) if K is None else (np.asarray(K, dtype=np.float64), np.linalg.inv(np.asarray(K, dtype=np.float64)))
+        return kernels.raycast(live, live_w, K, Kinv, lws, H, W, self.scale, self.center, tsdf_res=R, res=(R, R, R),
                                x_range=x_range, **kw)
 
     def raycast_canonical(self, K, lws, H, W, colors=True, **kw):
@@ -606,6 +620,24 @@ class SlabFrame:
         verts, faces, normals, _ = _mesh.marching_cubes(self.T, 0.0, 1)
         rgb, valid = kernels.sample_colors(self.C, verts.double())
         return verts, faces, normals, rgb, valid
+
+    def _track(self, depth_list, lw_list):
+        """step(track=True): the tracked cameras of this frame's maps, from the priors lw_list."""
+        if self.tracker is None:
+            raise ValueError("step(track=True) needs the constructor's tracker")
+        if self.track_model == "live":
+            def model(lws, K, H, W):
+                r = self.raycast_live(lws, H, W, K=K, want=("depth", "normals"))
+                return r.depth, r.normals
+            gate = None
+        else:
+            def model(lws, K, H, W):
+                depth, normals, _ = self.render_live(lws, H, W, K=K)
+                return depth, normals
+            gate = False
+        lws, self.track_stats = self.tracker.track(depth_list, lw_list, model, gate_normals=gate)
+        self.tracked_lw = lws
+        return lws
 
     def visible_samples(self, lws, H, W, stride=1, max_samples=None):
         """The visible-surface samples of the loop's current live model in the views `lws`: render_live's mesh, warp and
@@ -656,8 +688,10 @@ class SlabFrame:
     def step(self, depth, lw_cam, gn_iters=10, rw=5.0, lm_abs=10.0, lm_rel=1e-2, max_dist=2.0, huber=0.5, stage_ms=None,
              update_graph=False, on_updated=None, data_views=None, relax=None, global_iters=None, global_lm=0.1, global_stride=None,
              data_term="depth", global_built=None, update="volume", update_weight="node_distance", graph_sampler="host",
-             normal_gate=_KEEP, colors=None):
-        """colors: None, or one uint8 (H, W, 3) / (H, W, 4) image per depth map of this frame: right after the TSDF update of
+             normal_gate=_KEEP, colors=None, track=False):
+        """track: True = lw_cam is a prior and the constructor's tracker finds the frame's cameras first (see there); unset, the frame
+        issues the calls it always did.
+        colors: None, or one uint8 (H, W, 3) / (H, W, 4) image per depth map of this frame: right after the TSDF update of
         either `update` route, and before the warp field decays, they are averaged into `self.C` through the field the update used
         (kernels.integrate_color on this rank's slab, with the update's workspace and its stored node indices where the buffer
         has them) -- colour and geometry see the same field.  Needs the constructor's color_band.  The call reads T, Wt, the maps
@@ -744,6 +778,9 @@ class SlabFrame:
             depth_list, self.live_normals = self.depth_prep(depth_list, self.Kinv, out=self._prep_out)
             self.clean_depth = depth_list
             mark("depth_prep")
+        if track:
+            lw_list = self._track(depth_list, lw_list)
+            mark("track")
         depth, lw_cam = depth_list[0], lw_list[0]
         nd = len(depth_list) if data_views is None else max(1, min(int(data_views), len(depth_list)))
         solve_depth, solve_lw = (depth_list[:nd], lw_list[:nd]) if nd > 1 else (depth, lw_cam)

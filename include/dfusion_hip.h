@@ -1239,6 +1239,89 @@ size_t dfh_raycast_table_bytes(const dfh_slab *slab);
 int dfh_raycast_table(const dfh_volume *vol, void *table, void *stream);
 int dfh_raycast(const dfh_raycast_params *p, void *stream);
 
+/* ---- K21  camera tracking: depth pyramid and dense projective point-to-plane ICP of a frame against the model -------------------
+ * KinectFusion's pose estimation (no reference counterpart): a frame's depth and normal maps (dfh_depth_prep's) are aligned to
+ * the model's predicted maps (dfh_raycast's, or a rendered mesh's), coarse to fine.  Both normal maps share one convention:
+ * camera space, facing the camera, zeros for none.  valid(d) is K12's test: d finite and d < 0.
+ *
+ * dfh_depth_halve: one pyramid step for n_views maps in one launch.  depth: HOST array of n_views device pointers, H x W row-major,
+ * DFH_F32 or DFH_F64 (a float64 value is rounded to nearest-even float32 at load); out: DEVICE (n_views, H/2, W/2) float32 (sizes
+ * rounded down: an odd last row or column is dropped).  float32 arithmetic, one rounding per operation.  Per output pixel (y, x):
+ *   a = D[2y][2x];  a not valid -> 0.  Otherwise sum = 0, n = 0 and, over the taps (2y,2x), (2y,2x+1), (2y+1,2x), (2y+1,2x+1) in
+ *   this order, every valid tap e with |e - a| <= (float)max_jump adds sum = sum + e, n = n + 1;  out = sum / (float)n.
+ * The level's intrinsics are the caller's: fx/2, fy/2, skew/2, cx' = (cx - 0.5)/2, cy' = (cy - 0.5)/2 (a pixel's coordinate is its
+ * integer index).  DFH_E_BADARG before any HIP call: a null depth, depth[v] or out; out equal to a depth[v]; n_views outside
+ * 1..16; a dtype other than DFH_F32 / DFH_F64; H or W < 2 or H*W >= 2^31; max_jump not finite or < 0.
+ *
+ * dfh_icp_track: n_iters Gauss-Newton iterations for all views of ONE pyramid level in one host call; two launches per
+ * iteration, nothing is read back in between.  T (DEVICE, n_views x 12 doubles, row-major 3 x 4: live camera -> model camera)
+ * is read, updated in place and chained over the iterations.  All arithmetic below is fp64 with ONE rounding per operation (no
+ * contraction, IEEE division, square root and rint), float32 map values widened at load; a comparison with a NaN is false.
+ * Per view and live pixel (y, x), X = (double)x, Y = (double)y:
+ *  1. live validity.  d = live_depth[y][x]; no row unless valid(d).  With live normals l: ll = (l0*l0 + l1*l1) + l2*l2; no row
+ *     unless ll > 0.
+ *  2. live vertex.  rho_r(X, Y) = (Kinv[r][0]*X + Kinv[r][1]*Y) + Kinv[r][2];  V_r = (-d)*rho_r;
+ *     P_r = ((T[r][0]*V_0 + T[r][1]*V_1) + T[r][2]*V_2) + T[r][3].
+ *  3. projection.  q_r = (K[r][0]*P_0 + K[r][1]*P_1) + K[r][2]*P_2; no row unless q_2 > 0 and q_2 finite;  ui = rint(q_0/q_2),
+ *     vi = rint(q_1/q_2) (half to even); no row unless 0 <= ui <= W-1 and 0 <= vi <= H-1, tested on the doubles.
+ *  4. model side.  m = model_depth[vi][ui] must be valid; n = model_normals[vi][ui] with nn = (n0*n0 + n1*n1) + n2*n2 > 0;
+ *     M_r = (-m)*rho_r(ui, vi).
+ *  5. gates.  e = P - M;  d2 = (e0*e0 + e1*e1) + e2*e2;  max_dist > 0: no row unless d2 <= max_dist*max_dist.  With live normals:
+ *     Rl_r = (T[r][0]*l_0 + T[r][1]*l_1) + T[r][2]*l_2;  c = (Rl_0*n_0 + Rl_1*n_1) + Rl_2*n_2;  mm = (Rl_0*Rl_0 + Rl_1*Rl_1) + Rl_2*Rl_2;
+ *     no row unless c > 0 and c*c >= (min_cos*min_cos)*(mm*nn)  (K13's form).
+ *  6. row.  r = (n_0*e_0 + n_1*e_1) + n_2*e_2;  J = (P x n, n): J0 = P_1*n_2 - P_2*n_1, J1 = P_2*n_0 - P_0*n_2, J2 = P_0*n_1 - P_1*n_0,
+ *     J3..5 = n: the derivative of r for a twist (omega, v) applied on the LEFT of T (apply_twist_one's order).
+ *     w = huber/|r| if huber > 0 and |r| > huber, else 1.
+ *  7. sums per view, 29 values: the 21 upper entries of A = sum w J^T J (row-major, i <= j), the 6 of g = sum w J r, the objective
+ *     sum w r^2, the count of rows.  The device forms s = sqrt(w), the products (s*J_i)*(s*J_j), (s*J_i)*(s*r), (s*r)*(s*r) and adds
+ *     them on the matrix cores in an order that is fixed (a constant number of workgroups per view, each walking the tiles
+ *     b, b + G, ..; their partials added in index order): the same bits on every run and every device, within
+ *     (n + 4) 2^-53 sum |w J_i J_j| of the exact sum of n rows.  The count is exact.
+ *  8. finish.  count < min_count: no step.  Otherwise D = A with D_ii = A_ii + lm_rel*A_ii, factored D = L L^T column by column,
+ *     j = 0..5:  s = D_jj, for k < j ascending s = s - L_jk*L_jk;  a pivot s that is not > 0 and finite refuses the step;
+ *     L_jj = sqrt(s);  for i > j: t = D_ij, for k < j ascending t = t - L_ik*L_jk;  L_ij = t / L_jj.
+ *     L y = -g: i = 0..5, t = -g_i, for k < i ascending t = t - L_ik*y_k, y_i = t / L_ii.  L^T xi = y: i = 5..0, t = y_i, for
+ *     k = i+1..5 ascending t = t - L_ki*xi_k, xi_i = t / L_ii.  ww = (xi_0*xi_0 + xi_1*xi_1) + xi_2*xi_2, vv likewise of xi_3..5;
+ *     the step is refused unless ww <= max_rot*max_rot and vv <= max_trans*max_trans (a NaN refuses).
+ *     Taken: T <- exp(xi) T.  ww < 1e-8: a = 1 - ww/6, b = 0.5 - ww/24, c = 1/6 - ww/120; otherwise th = sqrt(ww),
+ *     a = sin(th)/th, b = (1 - cos(th))/ww, c = (th - sin(th))/(ww*th).  Om = [omega]x, Om2_ij = omega_i*omega_j (- ww on the
+ *     diagonal);  R_ij = (I_ij + a*Om_ij) + b*Om2_ij;  Vm_ij = (I_ij + b*Om_ij) + c*Om2_ij;  t_r = (Vm_r0*xi_3 + Vm_r1*xi_4) + Vm_r2*xi_5;
+ *     T'[r][c] = (R_r0*T[0][c] + R_r1*T[1][c]) + R_r2*T[2][c], + t_r for c = 3.
+ *     A refused step leaves T untouched: the iterations after it see the same maps and the same T and refuse again.
+ * Outputs: stats, DEVICE doubles (n_views, n_iters, 40): the 29 sums | status (1 stepped, 0 refused) | xi (6, zeros when refused) |
+ * 4 zeros.  rows, optional DEVICE doubles (n_views, H, W, 8): J0..5 | r | w of the FIRST iteration (the one that reads the
+ * caller's T), all zero where there is no row.  scratch: DEVICE, dfh_icp_track_bytes(n_views) bytes, no initial state.
+ * live_depth (V,H,W), model_depth (V,H,W), model_normals (V,H,W,3), live_normals (V,H,W,3) or NULL (no normal gate, no ll test):
+ * DEVICE float32, view-major, contiguous, only read.  n_iters == 0: DFH_OK, nothing launched.
+ * DFH_E_BADARG before any HIP call: null params; n_views outside 1..16; H or W < 1 or H*W >= 2^31; a null live_depth,
+ * model_depth, model_normals, T or scratch, a null stats with n_iters > 0; a K or Kinv entry that is not finite; max_dist, huber or lm_rel negative or
+ * not finite; min_cos outside [0, 1]; n_iters outside 0..64; min_count < 6; max_rot or max_trans not > 0; a scratch smaller
+ * than dfh_icp_track_bytes (which is 0 for n_views outside 1..16). */
+typedef struct dfh_icp_track_params {
+    int n_views;                      /* 1..16 */
+    int H, W;
+    const float *live_depth;          /* DEVICE (V, H, W) */
+    const float *live_normals;        /* DEVICE (V, H, W, 3) or NULL */
+    const float *model_depth;         /* DEVICE (V, H, W) */
+    const float *model_normals;       /* DEVICE (V, H, W, 3) */
+    double K[9], Kinv[9];             /* 3x3 row-major, of this level */
+    double *T;                        /* DEVICE, V x 12, in and out */
+    double max_dist;                  /* 0: no distance gate */
+    double min_cos;                   /* 0..1 */
+    double huber;                     /* 0: no robust weight */
+    double lm_rel;
+    int n_iters;                      /* 0..64 */
+    int min_count;                    /* >= 6 */
+    double max_rot, max_trans;        /* largest |omega| and |v| of one step */
+    double *stats;                    /* DEVICE (V, n_iters, 40) */
+    double *rows;                     /* DEVICE (V, H, W, 8) or NULL */
+    void *scratch;                    /* DEVICE */
+    size_t scratch_bytes;
+} dfh_icp_track_params;
+int dfh_depth_halve(const void *const *depth, int n_views, int depth_dtype, int H, int W, double max_jump, float *out, void *stream);
+size_t dfh_icp_track_bytes(int n_views);
+int dfh_icp_track(const dfh_icp_track_params *p, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
