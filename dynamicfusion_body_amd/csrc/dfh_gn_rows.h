@@ -383,19 +383,33 @@ inline AssocArgs assoc_args(const dfh_gn_problem &p, const dfh_gn_frame &f, bool
     aa.cull = cull && f.n_views >= 4 && !on(opt().gn_no_view_cull) ? 1 : 0;
     return aa;
 }
-// ... and of a landmark term (dfh_gn_landmarks; a NaN fails every comparison it meets)
-inline int check_landmarks(const char *what, const dfh_gn_landmarks *l) {
-    DFH_REQUIRE(l, "%s: null landmarks", what);
-    DFH_REQUIRE(l->n >= 0, "%s: negative landmark count", what);
-    DFH_REQUIRE(l->weight >= 0.0 && l->weight < __builtin_huge_val(), "%s: landmark weight negative or not finite", what);
-    DFH_REQUIRE(l->huber_delta >= 0.0, "%s: landmark huber_delta negative or NaN", what);
-    DFH_REQUIRE(l->max_dist == l->max_dist, "%s: landmark max_dist is NaN", what);
-    if (l->n > 0) {
-        DFH_REQUIRE(l->pos && l->nbr && l->weights && l->target, "%s: null landmark pointer", what);
-        DFH_REQUIRE(l->n_rows >= 1 && l->run_id && l->partial && l->blk_ptr && l->blk_ent && l->node_ptr && l->node_ent,
-                    "%s: null landmark plan array", what);
+// What the sparse terms' checks share (a NaN fails every comparison it meets).  `term` / `item` are the nouns of the messages:
+// "landmark" / "landmark", "photometric" / "photo sample".  First the scalars ...
+inline int check_term_scalars(const char *what, const char *term, const char *item, int n, double weight, double huber) {
+    DFH_REQUIRE(n >= 0, "%s: negative %s count", what, item);
+    DFH_REQUIRE(weight >= 0.0 && weight < __builtin_huge_val(), "%s: %s weight negative or not finite", what, term);
+    DFH_REQUIRE(huber >= 0.0, "%s: %s huber_delta negative or NaN", what, term);
+    return DFH_OK;
+}
+// ... and after the term's own checks, in the order they have always been reported in, the arrays of a term with items: `items`,
+// whether the item arrays are all there, and the plan of T = dfh_gn_landmarks / dfh_gn_photometric.
+template <typename T>
+inline int check_term_arrays(const char *what, const char *term, const char *item, const T *t, bool items) {
+    if (t->n > 0) {
+        DFH_REQUIRE(items, "%s: null %s pointer", what, item);
+        DFH_REQUIRE(t->n_rows >= 1 && t->run_id && t->partial && t->blk_ptr && t->blk_ent && t->node_ptr && t->node_ent,
+                    "%s: null %s plan array", what, term);
     }
     return DFH_OK;
+}
+
+// ... and of a landmark term (dfh_gn_landmarks)
+inline int check_landmarks(const char *what, const dfh_gn_landmarks *l) {
+    DFH_REQUIRE(l, "%s: null landmarks", what);
+    const int rc = check_term_scalars(what, "landmark", "landmark", l->n, l->weight, l->huber_delta);
+    if (rc != DFH_OK) return rc;
+    DFH_REQUIRE(l->max_dist == l->max_dist, "%s: landmark max_dist is NaN", what);
+    return check_term_arrays(what, "landmark", "landmark", l, l->pos && l->nbr && l->weights && l->target);
 }
 
 // The launch of gn_gather_kernel<knn> (dfh_solve.hip) for callers outside that file: the rows of `partial` (live flags behind the
@@ -410,21 +424,14 @@ int gn_add_landmarks_impl(const dfh_gn_problem &q, const dfh_gn_landmarks &l, vo
 // ... and of a photometric term with its frame (dfh_gn_photometric; `fused`: the frame also feeds a fused build)
 inline int check_photometric(const char *what, const dfh_gn_photometric *t, const dfh_gn_frame *f, bool fused) {
     DFH_REQUIRE(t, "%s: null photometric term", what);
-    const int rc = check_frame(what, f, fused);
+    int rc = check_frame(what, f, fused);
+    if (rc == DFH_OK) rc = check_term_scalars(what, "photometric", "photo sample", t->n, t->weight, t->huber_delta);
     if (rc != DFH_OK) return rc;
-    DFH_REQUIRE(t->n >= 0, "%s: negative photo sample count", what);
-    DFH_REQUIRE(t->weight >= 0.0 && t->weight < __builtin_huge_val(), "%s: photometric weight negative or not finite", what);
-    DFH_REQUIRE(t->huber_delta >= 0.0, "%s: photometric huber_delta negative or NaN", what);
     DFH_REQUIRE(t->max_diff == t->max_diff, "%s: photometric max_diff is NaN", what);
     DFH_REQUIRE(t->band_sd > 0.0, "%s: photometric band_sd must be > 0", what);
     DFH_REQUIRE(t->color, "%s: null colour image array", what);
     for (int v = 0; v < f->n_views; ++v) DFH_REQUIRE(t->color[v], "%s: colour image %d is null", what, v);
-    if (t->n > 0) {
-        DFH_REQUIRE(t->pos && t->nbr && t->weights && t->ref, "%s: null photo sample pointer", what);
-        DFH_REQUIRE(t->n_rows >= 1 && t->run_id && t->partial && t->blk_ptr && t->blk_ent && t->node_ptr && t->node_ent,
-                    "%s: null photometric plan array", what);
-    }
-    return DFH_OK;
+    return check_term_arrays(what, "photometric", "photo sample", t, t->pos && t->nbr && t->weights && t->ref);
 }
 
 // The photometric term added to the problem's system (dfh_photometric.hip); the structs are checked by the caller.

@@ -34,6 +34,25 @@ def _i32(a, shape_tail=None):
     return t
 
 
+def _term_takers(n, order, noun, items):
+    """(take, u8) for the per-item arrays of a sparse term with n items.  take(a, conv, what): a converted by conv (None stays
+    None), its length checked, brought into the solver's order -- `order` is the permutation, None: a is already in it -- and always
+    a copy of its own; u8(a): validity flags.  noun / items word the message."""
+    def take(a, conv, what):
+        if a is None:
+            return None
+        t = conv(a)
+        if t.shape[0] != n:
+            raise ValueError("%s %s disagree with the %s in length" % (noun, what, items))
+        return (t[order] if order is not None else t.clone()).contiguous()
+
+    def u8(a):
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
+        return (t != 0).to(device="cuda", dtype=torch.uint8).reshape(-1)
+
+    return take, u8
+
+
 # ------------------------------------------------------------------------------ residual evaluators
 def residual_rigid(x, verts, normals, corr):
     """FusionDM.computef_lw rows (reference core/fusion_dm.py:285-297) -> CUDA fp64 tensor."""
@@ -378,21 +397,10 @@ class WarpSolver:
         used, no second sort and no second plan; only the scratch rows are the term's own.  The term is added by every build that
         is given colour images (colors=) while photo_weight != 0; set_samples and set_graph clear it.  presorted: the arrays are
         already in the solver's own order (that of spos), e.g. computed from it."""
-        def take(a, conv, what):
-            if a is None:
-                return None
-            t = conv(a)
-            if t.shape[0] != self.S:
-                raise ValueError("photometric %s disagree with the samples in length" % what)
-            return (t[self._order_index()] if self.order is not None and not presorted else t.clone()).contiguous()
-
-        def u8(a):
-            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
-            return (t != 0).to(device="cuda", dtype=torch.uint8).reshape(-1)
-
         if ref is None:
             raise ValueError("reference intensities are required")
         S = self.S
+        take, u8 = _term_takers(S, None if self.order is None or presorted else self._order_index(), "photometric", "samples")
         self._ph = {"ref": take(ref, lambda a: _f64(a, ()), "reference intensities"), "valid": take(valid, u8, "validity flags"),
                     "conf": take(conf, lambda a: _f64(a, ()), "confidences"), "partial": None,
                     "active": torch.zeros(S, dtype=torch.uint8, device="cuda"),
@@ -519,19 +527,7 @@ class WarpSolver:
         lm = self._lm
         if lm is None:
             raise ValueError("set_landmarks first")
-
-        def take(a, conv, what):
-            if a is None:
-                return None
-            t = conv(a)
-            if t.shape[0] != lm["L"]:
-                raise ValueError("landmark %s disagree with the landmarks in length" % what)
-            return (t[lm["order"]] if lm["order"] is not None else t.clone()).contiguous()
-
-        def u8(a):
-            t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.asarray(a))
-            return (t != 0).to(device="cuda", dtype=torch.uint8).reshape(-1)
-
+        take, u8 = _term_takers(lm["L"], lm["order"], "landmark", "landmarks")
         lm["target"] = take(target, lambda a: _f64(a, (3,)), "targets")
         lm["valid"] = take(valid, u8, "validity flags")
         lm["conf"] = take(conf, lambda a: _f64(a, ()), "confidences")

@@ -120,10 +120,10 @@ def settings(sv, npos, nw, rng):
 
 
 # ---------------------------------------------------------------- 1. the system against the restatement
-@pytest.mark.parametrize("L", [1, 127, 128, 129, 300])
-@pytest.mark.parametrize("K", [1, 3, 4, 8])
+@pytest.mark.parametrize("K,L", [(K, L) for L in (1, 127, 128, 129, 300) for K in (1, 3, 4, 8)] + [(K, 129) for K in (2, 5, 6, 7)])
 def test_system_vs_restatement(K, L):
-    """build + term at knn 1, 3, 4, 8 and landmark counts on both sides of the 128-landmark tile: Huber and gate off and on,
+    """build + term at knn 1, 3, 4, 8 and landmark counts on both sides of the 128-landmark tile, and at every other knn with one
+    full tile plus a one-landmark tile (every instance of the kernel runs): Huber and gate off and on,
     valid = 0, conf = 0 and a NaN target inactive, active_out exact -- in the solver's order and in the caller's --, the same bits
     twice, the term additive bit for bit, and the no-op forms (weight 0, no landmarks, n = 0) equal to the plain build."""
     rng = np.random.default_rng(1600 + 10 * K + L)
@@ -172,9 +172,10 @@ def test_system_vs_restatement(K, L):
 
 
 # ---------------------------------------------------------------- 2. tuple structure: one run cut by tiles, all distinct, a growing pattern
-@pytest.mark.parametrize("K", [1, 3, 4, 8])
+@pytest.mark.parametrize("K", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_one_tuple_for_all_landmarks(K):
-    """300 landmarks in one node tuple: one run, cut into three scratch rows by the tiles."""
+    """300 landmarks in one node tuple: one run, cut into three scratch rows by the tiles -- and a tile's hundred active rows of one
+    run into passes of kTile / 3 landmarks, the run carried over their boundaries, in every instance of the kernel."""
     rng = np.random.default_rng(1700 + K)
     sv, npos, nw = make_solver(K, rng)
     pos, target, valid, conf = landmark_set(300, rng, "one_tuple")

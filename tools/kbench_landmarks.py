@@ -5,7 +5,9 @@
      frame's fused build (dfh_gn_build with the frame);
   2. one frame's solve (10 GN iterations, one library call) without landmarks and with 19 000 / 77 000;
   3. --parent-lib PATH: the one-call solve WITHOUT landmarks through this build's library and through the parent commit's
-     (a second CDLL on the same problem structs), beside the spread of each variant timed twice.
+     (a second CDLL on the same problem structs), beside the spread of each variant timed twice; then dfh_gn_add_landmarks through
+     both: the term's live scratch rows, tile-cost pairs and live flags, the system after build + term and active_out compared bit
+     for bit, and the term alone timed through both (this build's median of its four medians against the parent's largest).
 
 Variants alternate inside a round, medians of --reps (default 30) per round, every variant is timed in two rounds.
 
@@ -179,6 +181,48 @@ def main():
         r = rounds({"this build": via(sv.lib), "parent": via(plib), "this build (b)": via(sv.lib), "parent (b)": via(plib)}, args.reps, prep=reset)
         for name, v in r.items():
             say("    %-15s %9.1f | %9.1f" % (name, v[0], v[1]))
+        res, argt = _lib._SIGNATURES["dfh_gn_add_landmarks"]
+        plib.dfh_gn_add_landmarks.restype, plib.dfh_gn_add_landmarks.argtypes = res, argt
+        say("   dfh_gn_add_landmarks on the same structs through both libraries: bits, then the term alone (us)")
+        for L in (19000, 77000):
+            set_landmarks(L)
+            reset()
+            build_and_term()                                                # (plans the landmarks)
+            plan = sv._lm["plan"]
+            n_rows, ne = plan["n_rows"], int(sv.lib.dfh_gn_partial_doubles(k))
+            tile = int(sv.lib.dfh_gn_tile_samples())
+            n_tiles = (L + tile - 1) // tile                                # the buffer: rows | {cost, 0} per tile | live flag per row
+
+            def term_via(lib):
+                prob, term = sv._problem(fs.lw), sv._landmark_term()
+
+                def run():
+                    rc = lib.dfh_gn_add_landmarks(prob, term, current_stream_ptr())
+                    assert rc == 0, rc
+                return run
+
+            def outputs(lib):
+                """build, then the term through `lib` into a scratch buffer of sentinels: what the term wrote and the system"""
+                plan["partial"].fill_(-1.0)
+                sv._lm["active"].fill_(7)
+                build_only()
+                term_via(lib)()
+                torch.cuda.synchronize()
+                p = plan["partial"]
+                live = p[n_rows * ne + 2 * n_tiles:]
+                rows = p[:n_rows * ne].view(n_rows, ne)[live == 1.0]      # (dead rows are never written: left out)
+                return [t.clone() for t in (rows, p[n_rows * ne:n_rows * ne + 2 * n_tiles], live, sv.system, sv._lm["active"])]
+            a, b = outputs(sv.lib), outputs(plib)
+            names = ("live scratch rows", "tile-cost pairs", "live flags", "system after build + term", "active_out")
+            say("    L = %6d (%d of %d scratch rows live): %s" % (L, int(a[2].sum()), n_rows, ", ".join(
+                "%s %s" % (n, "identical" if torch.equal(x, y) else "DIFFER") for n, x, y in zip(names, a, b))))
+            r = rounds({"this build": term_via(sv.lib), "parent": term_via(plib), "this build (b)": term_via(sv.lib), "parent (b)": term_via(plib)},
+                       args.reps)
+            for name, v in r.items():
+                say("      term alone, %-15s %8.1f | %8.1f" % (name, v[0], v[1]))
+            new4, par4 = r["this build"] + r["this build (b)"], r["parent"] + r["parent (b)"]
+            say("      term alone: this build's median of four %.1f, the parent's four span %.1f .. %.1f: %s"
+                % (float(np.median(new4)), min(par4), max(par4), "no slower" if float(np.median(new4)) <= max(par4) else "SLOWER"))
     if args.out:
         with open(os.path.join(ROOT, args.out) if not os.path.isabs(args.out) else args.out, "w") as f:
             f.write("\n".join(lines) + "\n")
