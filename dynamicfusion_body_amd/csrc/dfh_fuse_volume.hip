@@ -6,7 +6,7 @@
 // reference's trilinear scheme and blend.  The warp / sampler arithmetic is the exact fp64
 // restatement in dfh_dq.h; the blend is evaluated in fp64 with IEEE division and rounded
 // once to the volume dtype.
-#include "dfh_dqb_front.h"
+#include "dfh_warped_views.h"       // (dfh_dqb_front.h; dqb_index_region)
 
 #include <algorithm>
 #include <cmath>
@@ -1634,12 +1634,10 @@ extern "C" int dfh_fuse_volume_dqb(const dfh_volume *vol, const dfh_live *live_v
     hipStream_t s = static_cast<hipStream_t>(stream);
     int *cand = static_cast<int *>(workspace);
     // a workspace of dfh_dqb_workspace_bytes_cached() also keeps every voxel's k node indices
-    const size_t base = cand_bytes(*sl);
-    const size_t cached1 = dfh_dqb_workspace_bytes_cached(sl, knn, n_nodes, 1);
-    const size_t cached2 = dfh_dqb_workspace_bytes_cached(sl, knn, n_nodes, 2);
-    const bool has_idx = cached1 > base && workspace_bytes >= cached1 && !on(opt().k3_no_cache);
-    const bool has_w = has_idx && workspace_bytes >= cached2;
-    unsigned short *knn_cache = has_idx ? reinterpret_cast<unsigned short *>(static_cast<char *>(workspace) + base) : nullptr;
+    size_t cached1;
+    unsigned short *knn_cache = dqb_index_region(sl, knn, n_nodes, workspace, workspace_bytes, &cached1);
+    const bool has_idx = knn_cache != nullptr;
+    const bool has_w = has_idx && workspace_bytes >= dfh_dqb_workspace_bytes_cached(sl, knn, n_nodes, 2);
     double *w_cache = has_w ? reinterpret_cast<double *>(static_cast<char *>(workspace) + cached1) : nullptr;
     int mode = !has_idx ? 0 : (rebuild_candidates ? 1 : (has_w ? 3 : 2));
     // float32 volumes with knn = 4 take the fast path; its cache (28 B per voxel) lives where the exact path keeps its fp64

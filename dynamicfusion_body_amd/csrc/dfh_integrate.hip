@@ -26,6 +26,7 @@
 //                    (scale*T*w + m)/(scale*(1+w)).
 // fp64 volumes always use exact_voxel() and IEEE fp64 division for the running average.
 #include "dfh_common.h"
+#include "dfh_warped_views.h"       // is_pinhole
 
 #include <cstdlib>
 
@@ -1053,8 +1054,7 @@ static bool fill_params(IntegrateParams &p, const dfh_slab &sl, const dfh_depth_
         p.planes_per_block = (int)((p.nx + chunks - 1) / chunks);
         if (opt().k1_planes_per_block > 0) p.planes_per_block = (int)opt().k1_planes_per_block;       // tuning knob for kbench sweeps
     }
-    return K[1] == 0.0 && K[3] == 0.0 && K[6] == 0.0 && K[7] == 0.0 && K[8] == 1.0 && Kinv[6] == 0.0 && Kinv[7] == 0.0 &&
-           Kinv[8] == 1.0;
+    return is_pinhole(K, Kinv);
 }
 
 }  // namespace dfh

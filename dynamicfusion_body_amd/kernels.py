@@ -40,14 +40,32 @@ def _check_depth(d):
         raise ValueError("depth must be a contiguous 2-D CUDA tensor")
 
 
-def _integrate(vol, tsdf_res, depths, K, Kinv, lws, scale, center, tdist, wmax, fresh, workspace):
-    """One dfh_integrate_depth call: the maps `depths` (at most 16, one shape and dtype) into `vol`."""
-    n = len(depths)
-    H, W = depths[0].shape
-    ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in depths])
-    lw = _lib.darr(np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in lws]), 12 * n)
-    views = _lib.DepthViews(n, ptrs, dtype_code(depths[0]), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), lw, float(scale),
-                            _lib.darr(np.asarray(center, dtype=np.float64), 3), tsdf_res)
+def _view_batches(depths, lws, K, Kinv, scale, center, on_gpu=False):
+    """The depth maps of one call: checks that they are 2-D tensors of one shape and dtype (on_gpu: _check_depth on each instead
+    of the first half, for callers that already hold a device) and returns batches(tsdf_res), a generator of (i, dfh_depth_views)
+    over the maps [i, i + 16) -- the most one library call takes."""
+    for d in depths:
+        if on_gpu:
+            _check_depth(d)
+        elif not (isinstance(d, torch.Tensor) and d.dim() == 2):
+            raise ValueError("depth must be a contiguous 2-D CUDA tensor")
+        if d.shape != depths[0].shape or d.dtype != depths[0].dtype:
+            raise ValueError("all depth maps of one call must have the same shape and dtype")
+
+    def batches(tsdf_res):
+        H, W = depths[0].shape
+        for i in range(0, len(depths), 16):
+            dd = depths[i:i + 16]
+            n = len(dd)
+            ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dd])
+            lw = _lib.darr(np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in lws[i:i + 16]]), 12 * n)
+            yield i, _lib.DepthViews(n, ptrs, dtype_code(dd[0]), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), lw, float(scale),
+                                     _lib.darr(np.asarray(center, dtype=np.float64), 3), tsdf_res)
+    return batches
+
+
+def _integrate(vol, views, tdist, wmax, fresh, workspace):
+    """One dfh_integrate_depth call: the maps of `views` (one batch of _view_batches) into `vol`."""
     ws_ptr, ws_bytes = (workspace.data_ptr(), workspace.numel() * workspace.element_size()) if isinstance(workspace, torch.Tensor) else (0, 0)
     rc = _lib.load().dfh_integrate_depth(vol, views, float(tdist), float(wmax), None if fresh is None else ctypes.c_double(float(fresh)),
                                          ws_ptr, ws_bytes, current_stream_ptr())
@@ -129,10 +147,10 @@ def integrate_depth(T, Wt, depth, K, Kinv, lw, scale, center, tdist, wmax=100.0,
     vol, tsdf_res = _volume(T, Wt, res, x_range, tsdf_res)
     if vol.slab.x1 == vol.slab.x0:
         return T, Wt
-    _check_depth(depth)
+    batches = _view_batches([depth], [lw], K, Kinv, scale, center, on_gpu=True)
     if workspace is None and T.dtype == torch.float32:
         workspace = integrate_workspace(1, *depth.shape, vol.slab.res, (vol.slab.x0, vol.slab.x1), T.device)
-    _integrate(vol, tsdf_res, [depth], K, Kinv, [lw], scale, center, tdist, wmax, None, workspace)
+    _integrate(vol, next(batches(tsdf_res))[1], tdist, wmax, None, workspace)
     return T, Wt
 
 
@@ -177,18 +195,14 @@ def integrate_depth_views(T, Wt, depths, K, Kinv, lws, scale, center, tdist, wma
             T.fill_(float(fresh))
             Wt.zero_()
         return T, Wt
-    for d in depths:
-        _check_depth(d)
-        if d.shape != depths[0].shape or d.dtype != depths[0].dtype:
-            raise ValueError("all depth maps of one call must have the same shape and dtype")
+    batches = _view_batches(depths, lws, K, Kinv, scale, center, on_gpu=True)
     H, W = depths[0].shape
     slab = vol.slab
-    for i in range(0, len(depths), 16):
-        dd, ll = depths[i:i + 16], lws[i:i + 16]
-        nbytes = lib.dfh_integrate_workspace_bytes(len(dd), int(H), int(W), slab)
+    for i, views in batches(tsdf_res):
+        nbytes = lib.dfh_integrate_workspace_bytes(views.n_views, int(H), int(W), slab)
         ws = workspace if (workspace is not None and workspace.numel() * workspace.element_size() >= nbytes) else \
-            integrate_workspace(len(dd), H, W, slab.res, (slab.x0, slab.x1), T.device)
-        _integrate(vol, tsdf_res, dd, K, Kinv, ll, scale, center, tdist, wmax, fresh if i == 0 else None, ws)
+            integrate_workspace(views.n_views, H, W, slab.res, (slab.x0, slab.x1), T.device)
+        _integrate(vol, views, tdist, wmax, fresh if i == 0 else None, ws)
     return T, Wt
 
 
@@ -315,11 +329,7 @@ def integrate_depth_dqb(T, Wt, depths, K, Kinv, lws, scale, center, tdist, node_
         raise ValueError('length of camera matrix array must equal that of depth maps')        # core/fusion_dm.py:96-97
     if weight not in WARPED_WEIGHTS:
         raise ValueError("weight must be one of %s, not %r" % (sorted(WARPED_WEIGHTS), weight))
-    for d in depths:                                   # (what needs no device is checked before one is asked for)
-        if not (isinstance(d, torch.Tensor) and d.dim() == 2):
-            raise ValueError("depth must be a contiguous 2-D CUDA tensor")
-        if d.shape != depths[0].shape or d.dtype != depths[0].dtype:
-            raise ValueError("all depth maps of one call must have the same shape and dtype")
+    batches = _view_batches(depths, lws, K, Kinv, scale, center)       # (what needs no device is checked before one is asked for)
     require_gpu()
     lib = _lib.load()
     vol, tsdf_res = _volume(T, Wt, res, x_range, tsdf_res)
@@ -331,15 +341,8 @@ def integrate_depth_dqb(T, Wt, depths, K, Kinv, lws, scale, center, tdist, node_
     if workspace is None:
         workspace = dqb_workspace(vol.slab.res, (vol.slab.x0, vol.slab.x1))
         rebuild_candidates = True
-    H, W = depths[0].shape
     nodes = _lib.Nodes(P.data_ptr(), Q.data_ptr(), Wn.data_ptr(), int(P.shape[0]), int(knn))
-    for i in range(0, len(depths), 16):
-        dd, ll = depths[i:i + 16], lws[i:i + 16]
-        n = len(dd)
-        ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dd])
-        lw = _lib.darr(np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in ll]), 12 * n)
-        views = _lib.DepthViews(n, ptrs, dtype_code(dd[0]), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), lw, float(scale),
-                                _lib.darr(np.asarray(center, dtype=np.float64), 3), tsdf_res)
+    for i, views in batches(tsdf_res):
         rc = lib.dfh_integrate_depth_dqb(vol, views, nodes, _lib.darr(lw_dq, 8), float(tdist), float(wmax), WARPED_WEIGHTS[weight],
                                          workspace.data_ptr(), workspace.numel() * 4, 1 if (rebuild_candidates and i == 0) else 0,
                                          current_stream_ptr())
@@ -414,11 +417,7 @@ def integrate_color(C, T, Wt, depths, colors, K, Kinv, lws, scale, center, tdist
     given = [a is not None for a in (node_pos, node_dq, node_w, knn, lw_dq)]
     if any(given) and not all(given):
         raise ValueError("node_pos, node_dq, node_w, knn and lw_dq go together")
-    for d in depths:
-        if not (isinstance(d, torch.Tensor) and d.dim() == 2):
-            raise ValueError("depth must be a contiguous 2-D CUDA tensor")
-        if d.shape != depths[0].shape or d.dtype != depths[0].dtype:
-            raise ValueError("all depth maps of one call must have the same shape and dtype")
+    batches = _view_batches(depths, lws, K, Kinv, scale, center)
     if stored_indices and (not given[0] or workspace is None):
         raise ValueError("stored_indices needs nodes and the workspace that holds the indices")
     require_gpu()
@@ -442,14 +441,8 @@ def integrate_color(C, T, Wt, depths, colors, K, Kinv, lws, scale, center, tdist
         ws_ptr, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
     if band_sd is None:
         band_sd = float(band) * abs(float(scale))
-    for i in range(0, len(depths), 16):
-        dd, ll, cc = depths[i:i + 16], lws[i:i + 16], colors[i:i + 16]
-        n = len(dd)
-        ptrs = (ctypes.c_void_p * n)(*[d.data_ptr() for d in dd])
-        cptrs = (ctypes.c_void_p * n)(*[c.data_ptr() for c in cc])
-        lw = _lib.darr(np.concatenate([np.asarray(l, dtype=np.float64).reshape(12) for l in ll]), 12 * n)
-        views = _lib.DepthViews(n, ptrs, dtype_code(dd[0]), int(H), int(W), _lib.darr(K, 9), _lib.darr(Kinv, 9), lw, float(scale),
-                                _lib.darr(np.asarray(center, dtype=np.float64), 3), tsdf_res)
+    for i, views in batches(tsdf_res):
+        cptrs = (ctypes.c_void_p * views.n_views)(*[c.data_ptr() for c in colors[i:i + 16]])
         rc = lib.dfh_integrate_color(cvol, vol, views, cptrs, nodes, lw8, float(tdist), float(band), float(band_sd), float(wmax),
                                      ws_ptr, ws_bytes, 1 if stored_indices else 0, current_stream_ptr())
         _lib.check(rc, "dfh_integrate_color")

@@ -20,6 +20,8 @@ BIG = 1 << 30
 
 @functools.lru_cache(maxsize=None)
 def scene_of(name):
+    if name == "skewed main":
+        return WN.skewed_scene(scene_of("main"))
     return {"main": WN.main_scene, "ragged": WN.ragged_scene, "clustered": WN.clustered_scene}[name]()
 
 
@@ -118,10 +120,10 @@ def test_sample_colors_by_hand():
 
 
 # ---------------------------------------------------------------------------------------------- (b) the exclusion cap
-LIVE = {"main": (428, 622, 881), "ragged": (38, 57, 80), "clustered": (44, 73, 105)}
+LIVE = {"main": (428, 622, 881), "ragged": (38, 57, 80), "clustered": (44, 73, 105), "skewed main": (431, 622, 884)}
 
 
-@pytest.mark.parametrize("name", ["main", "ragged", "clustered"])
+@pytest.mark.parametrize("name", ["main", "ragged", "clustered", "skewed main"])
 def test_scenes_stay_clear_of_the_decision_boundaries(name):
     sc = scene_of(name)
     T, Wt = volumes(name)

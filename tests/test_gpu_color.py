@@ -33,6 +33,8 @@ def dev(a, dtype=None):
 
 @functools.lru_cache(maxsize=None)
 def scene_of(name):
+    if name == "skewed main":
+        return WN.skewed_scene(scene_of("main"))
     return {"main": WN.main_scene, "ragged": WN.ragged_scene, "clustered": WN.clustered_scene}[name]()
 
 
@@ -128,23 +130,25 @@ def live_of(T, Wt, band):
 
 # ---------------------------------------------------------------------------------------------- 1. parity
 @pytest.mark.parametrize("mode", ["search", "stored"])
-@pytest.mark.parametrize("name,knn", [("main", 1), ("main", 3), ("main", 4), ("main", 8), ("ragged", 4), ("clustered", 4)])
-def test_parity_with_the_restatement(name, knn, mode):
+@pytest.mark.parametrize("name,knn,depth_dtype", [
+    pytest.param("main", 1, None, id="main-1"), pytest.param("main", 3, None, id="main-3"), pytest.param("main", 4, None, id="main-4"),
+    pytest.param("main", 8, None, id="main-8"), pytest.param("ragged", 4, None, id="ragged-4"),
+    pytest.param("clustered", 4, None, id="clustered-4"), pytest.param("skewed main", 3, None, id="skewed main-3"),
+    pytest.param("skewed main", 8, None, id="skewed main-8"), pytest.param("main", 3, torch.float64, id="main-3-float64 maps")])
+def test_parity_with_the_restatement(name, knn, depth_dtype, mode):
     """Two views with different images through a non-rigid field.  ragged: no extent is a multiple of the brick; clustered: more
-    than the 256 candidates a brick keeps, so the device scans every node."""
+    than the 256 candidates a brick keeps, so the device scans every node; skewed main: the general projection chain (the volumes
+    and the reference are the restatement's through the same K); float64 maps: the same values, the other load."""
     sc = scene_of(name)
     T, Wt = volumes(name, knn)
     start = CN.pattern(sc["shape"])
-    C = run(sc, start, T, Wt, images(name), 1.5, knn=knn, mode=mode)
+    C = run(sc, start, T, Wt, images(name), 1.5, knn=knn, mode=mode, depth_dtype=depth_dtype)
     compare(C, reference(name, knn, 1.5), start, live_of(T, Wt, 1.5))
 
 
 # ---------------------------------------------------------------------------------------------- 2. the no-warp anchor
 def skewed():
-    K = scene_of("main")["K"].copy()
-    K[0, 1] = 0.7                      # skew
-    K[2, 0], K[2, 1] = 1e-5, -2e-5     # a projective row: K^-1's third row is full
-    return K, np.linalg.inv(K)
+    return WN.skewed(scene_of("main")["K"])
 
 
 @pytest.mark.parametrize("mode", ["search", "stored"])

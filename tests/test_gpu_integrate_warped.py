@@ -29,6 +29,8 @@ def dev(a, dtype=None):
 
 @functools.lru_cache(maxsize=None)
 def scene_of(name):
+    if name == "skewed ragged":
+        return WN.skewed_scene(scene_of("ragged"))
     return {"main": WN.main_scene, "ragged": WN.ragged_scene, "clustered": WN.clustered_scene}[name]()
 
 
@@ -197,10 +199,7 @@ def test_bad_depth_values_update_nothing(dtype):
 @functools.lru_cache(maxsize=None)
 def general_k_case(dtype):
     sc = scene_of("main")
-    K = sc["K"].copy()
-    K[0, 1] = 0.7                      # skew
-    K[2, 0], K[2, 1] = 1e-5, -2e-5     # a projective row: (K lpos)_2 != lpos_2, and K^-1's third row is full
-    Kinv = np.linalg.inv(K)
+    K, Kinv = WN.skewed(sc["K"])
     T, Wt, masks, mg = WN.restate(sc, 4, "node_distance", 7.0, dtype, K=K, Kinv=Kinv)
     return K, Kinv, (T, Wt, masks, WN.excluded(mg))
 
@@ -216,14 +215,17 @@ def test_general_intrinsics(dtype):
 
 # ---------------------------------------------------------------------------------------------- 4. workspace
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
-@pytest.mark.parametrize("knn", [3, 4, 8])
-def test_search_store_and_load_agree(knn, dtype):
-    sc = scene_of("main")
+@pytest.mark.parametrize("knn,name", [pytest.param(3, "main", id="3"), pytest.param(4, "main", id="4"), pytest.param(8, "main", id="8"),
+                                      pytest.param(3, "skewed ragged", id="3-skewed ragged"),
+                                      pytest.param(8, "skewed ragged", id="8-skewed ragged")])
+def test_search_store_and_load_agree(knn, name, dtype):
+    """skewed ragged: the general projection chain through the storing and the loading mode, on bricks and z-runs with ragged ends."""
+    sc = scene_of(name)
     N = len(sc["node_pos"])
     base = kernels.dqb_workspace(sc["shape"])
     T, Wt = run(sc, knn, "node_distance", 7.0, dtype, workspace=base, rebuild_candidates=True)              # search only
     T1, W1 = run(sc, knn, "node_distance", 7.0, dtype, workspace=base, rebuild_candidates=False)            # ... of existing lists
-    assert torch.equal(T1, T) and torch.equal(W1, Wt)
+    assert torch.equal(T1, T) and torch.equal(W1, Wt) and bool((Wt != 0).any()) and bool((Wt == 0).any())
     other_dq = WN.field(np.random.default_rng(3), N, 0.05, 0.2, 0.0)
     for level in (1, 2):
         ws = kernels.dqb_workspace(sc["shape"], knn=knn, n_nodes=N, level=level)

@@ -180,6 +180,20 @@ def clustered_scene(seed=9):
                 node_dq=node_dq, lw_dq=lw_dq, shape=shape, tsdf_res=32)
 
 
+def skewed(K):
+    """K with a skew and a projective row, and its inverse, whose third row is full: the general projection chain."""
+    K = K.copy()
+    K[0, 1] = 0.7                      # skew
+    K[2, 0], K[2, 1] = 1e-5, -2e-5     # a projective row: (K lpos)_2 != lpos_2, and K^-1's third row is full
+    return K, np.linalg.inv(K)
+
+
+def skewed_scene(sc):
+    """A copy of the scene seen through skewed(K)."""
+    K, Kinv = skewed(sc["K"])
+    return dict(sc, K=K, Kinv=Kinv)
+
+
 def start_volumes(sc, dtype=np.float64):
     T = np.full(sc["shape"], sc["tdist"] / sc["scale"], dtype=dtype)
     return T, np.zeros(sc["shape"], dtype=dtype)
