@@ -147,6 +147,25 @@ class IcpTrackParams(ctypes.Structure):
                 ("stats", _vp), ("rows", _vp), ("scratch", _vp), ("scratch_bytes", ctypes.c_size_t)]
 
 
+class MeshSdfLayout(ctypes.Structure):
+    """dfh_mesh_sdf_layout: the cell table's geometry and size, filled by dfh_mesh_sdf_plan."""
+    _fields_ = [("lo", _dbl * 3), ("hi", _dbl * 3), ("cell", _dbl), ("maxabs", _dbl), ("dims", _int * 3),
+                ("n_verts", ctypes.c_long), ("n_faces", ctypes.c_long), ("n_entries", ctypes.c_long), ("bytes", ctypes.c_size_t)]
+
+
+class MeshSdf(ctypes.Structure):
+    """dfh_mesh_sdf: a mesh on the device with its pseudonormal tables and its cell table."""
+    _fields_ = [("verts", _vp), ("faces", _vp), ("keep", _vp), ("face_normals", _vp), ("edge_normals", _vp), ("vertex_normals", _vp),
+                ("n_verts", ctypes.c_long), ("n_faces", ctypes.c_long), ("table", _vp), ("table_bytes", ctypes.c_size_t),
+                ("layout", MeshSdfLayout)]
+
+
+class MeshSdfGridParams(ctypes.Structure):
+    """dfh_mesh_sdf_grid_params: the grid, the band and the device outputs of one dfh_mesh_sdf_grid call."""
+    _fields_ = [("origin", _dbl * 3), ("spacing", _dbl * 3), ("shape", _int * 3), ("band", _dbl), ("orientation", _int), ("dtype", _int),
+                ("value", _vp), ("status", _vp), ("closest", _vp), ("face", _vp)]
+
+
 _problem_p = ctypes.POINTER(Problem)
 _frame_p = ctypes.POINTER(Frame)
 _slab_p = ctypes.POINTER(Slab)
@@ -160,7 +179,8 @@ STRUCTS = {"dfh_gn_problem": Problem, "dfh_gn_frame": Frame, "dfh_gn_solve_param
            "dfh_gn_volume_term": VolumeTerm, "dfh_depth_prep_params": DepthPrepParams,
            "dfh_gn_normal_gate": NormalGate, "dfh_gn_landmarks": Landmarks, "dfh_color_volume": ColorVolume,
            "dfh_gn_photometric": Photometric, "dfh_rgbd_view": RGBDView, "dfh_rgbd_ingest_params": RGBDIngestParams,
-           "dfh_raycast_params": RaycastParams, "dfh_icp_track_params": IcpTrackParams}
+           "dfh_raycast_params": RaycastParams, "dfh_icp_track_params": IcpTrackParams,
+           "dfh_mesh_sdf_layout": MeshSdfLayout, "dfh_mesh_sdf": MeshSdf, "dfh_mesh_sdf_grid_params": MeshSdfGridParams}
 
 _SIGNATURES = {
     "dfh_version": (_int, []),
@@ -279,6 +299,11 @@ _SIGNATURES = {
     "dfh_depth_halve": (_int, [ctypes.POINTER(_vp), _int, _int, _int, _int, _dbl, _vp, _vp]),
     "dfh_icp_track_bytes": (ctypes.c_size_t, [_int]),
     "dfh_icp_track": (_int, [ctypes.POINTER(IcpTrackParams), _vp]),
+    "dfh_mesh_sdf_chunk": (_int, []),
+    "dfh_mesh_sdf_plan": (_int, [_vp, ctypes.c_long, _vp, _vp, ctypes.c_long, _dbl, ctypes.POINTER(MeshSdfLayout)]),
+    "dfh_mesh_sdf_build": (_int, [ctypes.POINTER(MeshSdf), _vp]),
+    "dfh_mesh_sdf_points": (_int, [ctypes.POINTER(MeshSdf), _vp, ctypes.c_long, _dbl, _int, _vp, _vp, _vp, _vp]),
+    "dfh_mesh_sdf_grid": (_int, [ctypes.POINTER(MeshSdf), ctypes.POINTER(MeshSdfGridParams), _vp]),
 }
 
 _lib = None

@@ -123,6 +123,16 @@ class Fusion:
             raise ValueError('Only accept 3D np array as tsdf')                  # :162-163
         return to_device(curr_tsdf, dtype=torch.float32 if f32_exact(curr_tsdf) else torch.float64)
 
+    def volume_from_mesh(self, verts, faces, band=None, orientation=+1):
+        """The signed-distance volume of a mesh given in the canonical volume's index coordinates (origin 0, spacing 1), with
+        the canonical volume's shape and dtype: the exact distance inside `band` (default: the truncation distance), +-band
+        beyond it (mesh.MeshDistance.grid).  The result goes straight into setupCorrespondences / updateTSDF."""
+        from . import mesh
+        self._ensure_volumes()
+        band = self._tdist if band is None else float(band)
+        md = mesh.MeshDistance(verts, faces, orientation=orientation, device=self._T.device)
+        return md.grid(0.0, 1.0, tuple(self._T.shape), band, dtype=self._vol_dtype)
+
     # ------------------------------------------------------------------ A4
     def updateTSDF(self, curr_tsdf=None, wmax=100.0):
         """Warp every canonical voxel through the DQB warp field and `_lw` into the live TSDF,

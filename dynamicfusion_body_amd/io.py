@@ -141,3 +141,23 @@ def write_ppm(path, image):
     with open(path, 'wb') as f:
         f.write(b'P6\n%d %d\n255\n' % (a.shape[1], a.shape[0]))
         f.write(np.ascontiguousarray(a).tobytes())
+
+
+def mesh_to_dist(path, verts, faces, res, b_min=None, b_max=None, margin=0.1, orientation=+1):
+    """Write the reference-format `.dist` file of a mesh: the exact signed distance (mesh.MeshDistance, band = inf) and the
+    closest surface point at the (1 + res)^3 grid vertices of the box [b_min, b_max] (default: the mesh's box grown by `margin`
+    on every side).  res: one integer or three.  Returns (b_min, b_max, volume, closest_points) as load_sdf would."""
+    from . import mesh
+    res = np.broadcast_to(np.asarray(res, dtype=np.int64), (3,))
+    if res.min() < 1:
+        raise ValueError("res must be at least 1")
+    md = mesh.MeshDistance(verts, faces, orientation=orientation)
+    v = np.asarray(verts.detach().cpu().numpy() if hasattr(verts, "detach") else verts, dtype=np.float64)
+    b_min = v.min(axis=0) - margin if b_min is None else np.asarray(b_min, dtype=np.float64).reshape(3)
+    b_max = v.max(axis=0) + margin if b_max is None else np.asarray(b_max, dtype=np.float64).reshape(3)
+    if not (np.isfinite(b_min).all() and np.isfinite(b_max).all() and (b_max > b_min).all()):
+        raise ValueError("the box must be finite with b_max > b_min")
+    vol, cp = md.grid(b_min, (b_max - b_min) / res, tuple(int(r) + 1 for r in res), float("inf"), dtype=np.float32, want_closest=True)
+    vol, cp = vol.cpu().numpy(), cp.cpu().numpy()
+    write_sdf(path, b_min, b_max, vol, cp)
+    return b_min, b_max, vol, cp

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .device import HostScalar, current_stream_ptr, dtype_code, require_gpu
+from .device import HostScalar, current_stream_ptr, dtype_code, require_gpu, torch_dtype
 
 
 def marching_cubes(volume, level=None, step_size=1, as_numpy=False, order="reference", visit_all_tiles=False):
@@ -338,3 +338,173 @@ def depth_error(rendered, observed, gate):
         out.append({"n_valid": n, "n_within": int((d <= gate).sum()) if n else 0,
                     "mean": float(d.mean()) if n else float("nan"), "median": float(d.median()) if n else float("nan")})
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- K22
+# Mesh -> signed distance (csrc/dfh_mesh_sdf.hip; the result is defined in include/dfusion_hip.h).  The pseudonormal tables are
+# built here, once per mesh, in numpy fp64 (the arccos stays on the host, so the device and tests/mesh_sdf_np.py read the same
+# tables); everything per query point runs on the device.
+
+def _mesh_arrays(verts, faces):
+    v = verts.detach().cpu().numpy() if isinstance(verts, torch.Tensor) else np.asarray(verts)
+    f = faces.detach().cpu().numpy() if isinstance(faces, torch.Tensor) else np.asarray(faces)
+    if v.ndim != 2 or v.shape[1] != 3 or v.dtype not in (np.float32, np.float64):
+        raise ValueError("verts must be (Nv, 3) float32 or float64")
+    if f.ndim != 2 or f.shape[1] != 3 or not np.issubdtype(f.dtype, np.integer):
+        raise ValueError("faces must be (F, 3) integer")
+    if len(f) and (int(f.min()) < 0 or int(f.max()) >= len(v)):
+        raise ValueError("faces hold a vertex index outside [0, %d)" % len(v))
+    return np.ascontiguousarray(v, dtype=np.float64), np.ascontiguousarray(f, dtype=np.int32)
+
+
+def _dot3(a, b):
+    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+
+def pseudonormals(verts, faces):
+    """The angle-weighted pseudonormal tables of Baerentzen and Aanaes, fp64: (face_normals (F,3), edge_normals (F,3,3),
+    vertex_normals (Nv,3), dropped (F,) bool).  dropped marks the faces whose ab x ac is the exact zero vector: they take part in
+    nothing.  face: the unit normal.  edge, per (face, local edge AB / AC / BC): the sum of the unit normals of the kept faces
+    sharing the undirected edge, in ascending face order (a boundary edge: the face's own).  vertex: the sum over the kept
+    (face, corner) pairs at the vertex, in ascending (face, corner) order, of angle * unit normal, angle = arccos of the clipped
+    cosine between the corner's two edges."""
+    v, f = _mesh_arrays(verts, faces)
+    A, B, C = v[f[:, 0]], v[f[:, 1]], v[f[:, 2]]
+    ab, ac = B - A, C - A
+    cr = np.stack([ab[:, 1] * ac[:, 2] - ab[:, 2] * ac[:, 1], ab[:, 2] * ac[:, 0] - ab[:, 0] * ac[:, 2],
+                   ab[:, 0] * ac[:, 1] - ab[:, 1] * ac[:, 0]], axis=1)
+    dropped = ~(cr != 0).any(axis=1)
+    keep = np.flatnonzero(~dropped)
+    fn = np.zeros((len(f), 3))
+    en = np.zeros((len(f), 3, 3))
+    vn = np.zeros((len(v), 3))
+    if len(keep):
+        with np.errstate(all="ignore"):
+            fn[keep] = cr[keep] / np.sqrt(_dot3(cr[keep], cr[keep]))[:, None]
+            fk = f[keep].astype(np.int64)
+            # edges: items in (face, local edge) order, grouped by their undirected vertex pair
+            pairs = np.stack([fk[:, [0, 1]], fk[:, [0, 2]], fk[:, [1, 2]]], axis=1).reshape(-1, 2)
+            key = pairs.min(axis=1) * len(v) + pairs.max(axis=1)
+            _, inv = np.unique(key, return_inverse=True)
+            inv = inv.reshape(-1)
+            acc = np.zeros((int(inv.max()) + 1, 3))
+            np.add.at(acc, inv, np.repeat(fn[keep], 3, axis=0))
+            en[keep] = acc[inv].reshape(-1, 3, 3)
+            # vertices: items in (face, corner) order
+            P = np.stack([A[keep], B[keep], C[keep]], axis=1)                  # (K, 3 corners, 3)
+            u = np.stack([P[:, 1] - P[:, 0], P[:, 2] - P[:, 1], P[:, 0] - P[:, 2]], axis=1).reshape(-1, 3)
+            w = np.stack([P[:, 2] - P[:, 0], P[:, 0] - P[:, 1], P[:, 1] - P[:, 2]], axis=1).reshape(-1, 3)
+            cosang = _dot3(u, w) / (np.sqrt(_dot3(u, u)) * np.sqrt(_dot3(w, w)))
+            ang = np.arccos(np.minimum(np.maximum(cosang, -1.0), 1.0))
+            np.add.at(vn, fk.reshape(-1), ang[:, None] * np.repeat(fn[keep], 3, axis=0))
+    return fn, en, vn, dropped
+
+
+class MeshDistance:
+    """A triangle mesh on the device, ready for exact distance queries: vertices widened to fp64, the pseudonormal tables, and
+    the uniform cell table the query kernel walks.  orientation = +1: the faces wind outward (positive outside); cell: the table's
+    cell edge (None: the library chooses); device: a CUDA device (None: the current one)."""
+
+    def __init__(self, verts, faces, orientation=+1, cell=None, device=None):
+        if orientation not in (1, -1):
+            raise ValueError("orientation must be +1 or -1")
+        v, f = _mesh_arrays(verts, faces)
+        self.lib = lib = _lib.load()
+        fn, en, vn, dropped = pseudonormals(v, f)
+        keep = np.ascontiguousarray(~dropped, dtype=np.uint8)
+        if cell is not None and not (np.isfinite(cell) and cell > 0):
+            raise ValueError("cell must be finite and > 0")
+        self.layout = lay = _lib.MeshSdfLayout()
+        _lib.check(lib.dfh_mesh_sdf_plan(v.ctypes.data, len(v), f.ctypes.data, keep.ctypes.data, len(f), 0.0 if cell is None else float(cell),
+                                         lay), "dfh_mesh_sdf_plan")
+        require_gpu()
+        self.device = dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.orientation = int(orientation)
+        self.n_verts, self.n_faces, self.dropped = len(v), len(f), dropped
+        with torch.cuda.device(dev):
+            self._t = [torch.from_numpy(a).to(dev) for a in (v, f, keep, fn, en, vn)]
+            self._table = torch.empty((lay.bytes + 7) // 8, dtype=torch.int64, device=dev)
+            self._m = _lib.MeshSdf(*[t.data_ptr() for t in self._t], len(v), len(f), self._table.data_ptr(), self._table.numel() * 8, lay)
+            _lib.check(lib.dfh_mesh_sdf_build(self._m, current_stream_ptr()), "dfh_mesh_sdf_build")
+
+    @property
+    def cell(self):
+        return float(self.layout.cell)
+
+    def query(self, points, band=float("inf")):
+        """points (N, 3) -> (signed distance (N,) float64, closest point (N, 3) float32, face (N,) int32), device tensors.  A point
+        farther than band: +band, NaN, -1."""
+        p = points if isinstance(points, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(points, dtype=np.float64))
+        if p.dim() != 2 or p.shape[1] != 3:
+            raise ValueError("points must be (N, 3)")
+        p = p.to(device=self.device, dtype=torch.float64).contiguous()
+        n = p.shape[0]
+        with torch.cuda.device(self.device):
+            # a wave searches around the box of its 64 consecutive points: hand them over in Morton order of their table cells
+            # (a point's result does not depend on its neighbours in the wave) and put the results back
+            order = self._morton_order(p) if n > 64 else None
+            q = p if order is None else p[order].contiguous()
+            sd = torch.empty(n, dtype=torch.float64, device=self.device)
+            cl = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+            fc = torch.empty(n, dtype=torch.int32, device=self.device)
+            _lib.check(self.lib.dfh_mesh_sdf_points(self._m, q.data_ptr(), n, float(band), self.orientation, sd.data_ptr(), cl.data_ptr(),
+                                                    fc.data_ptr(), current_stream_ptr()), "dfh_mesh_sdf_points")
+            if order is not None:
+                inv = torch.empty_like(order)
+                inv[order] = torch.arange(n, device=self.device)
+                sd, cl, fc = sd[inv], cl[inv], fc[inv]
+        return sd, cl, fc
+
+    def _morton_order(self, p):
+        lay = self.layout
+        lo = torch.tensor(list(lay.lo), dtype=torch.float64, device=self.device)
+        c = torch.nan_to_num((p - lo) / lay.cell, nan=0.0).floor().clamp(-1.0, 1022.0).to(torch.int64) + 1          # 10 bits an axis
+        for shift, mask in ((16, 0x30000FF), (8, 0x300F00F), (4, 0x30C30C3), (2, 0x9249249)):
+            c = (c | (c << shift)) & mask
+        return torch.argsort((c[:, 0] << 2) | (c[:, 1] << 1) | c[:, 2])
+
+    def grid(self, origin, spacing, shape, band, dtype=np.float32, want_closest=False, want_face=False, out=None):
+        """The signed distance on the grid origin + idx * spacing (scalars or 3-vectors), shape (X, Y, Z): a contiguous device
+        volume of `dtype`; with a finite band the far vertices hold +-band, signed by the far fill (band >= max(spacing)).
+        Returns the volume, then the closest points (X, Y, Z, 3) float32 and / or the faces (X, Y, Z) int32 if asked for."""
+        shape = tuple(int(s) for s in shape)
+        if len(shape) != 3:
+            raise ValueError("shape must have three entries")
+        dt = torch_dtype(dtype)
+        if out is None:
+            if min(shape) < 1:
+                raise ValueError("shape entries must be at least 1")
+            out = torch.empty(shape, dtype=dt, device=self.device)
+        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.is_contiguous() and tuple(out.shape) == shape and out.dtype == dt):
+            raise ValueError("out must be a contiguous device tensor of the grid's shape and dtype")
+        g = _lib.MeshSdfGridParams()
+        g.origin = (_lib._dbl * 3)(*np.broadcast_to(np.asarray(origin, dtype=np.float64), (3,)))
+        g.spacing = (_lib._dbl * 3)(*np.broadcast_to(np.asarray(spacing, dtype=np.float64), (3,)))
+        g.shape = _lib.iarr(shape)
+        g.band, g.orientation, g.dtype, g.value = float(band), self.orientation, dtype_code(out), out.data_ptr()
+        with torch.cuda.device(self.device):
+            status = torch.empty(shape, dtype=torch.int8, device=self.device) if np.isfinite(band) else None
+            cl = torch.empty(shape + (3,), dtype=torch.float32, device=self.device) if want_closest else None
+            fc = torch.empty(shape, dtype=torch.int32, device=self.device) if want_face else None
+            g.status = status.data_ptr() if status is not None else None
+            g.closest = cl.data_ptr() if cl is not None else None
+            g.face = fc.data_ptr() if fc is not None else None
+            _lib.check(self.lib.dfh_mesh_sdf_grid(self._m, g, current_stream_ptr()), "dfh_mesh_sdf_grid")
+        extras = tuple(t for t in (cl, fc) if t is not None)
+        return (out,) + extras if extras else out
+
+
+
+def surface_distance(points, verts, faces):
+    """Unsigned distance (N,) float64 (device) from each point to the mesh's surface."""
+    return MeshDistance(verts, faces).query(points)[0].abs()
+
+
+def compare_meshes(verts_a, faces_a, verts_b, faces_b):
+    """Vertex-to-surface distances both ways: accuracy (A's vertices to B's surface) and completeness (B's vertices to A's
+    surface), each as mean, rms and max."""
+    def stats(d):
+        return {"mean": float(d.mean()), "rms": float(torch.sqrt((d * d).mean())), "max": float(d.max())}
+    va, _ = _mesh_arrays(verts_a, faces_a)
+    vb, _ = _mesh_arrays(verts_b, faces_b)
+    return {"accuracy": stats(surface_distance(va, verts_b, faces_b)), "completeness": stats(surface_distance(vb, verts_a, faces_a))}

@@ -1322,6 +1322,79 @@ int dfh_depth_halve(const void *const *depth, int n_views, int depth_dtype, int 
 size_t dfh_icp_track_bytes(int n_views);
 int dfh_icp_track(const dfh_icp_track_params *p, void *stream);
 
+/* ---- K22  mesh -> signed distance: exact point-to-mesh distance, closest point, face and pseudonormal sign --------------------
+ * No reference counterpart (the reference reads `.dist` files made by an external tool).  Vertices are fp64; all arithmetic is
+ * fp64 with ONE rounding per operation; dot(u, v) = (u0*v0 + u1*v1) + u2*v2; a comparison with a NaN is false.
+ *
+ * Closest point of P on one face (A, B, C), Ericson's walk.  ab = B - A, ac = C - A, ap = P - A, bp = P - B, cp = P - C;
+ *   d1 = dot(ab, ap), d2 = dot(ac, ap), d3 = dot(ab, bp), d4 = dot(ac, bp), d5 = dot(ab, cp), d6 = dot(ac, cp);
+ *   vc = d1*d4 - d3*d2, vb = d5*d2 - d1*d6, va = d3*d6 - d5*d4.  The first region that holds wins (feature id in brackets):
+ *   [0] d1 <= 0 and d2 <= 0: Q = A.            [1] d3 >= 0 and d4 <= d3: Q = B.
+ *   [3] vc <= 0, d1 >= 0, d3 <= 0: Q = A + (d1/(d1 - d3))*ab.            [2] d6 >= 0 and d5 <= d6: Q = C.
+ *   [4] vb <= 0, d2 >= 0, d6 <= 0: Q = A + (d2/(d2 - d6))*ac.
+ *   [5] va <= 0, d4 - d3 >= 0, d5 - d6 >= 0: Q = B + ((d4 - d3)/((d4 - d3) + (d5 - d6)))*(C - B).
+ *   [6] otherwise: den = 1/((va + vb) + vc), Q = (A + (vb*den)*ab) + (vc*den)*ac.
+ *   D2 = dot(P - Q, P - Q).
+ * Winner: the face with the smallest D2, the lowest index on ties, over the faces with keep[f] != 0 (the caller clears keep for
+ * the faces whose ab x ac is the exact zero vector).  A minimum over a set: no search order can change it.
+ * Sign: N = face_normals[f] (feature 6), edge_normals[f][feature - 3] (3..5) or vertex_normals[faces[f][feature]] (0..2), the
+ * caller's angle-weighted pseudonormal tables; the value is negative iff dot(P - Q, N)*orientation < 0 and D2 != 0; D2 == 0 gives
+ * +0.0.  Known iff D2 <= band*band (band = +inf: always).  Known: value = +-sqrt(D2) rounded once to the output type, closest = Q
+ * rounded to float32, face = the winner.  Far: face = -1, closest = NaN, value = +band (points).
+ * Grid vertex (i, j, k) is at origin_a + (double)idx_a*spacing_a; outputs are (X, Y, Z) row-major, z fastest.  Far fill (grids,
+ * finite band): three sweeps, along z, then y, then x.  Along each line an undecided (far) vertex takes the sign of the preceding
+ * decided vertex of the line, the vertices before the first decided one take that one's sign, a line with nothing decided is
+ * left to the next sweep; whatever is left after x is +.  A far vertex's value is +-band.
+ *
+ * dfh_mesh_sdf_plan (HOST arrays, no device work): checks the mesh and lays out the cell table -- the box of the kept faces, the
+ * cell edge (cell == 0: twice the mean face extent; never below extent/127, so that an axis has at most 128 cells), the entry
+ * count.  dfh_mesh_sdf_build fills the table on the device (count -> scan -> fill).  The queries then walk it shell by shell
+ * (csrc/dfh_mesh_sdf.hip has the proof of the stopping rule).  dfh_mesh_sdf_chunk: faces staged in LDS per evaluation pass.
+ * DFH_E_BADARG before any device work -- plan: a null array, n_faces == 0, a vertex index outside [0, n_verts), a vertex
+ * coordinate that is not finite, no kept face, cell negative or not finite, 2^31 entries or more; build and the queries: a null
+ * mesh or mesh array, a layout that is not plan's for these counts, a table smaller than layout.bytes; the queries: band not
+ * > 0 (NaN included), orientation not +-1, null points / sdist with n > 0, a null value, a bad dtype, a shape entry < 1, 2^31
+ * vertices or more, an origin that is not finite, a spacing not finite or <= 0, a finite band below max(spacing) or without
+ * the status workspace. */
+typedef struct dfh_mesh_sdf_layout {
+    double lo[3], hi[3];              /* box of the kept faces = the table's box */
+    double cell;                      /* cell edge in use */
+    double maxabs;                    /* largest |vertex coordinate| */
+    int dims[3];                      /* cells per axis, 1..128 */
+    long n_verts, n_faces, n_entries;
+    size_t bytes;                     /* of the device table */
+} dfh_mesh_sdf_layout;
+typedef struct dfh_mesh_sdf {
+    const double *verts;              /* DEVICE (n_verts, 3) */
+    const int *faces;                 /* DEVICE (n_faces, 3) */
+    const unsigned char *keep;        /* DEVICE (n_faces) */
+    const double *face_normals;       /* DEVICE (n_faces, 3) */
+    const double *edge_normals;       /* DEVICE (n_faces, 3, 3): local edges AB, AC, BC */
+    const double *vertex_normals;     /* DEVICE (n_verts, 3) */
+    long n_verts, n_faces;
+    void *table;                      /* DEVICE, layout.bytes */
+    size_t table_bytes;
+    dfh_mesh_sdf_layout layout;       /* dfh_mesh_sdf_plan's */
+} dfh_mesh_sdf;
+typedef struct dfh_mesh_sdf_grid_params {
+    double origin[3], spacing[3];
+    int shape[3];
+    double band;                      /* > 0 or +inf */
+    int orientation;                  /* +1: faces wind outward */
+    int dtype;                        /* DFH_F32 / DFH_F64 of value */
+    void *value;                      /* DEVICE (X, Y, Z) */
+    signed char *status;              /* DEVICE (X, Y, Z) workspace, needed with a finite band */
+    float *closest;                   /* DEVICE (X, Y, Z, 3) or NULL */
+    int *face;                        /* DEVICE (X, Y, Z) or NULL */
+} dfh_mesh_sdf_grid_params;
+int dfh_mesh_sdf_chunk(void);
+int dfh_mesh_sdf_plan(const double *verts, long n_verts, const int *faces, const unsigned char *keep, long n_faces, double cell,
+                      dfh_mesh_sdf_layout *out);
+int dfh_mesh_sdf_build(const dfh_mesh_sdf *m, void *stream);
+int dfh_mesh_sdf_points(const dfh_mesh_sdf *m, const double *points, long n, double band, int orientation, double *sdist,
+                        float *closest, int *face, void *stream);
+int dfh_mesh_sdf_grid(const dfh_mesh_sdf *m, const dfh_mesh_sdf_grid_params *g, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
