@@ -5,8 +5,10 @@
 // T in voxel units as fuseDepths stores it) yields one sample -- the voxel centre moved onto the
 // zero level set along the TSDF gradient, with the normalised gradient as normal.  Three launches:
 // per-block counts, a single-block exclusive scan, ordered emission (samples come out in voxel
-// order [x][y][z], deterministically, with no atomics).
+// order [x][y][z], deterministically, with no atomics).  The scan's workgroup prefix sum is the
+// shared block_scan_exclusive of dfh_scan.h.
 #include "dfh_common.h"
+#include "dfh_scan.h"
 
 namespace dfh {
 
@@ -223,7 +225,8 @@ __global__ __launch_bounds__(256) void surface_emit_vec_kernel(const float *__re
 
 // Exclusive scan of the block counts in place, total -> *total_out and the sentinel block_count[nblocks].
 // Two launches: a workgroup scans ITS 4 096 counts from zero (a thread takes four consecutive ones with one 16-byte load, the
-// waves scan the threads' sums with six 32-bit shuffles, sixteen wave totals go through LDS) and leaves the chunk's total; then
+// waves scan the threads' sums with six 32-bit shuffles, sixteen wave totals go through LDS: dfh_scan.h's block_scan_exclusive,
+// under this kernel's own aligned 16-byte load and store) and leaves the chunk's total; then
 // every 256 counts add the sum of the chunk totals before theirs.  (Rounds 2-4 scanned 16 K counts per workgroup with sixteen
 // 64-bit shuffle scans per thread: 192 ds_bpermute per wave, 3 072 through ONE CU's LDS pipe -- 29 us at 256^3 where this takes
 // 5 + 4; a single workgroup walking a 512^3 volume's list took 235 us.  Tried with it and dropped: one wave per block, four
@@ -234,7 +237,7 @@ template <bool SINGLE>
 __global__ __launch_bounds__(1024) void surface_scan_chunk_kernel(int *__restrict__ block_count, int nblocks, long *__restrict__ chunk_tot,
                                                                    long *__restrict__ total_out) {
     __shared__ int wtot[16];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+    const int t = threadIdx.x;
     const long base = (long)blockIdx.x * kScanChunk + 4 * (long)t;
     int v[4] = {0, 0, 0, 0};
     if (base + 3 < nblocks && ((uintptr_t)block_count & 15) == 0) {
@@ -245,22 +248,8 @@ __global__ __launch_bounds__(1024) void surface_scan_chunk_kernel(int *__restric
         for (int j = 0; j < 4; ++j) v[j] = base + j < nblocks ? block_count[base + j] : 0;
     }
     const int sum = (v[0] + v[1]) + (v[2] + v[3]);      // (a chunk holds at most 4 096 x 1 024 samples: int is enough)
-    int x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wtot[wv] = x;
-    __syncthreads();
-    int off = 0, all = 0;
-#pragma unroll
-    for (int w_ = 0; w_ < 16; ++w_) {
-        const int q = wtot[w_];
-        off += w_ < wv ? q : 0;
-        all += q;
-    }
-    const int ex = off + x - sum;
+    int all;
+    const int ex = block_scan_exclusive<16>(sum, wtot, all);
     const int o4[4] = {ex, ex + v[0], ex + v[0] + v[1], ex + v[0] + v[1] + v[2]};
     if (base + 3 < nblocks && ((uintptr_t)block_count & 15) == 0) {
         *reinterpret_cast<int4 *>(block_count + base) = make_int4(o4[0], o4[1], o4[2], o4[3]);

@@ -35,6 +35,7 @@
 #include <cmath>
 
 #include "dfh_common.h"
+#include "dfh_scan.h"
 
 namespace dfh {
 
@@ -234,24 +235,15 @@ __global__ __launch_bounds__(256) void rs_count_kernel(const unsigned char *__re
     if (threadIdx.x == 0) blk[blockIdx.x] = cnt[0] + cnt[1] + cnt[2] + cnt[3];
 }
 
-// exclusive scan of blk[0..m) in place by one workgroup (thread t: a contiguous chunk), the sum to total and to the host word
+// exclusive scan of blk[0..m) in place by one workgroup (dfh_scan.h's block_scan_rounds), the sum to total and to the host word
 __global__ __launch_bounds__(1024) void rs_scan_kernel(long *__restrict__ blk, long m, long *__restrict__ total, long *__restrict__ total_host) {
-    __shared__ long part[1024];
-    const long chunk = (m + 1023) / 1024;
-    const long b0 = min(m, (long)threadIdx.x * chunk), b1 = min(m, b0 + chunk);
-    long s = 0;
-    for (long b = b0; b < b1; ++b) s += blk[b];
-    part[threadIdx.x] = s;
-    __syncthreads();
+    __shared__ long wtot[16];
+    const long sum = block_scan_rounds<16, 1, long>(
+        m, wtot, [&](long i) { return blk[i]; }, [&](long i, long at) { blk[i] = at; });
     if (threadIdx.x == 0) {
-        long run = 0;
-        for (int t = 0; t < 1024; ++t) { const long v = part[t]; part[t] = run; run += v; }
-        *total = run;
-        *total_host = run;
+        *total = sum;
+        *total_host = sum;
     }
-    __syncthreads();
-    long run = part[threadIdx.x];
-    for (long b = b0; b < b1; ++b) { const long v = blk[b]; blk[b] = run; run += v; }
 }
 
 __global__ __launch_bounds__(256) void rs_emit_kernel(const unsigned char *__restrict__ state, long n, const long *__restrict__ blk,

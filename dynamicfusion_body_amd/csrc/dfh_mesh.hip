@@ -21,8 +21,12 @@
 //   mc_active_kernel       compacted list of tiles that emit anything (the emit passes launch only those)
 //   mc_vertex_kernel       code[p] = crossing mask << 29 | index of p's first vertex; positions, normals
 //   mc_face_kernel         faces, looking up the owners' codes
+// Every prefix sum is a piece of dfh_scan.h: block_scan_exclusive under mc_scan_chunk's three fields
+// and the rank passes, wave_scan_exclusive inside a row of the emit passes, block_scan_rounds for
+// mc_scan1.
 #include "dfh_common.h"
 #include "dfh_mc_table.h"
+#include "dfh_scan.h"
 
 namespace dfh {
 
@@ -200,41 +204,7 @@ __device__ __forceinline__ int mc_tri_count(const McSigns &q) {
     return kept;
 }
 
-// exclusive scan of one int per thread over the 256-thread workgroup; *total = workgroup sum
-__device__ __forceinline__ int mc_block_scan(int v, int *lds /* 4 ints */, int *total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    if (lane == 63) lds[wave] = inc;
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kMcBlock / 64; ++w) {
-        const int t = lds[w];
-        before += w < wave ? t : 0;
-        tot += t;
-    }
-    __syncthreads();
-    *total = tot;
-    return before + inc - v;
-}
-
-// exclusive scan over the 64 lanes of a wave (no barrier); *total = wave sum
-__device__ __forceinline__ int mc_wave_scan(int v, int *total) {
-    const int lane = threadIdx.x & 63;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += t;
-    }
-    *total = __shfl(inc, 63, 64);
-    return inc - v;
-}
+constexpr int kMcWaves = kMcBlock / kWave;
 
 // 256-point segment `seg` of a row in the row's activity mask; segments beyond the 31st share bit 31.
 __device__ __forceinline__ unsigned mc_chunk_bit(int seg) { return 1u << (seg < 31 ? seg : 31); }
@@ -322,7 +292,7 @@ __global__ __launch_bounds__(kMcBlock) void mc_count_kernel(const VolT *__restri
 
 // entries[t] = {vertices, faces, active, -} -> exclusive prefixes inside the chunk; chunk sums to chunk_tot
 __global__ __launch_bounds__(kMcBlock) void mc_scan_chunk_kernel(uint4 *__restrict__ entries, long ntiles, uint4 *__restrict__ chunk_tot) {
-    __shared__ int lds[4];
+    __shared__ unsigned lds[kMcWaves];
     const long t0 = (long)blockIdx.x * kMcChunk + (long)threadIdx.x * 8;
     uint4 e[8];
     unsigned sv = 0, sf = 0, sa = 0;
@@ -333,14 +303,16 @@ __global__ __launch_bounds__(kMcBlock) void mc_scan_chunk_kernel(uint4 *__restri
         sv += e[j].x; sf += e[j].y; sa += e[j].z;
         e[j] = pre;
     }
-    int tv, tf, ta;
-    const unsigned bv = (unsigned)mc_block_scan((int)sv, lds, &tv);
-    const unsigned bf = (unsigned)mc_block_scan((int)sf, lds, &tf);
-    const unsigned ba = (unsigned)mc_block_scan((int)sa, lds, &ta);
+    unsigned tv, tf, ta;
+    const unsigned bv = block_scan_exclusive<kMcWaves>(sv, lds, tv);
+    __syncthreads();                                                  // lds is rewritten by the next field's scan
+    const unsigned bf = block_scan_exclusive<kMcWaves>(sf, lds, tf);
+    __syncthreads();
+    const unsigned ba = block_scan_exclusive<kMcWaves>(sa, lds, ta);
 #pragma unroll
     for (int j = 0; j < 8; ++j)
         if (t0 + j < ntiles) entries[t0 + j] = make_uint4(e[j].x + bv, e[j].y + bf, e[j].z + ba, e[j].w);
-    if (threadIdx.x == 0) chunk_tot[blockIdx.x] = make_uint4((unsigned)tv, (unsigned)tf, (unsigned)ta, 0u);
+    if (threadIdx.x == 0) chunk_tot[blockIdx.x] = make_uint4(tv, tf, ta, 0u);
 }
 
 // chunk totals -> exclusive prefixes (few hundred at most: one thread), grand totals {vertices, faces, active tiles}
@@ -451,7 +423,7 @@ __global__ __launch_bounds__(kMcBlock) void mc_vertex_kernel(const VolT *__restr
             for (int j = 0; j < 4; ++j) q[j].cross = 0u;
         }
         int tot;
-        int rank = mc_wave_scan(cnt, &tot);
+        int rank = wave_scan_exclusive(cnt, tot);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             if (z0 + j < p.NZ) code_row[z0 + j] = (q[j].cross << 29) | ((carry + (unsigned)rank) & kMcBaseMask);
@@ -499,7 +471,7 @@ __global__ __launch_bounds__(kMcBlock) void mc_face_kernel(const VolT *__restric
             for (int j = 0; j < 4; ++j) { nt[j] = mc_tri_count(q[j]); cnt += nt[j]; }
         }
         int tot;
-        int rank = mc_wave_scan(cnt, &tot);
+        int rank = wave_scan_exclusive(cnt, tot);
         if (tot == 0) continue;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -565,40 +537,16 @@ __global__ __launch_bounds__(256) void mc_rank_count_kernel(const int *__restric
         if (key < nkeys) c += first[mc_key_vertex(faces, key)] == (unsigned)key ? 1 : 0;
     }
     int tot;
-    mc_block_scan(c, lds, &tot);
+    block_scan_exclusive<4>(c, lds, tot);
     if (threadIdx.x == 0) bsum[blockIdx.x] = (unsigned)tot;
 }
 
 // exclusive scan of n unsigned values in place (one workgroup), *total = sum
 __global__ __launch_bounds__(1024) void mc_scan1_kernel(unsigned *__restrict__ a, long n, long *__restrict__ total) {
     __shared__ unsigned long long wsum[16];
-    __shared__ unsigned long long carry;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry = 0ull;
-    __syncthreads();
-    for (long base = 0; base < n; base += 1024) {
-        const long b = base + threadIdx.x;
-        const unsigned long long v = b < n ? a[b] : 0u;
-        unsigned long long inc = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long t = __shfl_up(inc, o, 64);
-            if (lane >= o) inc += t;
-        }
-        if (lane == 63) wsum[wave] = inc;
-        __syncthreads();
-        unsigned long long before = carry;
-        for (int w = 0; w < wave; ++w) before += wsum[w];
-        if (b < n) a[b] = (unsigned)(before + inc - v);
-        __syncthreads();
-        if (threadIdx.x == 1023) {
-            unsigned long long tot = carry;
-            for (int w = 0; w < 16; ++w) tot += wsum[w];
-            carry = tot;
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) *total = (long)carry;
+    const unsigned long long sum = block_scan_rounds<16, 1, unsigned long long>(
+        n, wsum, [&](long i) { return a[i]; }, [&](long i, unsigned long long at) { a[i] = (unsigned)at; });
+    if (threadIdx.x == 0) *total = (long)sum;
 }
 
 __global__ __launch_bounds__(256) void mc_rank_apply_kernel(const int *__restrict__ faces, long nkeys,
@@ -618,7 +566,7 @@ __global__ __launch_bounds__(256) void mc_rank_apply_kernel(const int *__restric
         c += flag[j];
     }
     int tot;
-    unsigned rank = boff[blockIdx.x] + (unsigned)mc_block_scan(c, lds, &tot);
+    unsigned rank = boff[blockIdx.x] + (unsigned)block_scan_exclusive<4>(c, lds, tot);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         if (flag[j]) newid[v[j]] = rank++;

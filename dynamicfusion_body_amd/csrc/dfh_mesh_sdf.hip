@@ -3,9 +3,9 @@
 // reference reads `.dist` files, this makes what goes inside.  The result is written out operation by operation in
 // include/dfusion_hip.h; tests/mesh_sdf_np.py restates it by brute force over all faces and agrees bit for bit.
 //
-// Shape.  A uniform cell table over the mesh's box (count -> scan -> fill; every kept face is listed in every cell its box
-// overlaps, each entry with its cell's z index).  One wave (= one workgroup) owns 64 query points: a 4 x 4 x 4 block of grid
-// vertices or 64 consecutive points.  It walks the cells around its block shell by shell; the lanes read the entries of a run of
+// Shape.  A uniform cell table over the mesh's box (count -> scan -> fill, the scan being dfh_scan.h's; every kept face is
+// listed in every cell its box overlaps, each entry with its cell's z index).  One wave (= one workgroup) owns 64 query
+// points: a 4 x 4 x 4 block of grid vertices or 64 consecutive points.  It walks the cells around its block shell by shell; the lanes read the entries of a run of
 // cells, keep each face once (below), stage the kept faces' nine coordinates in LDS (kMsdChunk faces: 4.75 KB a wave) and then
 // every lane evaluates every staged face (one IEEE division a face: the region is chosen first, then ONE quotient is formed).
 // The winner is a minimum over a set under a total order (d2, then face index), so neither the order of the entries in a cell
@@ -45,6 +45,7 @@
 #include <cmath>
 
 #include "dfh_common.h"
+#include "dfh_scan.h"
 
 namespace dfh {
 
@@ -110,29 +111,13 @@ __global__ __launch_bounds__(256) void msd_bin_kernel(MsdTable t, const double *
             }
 }
 
-// exclusive scan of cursor[0..nc) into cell_start[0..nc] and back into cursor (one workgroup: the table has at most 2^21 cells)
+// exclusive scan of cursor[0..nc) into cell_start[0..nc] and back into cursor (one workgroup: the table has at most 2^21 cells,
+// 256 rounds of dfh_scan.h's block_scan_rounds at eight cells a thread)
 __global__ __launch_bounds__(1024) void msd_scan_kernel(MsdTable t, long nc) {
-    __shared__ int part[1024];
-    const int tid = threadIdx.x;
-    const long per = (nc + 1023) / 1024, b = tid * per, e = b + per < nc ? b + per : nc;
-    int s = 0;
-    for (long i = b; i < e; ++i) s += t.cursor[i];
-    part[tid] = s;
-    __syncthreads();
-    for (int d = 1; d < 1024; d <<= 1) {
-        const int v = tid >= d ? part[tid - d] : 0;
-        __syncthreads();
-        part[tid] += v;
-        __syncthreads();
-    }
-    int run = part[tid] - s;
-    for (long i = b; i < e; ++i) {
-        const int c = t.cursor[i];
-        t.cell_start[i] = run;
-        t.cursor[i] = run;
-        run += c;
-    }
-    if (tid == 1023) t.cell_start[nc] = part[1023];
+    __shared__ int wtot[16];
+    const int sum = block_scan_rounds<16, 8, int>(
+        nc, wtot, [&](long i) { return t.cursor[i]; }, [&](long i, int at) { t.cell_start[i] = at; t.cursor[i] = at; });
+    if (threadIdx.x == 0) t.cell_start[nc] = sum;
 }
 
 // ---- the query ------------------------------------------------------------------------------------------------------------

@@ -3,8 +3,10 @@
 // (row, slot) entries that contribute to it).  The host used to assemble all this from ~35 torch launches per frame
 // (pack, sort, cumsum, searchsorted, ...): host-bound at ~0.6 ms.  Here it is a handful of launches behind three C
 // entry points; the two key sorts are rocPRIM's device radix sort (stable, so every list comes out in ascending entry
-// order -- the fixed summation order the bit-reproducible build relies on), everything else is hand-written.
+// order -- the fixed summation order the bit-reproducible build relies on), everything else is hand-written; the two scans
+// (plan_scan_kernel, plan_scan2_kernel) are block_scan_rounds of dfh_scan.h.
 #include "dfh_common.h"
+#include "dfh_scan.h"
 
 #include <cstring>
 
@@ -92,29 +94,9 @@ __global__ __launch_bounds__(kPlanTile) void plan_heads_kernel(const int *__rest
 // exclusive scan of the tile counts in place (one workgroup; tile_rows[n_tiles] = total = *n_rows_out)
 __global__ __launch_bounds__(1024) void plan_scan_kernel(int *__restrict__ tile_rows, int n_tiles, int *__restrict__ n_rows_out) {
     __shared__ int wsum[16];
-    __shared__ int carry_s;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    for (int base = 0; base < n_tiles; base += 1024) {
-        const int i = base + threadIdx.x;
-        const int v = i < n_tiles ? tile_rows[i] : 0;
-        int x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wsum[wv] = x;
-        __syncthreads();
-        int off = carry_s;
-        for (int w = 0; w < wv; ++w) off += wsum[w];
-        if (i < n_tiles) tile_rows[i] = off + x - v;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = off + x;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { tile_rows[n_tiles] = carry_s; *n_rows_out = carry_s; }
+    const int sum = block_scan_rounds<16, 1, int>(
+        n_tiles, wsum, [&](int i) { return tile_rows[i]; }, [&](int i, int at) { tile_rows[i] = at; });
+    if (threadIdx.x == 0) { tile_rows[n_tiles] = sum; *n_rows_out = sum; }
 }
 
 // run_id of every sample and the first sample of every row
@@ -210,51 +192,18 @@ __global__ __launch_bounds__(256) void plan_zero2_kernel(int *__restrict__ a, in
 __global__ void plan_flag_out_kernel(const int *__restrict__ flag_in, int *__restrict__ flag_out) { *flag_out = *flag_in; }
 
 // exclusive scans of the two count arrays in place (workgroup 0: a[0..na), total to a[na]; workgroup 1: b likewise).
-// Every thread takes a contiguous chunk of up to 16 counts (one pass for up to 16 K lists, three barriers; more lists: rounds).
+// Every thread takes a contiguous chunk of up to 16 counts (dfh_scan.h's block_scan_rounds: one round for up to 16 K lists).
 // flag_in -> *flag_out: the "pattern must grow" flag of the launch before (set there by atomics, in the workspace) goes to the
 // caller's word by ONE plain store, so that word may be pinned host memory the host spins on.
 __global__ __launch_bounds__(1024) void plan_scan2_kernel(int *__restrict__ a, int na, int *__restrict__ b, int nb,
                                                            const int *__restrict__ flag_in, int *__restrict__ flag_out) {
     __shared__ int wsum[16];
-    __shared__ int carry_s;
     if (blockIdx.x == 0 && threadIdx.x == 0) *flag_out = *flag_in;
     int *v_ = blockIdx.x == 0 ? a : b;
     const int n = blockIdx.x == 0 ? na : nb;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    if (threadIdx.x == 0) carry_s = 0;
-    __syncthreads();
-    constexpr int C = 16;
-    for (int base = 0; base < n; base += 1024 * C) {
-        const int per = min(C, (min(n - base, 1024 * C) + 1023) / 1024);       // counts per thread in this round
-        const int i0 = base + (int)threadIdx.x * per;
-        int v[C];
-        int sum = 0;
-#pragma unroll
-        for (int j = 0; j < C; ++j) {
-            v[j] = (j < per && i0 + j < n) ? v_[i0 + j] : 0;
-            sum += v[j];
-        }
-        int x = sum;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wsum[wv] = x;
-        __syncthreads();
-        int off = carry_s;
-        for (int w = 0; w < wv; ++w) off += wsum[w];
-        int run = off + x - sum;
-#pragma unroll
-        for (int j = 0; j < C; ++j) {
-            if (j < per && i0 + j < n) v_[i0 + j] = run;
-            run += v[j];
-        }
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = off + x;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) v_[n] = carry_s;
+    const int sum = block_scan_rounds<16, 16, int>(
+        n, wsum, [&](int i) { return v_[i]; }, [&](int i, int at) { v_[i] = at; });
+    if (threadIdx.x == 0) v_[n] = sum;
 }
 
 // every entry to its slot: ent[ptr[key] + rank]

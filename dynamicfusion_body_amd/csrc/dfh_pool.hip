@@ -5,8 +5,9 @@
 // Launch sequence, no host synchronisation, no floating-point atomic:
 //   pool_count_kernel      one lane per pixel: slot[p] = cnt[v]++ (integer atomic; the COUNT does not depend on the order, the
 //                          slots of a vertex's pixels are 0 .. cnt[v] - 1 in the order the schedule chose)
-//   pool_scan_kernel       a workgroup scans kPoolScanChunk counts from zero and leaves the chunk's total
-//   pool_scan_top_kernel   ONE workgroup scans the chunk totals: vertex v's segment starts at chunk_base[v / chunk] + local[v]
+//   scan_chunks_kernel     (dfh_scan.h) a workgroup scans kPoolScanChunk counts from zero and leaves the chunk's total
+//   scan_chunk_totals_kernel  (dfh_scan.h) ONE workgroup scans the chunk totals: vertex v's segment starts at
+//                          chunk_base[v / chunk] + local[v]
 //   pool_scatter_kernel    one lane per pixel: its index goes to its slot of its vertex's segment (no second atomic) -- the
 //                          segment now holds the right SET of pixels in an order the schedule chose
 //   pool_order_kernel      one wave per vertex: a segment of up to kPoolCap entries is ordered in LDS by counting, for every
@@ -14,12 +15,14 @@
 //                          segment's vertex goes onto a list
 //   pool_order_big_kernel  a fixed grid pulls the listed vertices; a workgroup finds the segment's smallest and largest pixel,
 //                          walks vid[] over that range in order and writes the matching indices as it meets them (an ordered
-//                          compaction: correct for any length, one vertex may own every pixel)
+//                          compaction through dfh_scan.h's block_scan_exclusive: correct for any length, one vertex may own
+//                          every pixel)
 //   pool_sum_kernel        `dim` lanes per vertex, lane c owns channel c: every 4 * dim-byte feature row is read by one group
 //                          of adjacent lanes, the additions of a channel are one lane's chain
 #include <cstdint>
 
 #include "dfh_common.h"
+#include "dfh_scan.h"
 
 namespace dfh {
 
@@ -67,68 +70,9 @@ __global__ __launch_bounds__(kPoolBlock) void pool_count_kernel(const int *__res
     if (v >= 0 && v < n_verts) slot[p] = atomicAdd(cnt + v, 1);
 }
 
-// local[v] = pixels of the vertices of v's chunk in front of v; chunk_tot[chunk] = pixels of the chunk (all < 2^31: n_pixels is)
-__global__ __launch_bounds__(kPoolBlock) void pool_scan_kernel(const int *__restrict__ cnt, long n_verts, int *__restrict__ local,
-                                                               int *__restrict__ chunk_tot) {
-    __shared__ int wtot[kPoolWaves];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const long base = (long)blockIdx.x * kPoolScanChunk + 4 * (long)t;
-    int v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = base + j < n_verts ? cnt[base + j] : 0;
-    const int sum = (v[0] + v[1]) + (v[2] + v[3]);
-    int x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wtot[wv] = x;
-    __syncthreads();
-    int off = 0, all = 0;
-#pragma unroll
-    for (int w_ = 0; w_ < kPoolWaves; ++w_) {
-        const int n = wtot[w_];
-        off += w_ < wv ? n : 0;
-        all += n;
-    }
-    const int ex = off + x - sum;
-    const int o4[4] = {ex, ex + v[0], ex + v[0] + v[1], ex + v[0] + v[1] + v[2]};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (base + j < n_verts) local[base + j] = o4[j];
-    if (t == 0) chunk_tot[blockIdx.x] = all;
-}
-
-// chunk_base[c] = pixels in front of chunk c (256 chunks a round, in order)
-__global__ __launch_bounds__(kPoolBlock) void pool_scan_top_kernel(const int *__restrict__ chunk_tot, long nchunks,
-                                                                   int *__restrict__ chunk_base) {
-    __shared__ int wtot[kPoolWaves];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    int carry = 0;
-    for (long first = 0; first < nchunks; first += kPoolBlock) {
-        const long i = first + t;
-        const int v = i < nchunks ? chunk_tot[i] : 0;
-        int x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wtot[wv] = x;
-        __syncthreads();
-        int off = 0, all = 0;
-#pragma unroll
-        for (int w_ = 0; w_ < kPoolWaves; ++w_) {
-            const int n = wtot[w_];
-            off += w_ < wv ? n : 0;
-            all += n;
-        }
-        if (i < nchunks) chunk_base[i] = carry + off + x - v;
-        carry += all;
-        __syncthreads();                                 // wtot is rewritten by the next round
-    }
-}
+// The segment starts: dfh_scan.h's two-level pair.  local[v] = pixels of the vertices of v's chunk in front of v, chunk_tot[chunk] =
+// pixels of the chunk, chunk_base[c] = pixels in front of chunk c (all < 2^31: n_pixels is)
+static_assert(kPoolScanChunk == 4 * kPoolBlock, "scan_chunks_kernel takes four counts a thread");
 
 __global__ __launch_bounds__(kPoolBlock) void pool_scatter_kernel(const int *__restrict__ vid, long n_pixels, long n_verts, PoolSegs segs,
                                                                   const int *__restrict__ slot, int *__restrict__ list) {
@@ -210,21 +154,9 @@ __global__ __launch_bounds__(kPoolBlock) void pool_order_big_kernel(const int *_
                 m[j] = p0 + j <= hi && vid[p0 + j] == v;
                 c += m[j];
             }
-            int x = c;
-#pragma unroll
-            for (int o = 1; o < 64; o <<= 1) {
-                const int y = __shfl_up(x, o, 64);
-                if (lane >= o) x += y;
-            }
-            if (lane == 63) wcnt[wv] = x;
-            __syncthreads();
-            int off = 0, all = 0;
-#pragma unroll
-            for (int w_ = 0; w_ < kPoolWaves; ++w_) {
-                off += w_ < wv ? wcnt[w_] : 0;
-                all += wcnt[w_];
-            }
-            int at = s + run + off + x - c;
+            int all;
+            const int off = block_scan_exclusive<kPoolWaves>(c, wcnt, all);
+            int at = s + run + off;
 #pragma unroll
             for (int j = 0; j < 4; ++j)
                 if (m[j]) list[at++] = (int)(p0 + j);
@@ -323,8 +255,10 @@ int dfh_pool_features(const int *vid, const float *feat, long n_pixels, int dim,
     const dim3 block(kPoolBlock);
     const dim3 pix_grid((unsigned)((n_pixels + kPoolBlock - 1) / kPoolBlock));
     hipLaunchKernelGGL(pool_count_kernel, pix_grid, block, 0, s, vid, n_pixels, n_verts, cnt_out, slot);
-    hipLaunchKernelGGL(pool_scan_kernel, dim3((unsigned)L.nchunks), block, 0, s, (const int *)cnt_out, n_verts, local, chunk_tot);
-    hipLaunchKernelGGL(pool_scan_top_kernel, dim3(1), block, 0, s, (const int *)chunk_tot, L.nchunks, chunk_base);
+    hipLaunchKernelGGL((scan_chunks_kernel<int, int, kPoolWaves>), dim3((unsigned)L.nchunks), block, 0, s, (const int *)cnt_out, n_verts, local,
+                       chunk_tot);
+    hipLaunchKernelGGL((scan_chunk_totals_kernel<int, kPoolWaves>), dim3(1), block, 0, s, (const int *)chunk_tot, L.nchunks, chunk_base,
+                       (int *)nullptr);
     hipLaunchKernelGGL(pool_scatter_kernel, pix_grid, block, 0, s, vid, n_pixels, n_verts, segs, (const int *)slot, list);
     hipLaunchKernelGGL(pool_order_kernel, dim3((unsigned)((n_verts + kPoolWaves - 1) / kPoolWaves)), block, 0, s, n_verts,
                        (const int *)cnt_out, segs, list, big_n, big);

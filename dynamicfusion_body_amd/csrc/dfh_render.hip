@@ -18,6 +18,7 @@
 // Everything that decides coverage and depth runs in fp64 with -ffp-contract=off, so the numpy restatement with the same
 // operation order gives the same bits.
 #include "dfh_common.h"
+#include "dfh_scan.h"
 
 #include <cmath>
 
@@ -259,8 +260,8 @@ static int render_params(const char *who, int nv, const double *K, const double 
 // empty yields one sample: attributes of the CANONICAL mesh interpolated perspective-correctly at the pixel with the winning
 // face's weights.  Work decomposition (ordered, no atomics -- the pattern of dfh_extract.hip):
 //   samples_count_kernel     a workgroup counts the non-empty keys of its kSamplesPix lattice pixels
-//   samples_scan_kernel      a workgroup scans kSamplesChunk of those counts from zero and leaves the chunk's total
-//   samples_scan_top_kernel  ONE workgroup scans the chunk totals (64-bit) and stores the count (one plain store)
+//   scan_chunks_kernel       (dfh_scan.h) a workgroup scans kSamplesChunk of those counts from zero and leaves the chunk's total
+//   scan_chunk_totals_kernel (dfh_scan.h) ONE workgroup scans the chunk totals (64-bit) and stores the count (one plain store)
 //   samples_compact_kernel   pass A: the count pass's walk again; every sample learns its rank, the subsample rule picks its
 //                            slot, and the kept samples' pixel indices go out -- pixel_out is both a result and pass B's list
 //   samples_emit_kernel      pass B: one lane per KEPT sample over that dense list (full waves where a fifth of the image is
@@ -310,72 +311,9 @@ __global__ __launch_bounds__(kRenderBlock) void samples_count_kernel(const unsig
     if (threadIdx.x == 0) block_cnt[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
-// block_off[b] = samples of the workgroups of b's chunk in front of b; chunk_tot[chunk] = samples of the chunk
-__global__ __launch_bounds__(kRenderBlock) void samples_scan_kernel(const int *__restrict__ block_cnt, int nblocks, int *__restrict__ block_off,
-                                                                    long *__restrict__ chunk_tot) {
-    __shared__ int wtot[4];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const long base = (long)blockIdx.x * kSamplesChunk + 4 * (long)t;
-    int v[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) v[j] = base + j < nblocks ? block_cnt[base + j] : 0;
-    const int sum = (v[0] + v[1]) + (v[2] + v[3]);
-    int x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) wtot[wv] = x;
-    __syncthreads();
-    int off = 0, all = 0;
-#pragma unroll
-    for (int w_ = 0; w_ < 4; ++w_) {
-        const int n = wtot[w_];
-        off += w_ < wv ? n : 0;
-        all += n;
-    }
-    const int ex = off + x - sum;
-    const int o4[4] = {ex, ex + v[0], ex + v[0] + v[1], ex + v[0] + v[1] + v[2]};
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (base + j < nblocks) block_off[base + j] = o4[j];
-    if (t == 0) chunk_tot[blockIdx.x] = (long)all;
-}
-
-// chunk_base[c] = samples in front of chunk c, chunk_base[nchunks] = *total_out = all of them (256 chunks a round, in order)
-__global__ __launch_bounds__(kRenderBlock) void samples_scan_top_kernel(const long *__restrict__ chunk_tot, int nchunks, long *__restrict__ chunk_base,
-                                                                        long *__restrict__ total_out) {
-    __shared__ long wtot[4];
-    const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    long carry = 0;
-    for (int first = 0; first < nchunks; first += kRenderBlock) {
-        const int i = first + t;
-        const long v = i < nchunks ? chunk_tot[i] : 0;
-        long x = v;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const long y = __shfl_up(x, o, 64);
-            if (lane >= o) x += y;
-        }
-        if (lane == 63) wtot[wv] = x;
-        __syncthreads();
-        long off = 0, all = 0;
-#pragma unroll
-        for (int w_ = 0; w_ < 4; ++w_) {
-            const long n = wtot[w_];
-            off += w_ < wv ? n : 0;
-            all += n;
-        }
-        if (i < nchunks) chunk_base[i] = carry + off + x - v;
-        carry += all;
-        __syncthreads();                                 // wtot is rewritten by the next round
-    }
-    if (t == 0) {
-        chunk_base[nchunks] = carry;
-        *total_out = carry;
-    }
-}
+// The scan is dfh_scan.h's two-level pair: block_off[b] = samples of the workgroups of b's chunk in front of b, chunk_tot[chunk] =
+// samples of the chunk, chunk_base[c] = samples in front of chunk c, chunk_base[nchunks] = *total_out = all of them
+static_assert(kSamplesChunk == 4 * kRenderBlock, "scan_chunks_kernel takes four counts a thread");
 
 __global__ __launch_bounds__(kRenderBlock) void samples_compact_kernel(const unsigned long long *__restrict__ keys, SampleLattice q,
                                                                        const int *__restrict__ block_cnt, const int *__restrict__ block_off,
@@ -610,10 +548,10 @@ int dfh_render_samples_count(int n_views, int H, int W, long n_faces, int stride
     const SamplesWorkspace sw = samples_workspace(q, scan_workspace);
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(samples_count_kernel, dim3((unsigned)sw.nblocks), dim3(kRenderBlock), 0, s, w.keys, q, sw.block_cnt);
-    hipLaunchKernelGGL(samples_scan_kernel, dim3((unsigned)sw.nchunks), dim3(kRenderBlock), 0, s, (const int *)sw.block_cnt, (int)sw.nblocks,
-                       sw.block_off, sw.chunk_tot);
-    hipLaunchKernelGGL(samples_scan_top_kernel, dim3(1), dim3(kRenderBlock), 0, s, (const long *)sw.chunk_tot, (int)sw.nchunks, sw.chunk_base,
-                       total_out);
+    hipLaunchKernelGGL((scan_chunks_kernel<int, long, kRenderBlock / kWave>), dim3((unsigned)sw.nchunks), dim3(kRenderBlock), 0, s,
+                       (const int *)sw.block_cnt, (long)sw.nblocks, sw.block_off, sw.chunk_tot);
+    hipLaunchKernelGGL((scan_chunk_totals_kernel<long, kRenderBlock / kWave>), dim3(1), dim3(kRenderBlock), 0, s, (const long *)sw.chunk_tot,
+                       (long)sw.nchunks, sw.chunk_base, total_out);
     DFH_HIP_CHECK(hipGetLastError());
     return DFH_OK;
 }

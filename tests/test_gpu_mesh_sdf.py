@@ -213,6 +213,8 @@ def test_g9_against_the_restatement_and_the_stored_field():
     d = np.load(os.path.join(GOLDEN, "g9_mesh.npz"))
     v, f, sdf = d["verts"], d["faces"], d["sdf"]
     md = mesh.MeshDistance(v, f, orientation=+1)
+    n_cells = int(np.prod(list(md.layout.dims)))
+    assert n_cells > 4 * 8192 and n_cells % 1024 != 0          # the table's scan: several rounds of 1 024 threads x 8 cells, a ragged last one
     vol, cl, fc = md.grid(0.0, 1.0, (65, 65, 65), 3.0, want_closest=True, want_face=True)
     idx = np.random.RandomState(65).choice(65 ** 3, 4096, replace=False)
     P = np.stack(np.unravel_index(idx, (65, 65, 65)), 1).astype(np.float64)

@@ -64,6 +64,16 @@ def test_sizes_at_the_kernels_edges(dim):
         assert (cnt == 0).any() and (cnt > 1).any()
 
 
+def test_more_scan_chunks_than_one_round_of_the_top_scan():
+    """The scan of the chunk totals takes PIX chunks a round and carries their sum into the next: one chunk beyond a round."""
+    rng = np.random.default_rng(77)
+    n_verts = PIX * SCAN + 5
+    vid = rng.integers(-1, n_verts, size=n_verts).astype(np.int32)
+    vid[[3, n_verts // 2]] = n_verts - 1                               # a segment of the last chunk: it starts behind the carry
+    _, cnt = check(vid, wide(rng, (n_verts, 1)), n_verts, ("top scan", n_verts))
+    assert (cnt == 0).any() and (cnt > 1).any() and cnt[-1] >= 2
+
+
 def test_ids_that_are_no_vertex():
     rng = np.random.default_rng(5)
     n, n_verts, dim = 3000, 40, 16

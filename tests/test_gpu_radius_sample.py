@@ -131,6 +131,22 @@ def test_uniform_cloud():
     assert 900 <= len(gi) <= 1300
 
 
+def test_more_blocks_than_one_round_of_the_output_scan():
+    """The output's count / scan / emit counts 256 points a block and scans 1 024 blocks a round: 1 026 blocks here.  The points
+    are runs of identical points at 150 sites far apart, so the selection is the first point of every run: indices in blocks on
+    both sides of the round's edge (and of every wave's edge), most blocks empty, and only 150 steps of the host loop."""
+    rng = np.random.default_rng(31)
+    n, sites = 1024 * 256 + 300, 150
+    starts = np.concatenate([[0], np.sort(rng.choice(np.arange(1, n - 300), size=sites - 2, replace=False)), [n - 7]])
+    site_pos = 10.0 * np.stack(np.unravel_index(rng.permutation(216)[:sites], (6, 6, 6)), -1)
+    p = np.repeat(site_pos, np.diff(np.concatenate([starts, [n]])), axis=0)
+    assert p.shape == (n, 3) and (starts >= 1024 * 256).any()
+    gi = _equal_to_host(p, 1.0)
+    assert np.array_equal(gi, starts)
+    idx, count, rounds, _ = _raw(p, 1.0)
+    assert count == sites and np.array_equal(idx, starts)
+
+
 # ---- 5. edges ------------------------------------------------------------------------------------------------------------------
 def test_one_point_and_identical_points():
     assert np.array_equal(_equal_to_host(np.array([[1.5, -2.0, 3.0]]), 0.7), [0])

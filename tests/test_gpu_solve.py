@@ -395,13 +395,10 @@ def test_planned_build_is_deterministic_and_matches_the_atomic_build(golden, mon
     assert float((s1 - s0).abs().max()) > 0                               # the regulariser really contributes
 
 
-def test_device_plan_builder_equals_the_torch_plan(monkeypatch):
-    """dfh_gn_sort_samples / dfh_gn_plan_count / dfh_gn_plan_build (run scan, block look-up, two stable radix sorts) against the
-    same bookkeeping assembled from torch ops: sample order, tuple keys, run ids, and all four CSR arrays, element for
-    element -- ragged sample counts, several tiles, a pattern that covers the pairs and one that does not; lists short enough
-    for the per-list sort's register and LDS networks and lists beyond them (five nodes, 800 000 samples)."""
-    rng = np.random.default_rng(11)
-    for N, k, S in ((40, 4, 1000), (300, 4, 70000), (9, 2, 257), (64, 3, 256), (5, 4, 800000)):   # the last: lists of thousands of entries
+def _device_and_torch_plans_agree(rng, cases):
+    """Every (nodes, knn, samples) of `cases` planned by the device builder and by torch ops: everything equal, element for
+    element.  Returns the last case's block count."""
+    for N, k, S in cases:
         npos = rng.uniform(0, 60, size=(N, 3)); nw = rng.uniform(3, 6, size=N)
         ndq = np.tile(np.array([1.0, 0, 0, 0, 0, 0, 0, 0]), (N, 1))
         pts = rng.uniform(0, 60, size=(S, 3)); nrm = rng.normal(size=(S, 3))
@@ -431,6 +428,24 @@ def test_device_plan_builder_equals_the_torch_plan(monkeypatch):
             sv.build(np.array([1.0, 0, 0, 0, 0, 0, 0, 0]), 0.5)
         assert a.B == b.B and torch.equal(a.col, b.col) and torch.equal(a.blk_ent, b.blk_ent) and torch.equal(a.vals, b.vals)
     _lib.set_option("py_plan_torch", None)
+    return a.B
+
+
+def test_device_plan_builder_equals_the_torch_plan(monkeypatch):
+    """dfh_gn_sort_samples / dfh_gn_plan_count / dfh_gn_plan_build (run scan, block look-up, two stable radix sorts) against the
+    same bookkeeping assembled from torch ops: sample order, tuple keys, run ids, and all four CSR arrays, element for
+    element -- ragged sample counts, several tiles, a pattern that covers the pairs and one that does not; lists short enough
+    for the per-list sort's register and LDS networks and lists beyond them (five nodes, 800 000 samples)."""
+    _device_and_torch_plans_agree(np.random.default_rng(11),
+                                  ((40, 4, 1000), (300, 4, 70000), (9, 2, 257), (64, 3, 256), (5, 4, 800000)))   # the last: lists of thousands of entries
+
+
+def test_device_plan_builder_beyond_one_round_of_the_list_scan():
+    """More block lists than one round of plan_scan2_kernel takes (1 024 threads x 16 counts): the carry into its second round.
+    The diagonal and the graph's edges alone give 6 000 nodes at knn 4 that many blocks; the samples only have to put entries
+    into lists on both sides of the round's edge."""
+    n_blocks = _device_and_torch_plans_agree(np.random.default_rng(12), ((6000, 4, 3000),))
+    assert n_blocks > 16 * 1024
 
 
 def test_block_pattern_kept_across_sample_sets(golden):

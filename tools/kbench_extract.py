@@ -1,6 +1,8 @@
 """Band-voxel extraction (K9: dfh_surface_count / _emit) on the bench's canonical volume: HIP-event times of the count (+ scan)
 and the emit pass, and of the count with a band so narrow that no voxel lies in it (the pure streaming read).
-python3 tools/kbench_extract.py [--res 256] [--reps 20]"""
+--parent-lib PATH: count (+ scan) and emit through this build's library and through the parent commit's (tools/parent_lib.py): the
+total, the scanned block offsets and the samples compared bit for bit, then both timed, alternating, two rounds each.
+python3 tools/kbench_extract.py [--res 256] [--reps 20] [--parent-lib build_variants/parent.so]"""
 import argparse
 import os
 import sys
@@ -15,6 +17,7 @@ from dynamicfusion_body_amd.device import current_stream_ptr, dtype_code
 ap = argparse.ArgumentParser()
 ap.add_argument("--res", type=int, default=256)
 ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--parent-lib", default=None)
 a = ap.parse_args()
 R = a.res
 H, W, fx, cx, cy = scene.CAMERAS["C2" if R <= 256 else "C5"]
@@ -64,3 +67,13 @@ t_emit = timeit(emit)
 nb = (R ** 3 + 1023) // 1024
 print("%d^3: %d band samples (%.1f %% of the voxels); count + scan %.1f us (no voxel in the band: %.1f us = %.0f GB/s), emit %.1f us"
       % (R, S, 100.0 * S / R ** 3, t_count, t_empty, 8.0 * R ** 3 / t_empty / 1e3, t_emit))
+if a.parent_lib:
+    import parent_lib
+
+    def count_scan_emit(through):
+        global lib
+        lib = through
+        count(4.0)
+        emit()
+        return total, ws, pos, nrm
+    parent_lib.against_parent(print, "%d^3 count + scan + emit" % R, count_scan_emit, ["dfh_surface_count", "dfh_surface_emit"], a.parent_lib, a.reps)

@@ -8,7 +8,10 @@ itself is printed as min .. max):
   evaluation rate: a 1 280-face icosphere in ONE cell (cell larger than the mesh) on a 65^3 grid, band inf: there every lane
                    evaluates every face exactly once, so point-face evaluations = waves * 64 * faces is known without a counter
 and the host cost of building a MeshDistance (pseudonormal tables in numpy, the plan, the upload and the table build).
-usage: python tools/kbench_mesh_sdf.py [--reps 10] [--no-256] [--out FILE]"""
+--parent-lib PATH: config 3's table build (dfh_mesh_sdf_build) and the 256^3 grid behind it through this build's library and
+through the parent commit's (tools/parent_lib.py): cell starts, the .dist grid, closest points and faces compared bit for bit, then
+both timed, alternating, two rounds each.
+usage: python tools/kbench_mesh_sdf.py [--reps 10] [--no-256] [--parent-lib build_variants/parent.so] [--out FILE]"""
 import argparse
 import math
 import os
@@ -26,6 +29,7 @@ from dynamicfusion_body_amd import FusionDM, mesh, scene
 ap = argparse.ArgumentParser()
 ap.add_argument("--reps", type=int, default=10)
 ap.add_argument("--no-256", action="store_true")
+ap.add_argument("--parent-lib", default=None)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 lines = []
@@ -95,6 +99,22 @@ if not a.no_256:
     say("100k points, band 4   : %8.3f ms  (%.3f .. %.3f)" % timed(lambda: md3.query(P, 4.0)))
     near = torch.from_numpy(v[np.random.RandomState(1).randint(0, len(v), 100000)] + np.random.RandomState(2).normal(0, 2.0, (100000, 3))).cuda()
     say("100k points within ~2 voxels of the surface, band inf: %8.3f ms  (%.3f .. %.3f)" % timed(lambda: md3.query(near)))
+    if a.parent_lib:
+        import parent_lib
+        from dynamicfusion_body_amd import _lib
+        from dynamicfusion_body_amd.device import current_stream_ptr
+        n_cells = int(np.prod(list(md3.layout.dims)))
+
+        def build(lib):
+            _lib.check(lib.dfh_mesh_sdf_build(md3._m, current_stream_ptr()), "dfh_mesh_sdf_build")
+            return (md3._table.view(torch.int32)[:n_cells + 1],)
+
+        def build_and_grid(lib):
+            md3.lib = lib
+            return build(lib) + tuple(md3.grid(0.0, 1.0, (256, 256, 256), 4.0, out=out, want_closest=True, want_face=True))
+        names = ["dfh_mesh_sdf_build", "dfh_mesh_sdf_grid"]
+        parent_lib.against_parent(say, "config 3 table build, %d cells" % n_cells, build, names, a.parent_lib, a.reps)
+        parent_lib.against_parent(say, "config 3 table build + 256^3 grid", build_and_grid, names, a.parent_lib, max(3, a.reps // 2))
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mesh_sdf_cases as MC

@@ -11,7 +11,9 @@ still lacks the count and the division); the host loop of the restatement (tests
 
 Bytes of the pooling call, counted from its passes (n pixels, c of them covered, m vertices, D channels, 4-byte words):
 vid twice (count, scatter) 8 n; the counts and offsets as the passes read and write them 24 m; the slots written and read
-8 c; the pixel list written, ordered (read + written) and read 16 c; the covered feature rows 4 D c; the result 4 D m."""
+8 c; the pixel list written, ordered (read + written) and read 16 c; the covered feature rows 4 D c; the result 4 D m.
+--parent-lib PATH: the pooling call through this build's library and through the parent commit's (tools/parent_lib.py): features and
+counts compared bit for bit, then both timed, alternating, two rounds each."""
 import argparse
 import os
 import statistics
@@ -33,6 +35,7 @@ ap.add_argument("--size", type=int, default=512)
 ap.add_argument("--runs", type=int, default=20)
 ap.add_argument("--host-pixels", type=int, default=200000, help="pixels of the host loop (0: skip it)")
 ap.add_argument("--copy-gbs", type=float, default=0.0, help="the copy ceiling bench.py's micro-benchmark reports, for the share")
+ap.add_argument("--parent-lib", default=None)
 a = ap.parse_args()
 
 
@@ -110,6 +113,9 @@ def measure(R):
           % (R, n_verts, faces.shape[0], len(lws), S, S, D, covered, n, 100.0 * covered / n, 100.0 * float((c > 0).float().mean()),
              int(c[c > 0].median()), int(c.max()), *res["ids"], *res["pool"], nbytes / 1e6, rate, share, *res["index_add"], a.runs, same),
           flush=True)
+    if a.parent_lib:
+        import parent_lib
+        parent_lib.against_parent(print, "%d^3: pool_features" % R, lambda lib: pool(), ["dfh_pool_features"], a.parent_lib, a.runs)
     if a.host_pixels > 0:
         import pool_np as PN
         hv = flat_vid[sel[:a.host_pixels]].cpu().numpy()

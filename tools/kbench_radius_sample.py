@@ -5,7 +5,9 @@ Inputs: the |d| < 1 shells of a sphere in a 64^3 / 128^3 / 256^3 grid (voxel cen
 config-5 sample set (512^3, the 8-view orbit, band 4: the frame loop's band samples in canonical order; radius = the mean node
 spacing of 2 048 nodes).  Per input: graph.uniform_sample on the host (wall time) and dfh_radius_sample on the device (HIP
 events around the call, and wall time), host and device alternating, each the median of --runs runs; the index lists are
-compared.  --host-runs-c5 bounds the host runs of the config-5 set (minutes each); 0 skips them."""
+compared.  --host-runs-c5 bounds the host runs of the config-5 set (minutes each); 0 skips them.
+--parent-lib PATH: every input also through the parent commit's library (tools/parent_lib.py): count and indices compared, then both
+libraries timed, alternating, two rounds each."""
 import argparse
 import ctypes
 import os
@@ -25,6 +27,7 @@ ap.add_argument("--runs", type=int, default=10)
 ap.add_argument("--host-runs-c5", type=int, default=1)
 ap.add_argument("--no-c5", action="store_true")
 ap.add_argument("--shells", default="64,128,256")
+ap.add_argument("--parent-lib", default=None)
 a = ap.parse_args()
 
 
@@ -88,6 +91,13 @@ def measure(name, P, radius, runs, host_runs):
     print("%-12s n=%8d radius=%6.2f nodes=%5d rounds=%4d | device %9.3f ms (events) %9.3f ms (wall), median of %d | host %s | same indices: %s"
           % (name, n, radius, count, rounds, med(ev), med(wall), runs,
              "%10.1f ms, median of %d" % (med(host), len(host)) if host else "not run", same), flush=True)
+    if a.parent_lib:
+        import parent_lib
+
+        def call(through):
+            count = device_run(through, P, radius, ws, idx)[2]
+            return idx[:count], torch.tensor([count])
+        parent_lib.against_parent(print, name, call, ["dfh_radius_sample"], a.parent_lib, runs)
 
 
 for res in [int(x) for x in a.shells.split(",") if x]:

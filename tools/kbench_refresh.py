@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Where the per-frame sample refresh spends its time (256^3, band 4): extraction, k-NN, sort, pattern, plan."""
+"""Where the per-frame sample refresh spends its time (256^3, band 4): extraction, k-NN, sort, pattern, plan.
+--parent-lib PATH: the data + regulariser plan (dfh_gn_plan_count, dfh_gn_plan_build) through this build's library and through the
+parent commit's (tools/parent_lib.py): run ids, row heads and the eight CSR arrays compared, then both timed, alternating."""
 import os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -11,6 +13,7 @@ import argparse
 ap = argparse.ArgumentParser()
 ap.add_argument("--res", type=int, default=256)
 ap.add_argument("--nodes", type=int, default=512)
+ap.add_argument("--parent-lib", default=None)
 a = ap.parse_args()
 R = a.res
 H, W, fx, cx, cy = scene.CAMERAS["C2" if R <= 256 else "C5"]
@@ -41,3 +44,11 @@ ms, _ = t(lambda: sf.refresh_samples()); print("refresh total  %.3f ms" % ms)
 keys = sv._pattern_keys
 ms, _ = t(lambda: sv._build_plan(keys, reg=False)); print("  data plan (+ coverage flag) %.3f ms (rows=%d)" % (ms, sv.n_rows))
 ms, _ = t(lambda: sv._build_plan(keys)); print("  data + regulariser plan %.3f ms" % ms)
+if a.parent_lib:
+    import parent_lib
+
+    def plan(lib):
+        sv.lib = lib
+        sv._build_plan(keys)
+        return (sv.run_id, sv._row_first, sv.blk_ptr, sv.blk_ent, sv.node_ptr, sv.node_ent, sv.rblk_ptr, sv.rblk_ent, sv.rnode_ptr, sv.rnode_ent)
+    parent_lib.against_parent(print, "plan, %d samples" % sv.S, plan, ["dfh_gn_plan_count", "dfh_gn_plan_build"], a.parent_lib, 20)

@@ -10,7 +10,10 @@ mesh.depth_error(render_live, observed) over ten frames of the config-5 motion a
 tests/test_gpu_render_samples.py::test_slab_frame_moving_sequence_band_and_visible).
 --band: the band source's |T| bound in voxels at the two configs (default 4, SlabFrame's and the bench frame's; the tracking
 sequence keeps the frame tests' band of 2).
-usage: python tools/kbench_visible_samples.py [--configs 3,5] [--band 4] [--reps 20] [--no-tracking] [--out FILE]"""
+--parent-lib PATH: per config, mesh.render_samples at both strides with the count (its scan) and the emit pass through this
+build's library and through the parent commit's (tools/parent_lib.py): positions, normals and pixels compared bit for bit, then
+both timed, alternating, two rounds each.
+usage: python tools/kbench_visible_samples.py [--configs 3,5] [--band 4] [--reps 20] [--no-tracking] [--parent-lib PATH] [--out FILE]"""
 import argparse
 import os
 import statistics
@@ -33,6 +36,7 @@ ap.add_argument("--configs", default="3,5")
 ap.add_argument("--reps", type=int, default=20)
 ap.add_argument("--band", type=float, default=4.0)
 ap.add_argument("--no-tracking", action="store_true")
+ap.add_argument("--parent-lib", default=None)
 ap.add_argument("--out", default=None)
 a = ap.parse_args()
 lines = []
@@ -206,6 +210,16 @@ def time_config(cfg):
                     times[(name, rnd)].append(e0.elapsed_time(e1) * 1e3)
     for name, _ in VARIANTS:
         say("  step(), %-28s %9.1f %9.1f   (S = %d at the end)" % ((name,) + medians(times, name) + (counts[name],)))
+    if a.parent_lib:
+        import parent_lib
+        sf = frames["band"]
+        verts, faces, normals, _ = mesh.marching_cubes(sf.T, 0.0, 1)
+        wsp = mesh.render_workspace(len(lws), H, W, faces.shape[0])
+        for stride in (1, 2):
+            parent_lib.against_parent(say, "  render_samples /%d" % stride,
+                                      lambda lib: mesh.render_samples(verts, faces, verts, normals, sf.K, lws, H, W, sf.scale, sf.center, sf.R / 2,
+                                                                      stride=stride, workspace=wsp),
+                                      ["dfh_render_samples_count", "dfh_render_samples_emit"], a.parent_lib, a.reps)
 
 
 def tracking():

@@ -43,6 +43,42 @@ def pair_order(variants, rnd):
     return variants if rnd == 0 else [variants[i ^ 1] for i in range(len(variants))]
 
 
+def against_parent(say, what, call, names, path, reps=20):
+    """One workload through this build's library and through the parent's entry points `names`.  call(lib) runs it (kernels.* and
+    the other wrappers inside it go through `lib` too) and returns its outputs, a sequence of tensors (None entries are skipped).
+    The outputs are compared bit for bit; then both libraries are timed by HIP events around call(), alternating (pair_order), two
+    rounds of `reps` each after two warm repetitions, and judged by verdict().  Returns (identical, no slower)."""
+    import torch
+    here, parent = _lib.load(), open_parent(path, names)
+
+    def run(lib):
+        with through(lib):
+            return call(lib)
+
+    def raw(t):
+        return t.contiguous().reshape(-1).view(torch.uint8)
+    outs = []
+    for lib in (here, parent):
+        outs.append([t.clone() for t in run(lib) if t is not None])
+        torch.cuda.synchronize()
+    same = len(outs[0]) == len(outs[1]) and all(x.shape == y.shape and x.dtype == y.dtype and torch.equal(raw(x), raw(y)) for x, y in zip(*outs))
+    say("%s: %d outputs through this build's library and the parent's: %s" % (what, len(outs[0]), "identical" if same else "DIFFER"))
+    variants = [("this build", here), ("parent", parent)]
+    times = {(name, rnd): [] for name, _ in variants for rnd in (0, 1)}
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for rep in range(reps + 2):
+        for rnd in (0, 1):
+            for name, lib in pair_order(variants, rnd):
+                e0.record()
+                run(lib)
+                e1.record()
+                torch.cuda.synchronize()
+                if rep >= 2:
+                    times[(name, rnd)].append(e0.elapsed_time(e1) * 1e3)
+    med = {name: [statistics.median(times[(name, rnd)]) for rnd in (0, 1)] for name, _ in variants}
+    return same, verdict(say, what + " (us)", med["this build"], med["parent"])
+
+
 def verdict(say, name, here, parent):
     """here, parent: a variant's medians (two rounds each).  The bar is the parent's own spread: this build's median of its medians
     may not exceed the larger of the parent's."""
