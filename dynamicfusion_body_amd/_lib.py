@@ -304,6 +304,12 @@ _SIGNATURES = {
     "dfh_mesh_sdf_build": (_int, [ctypes.POINTER(MeshSdf), _vp]),
     "dfh_mesh_sdf_points": (_int, [ctypes.POINTER(MeshSdf), _vp, ctypes.c_long, _dbl, _int, _vp, _vp, _vp, _vp]),
     "dfh_mesh_sdf_grid": (_int, [ctypes.POINTER(MeshSdf), ctypes.POINTER(MeshSdfGridParams), _vp]),
+    "dfh_mesh_components_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long]),
+    "dfh_mesh_components": (_int, [_vp, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_long), _vp, ctypes.c_size_t, _vp]),
+    "dfh_mesh_component_table": (_int, [_vp, _int, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, _vp,
+                                        _vp, ctypes.c_size_t, _vp]),
+    "dfh_mesh_compact": (_int, [_vp, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, ctypes.c_long, _int, _vp, _vp, _vp,
+                                ctypes.POINTER(ctypes.c_long), _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

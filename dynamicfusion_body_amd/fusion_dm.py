@@ -65,6 +65,7 @@ class FusionDM:
         self._neighbor_look_up = []
         self._correspondences = []
         self._corridx = []
+        self.min_component_faces = None          # a number: marching_cubes() drops the components with fewer faces from the stored mesh
         self._vertices = None
         self._normals = None
         self._kdtree = None
@@ -248,7 +249,12 @@ class FusionDM:
         if tsdf is not None:
             return _mesh.marching_cubes(self._live_to_device(tsdf), None, step_size, as_numpy=True)
         self._ensure_volumes()
-        self._vertices, self._faces, self._normals, values = _mesh.marching_cubes(self._T, None, step_size, as_numpy=True)
+        if self.min_component_faces is None:
+            self._vertices, self._faces, self._normals, values = _mesh.marching_cubes(self._T, None, step_size, as_numpy=True)
+        else:                                    # the mesh without its fragments (mesh.filter_components), cleaned on the device
+            v, f, n, _ = _mesh.marching_cubes(self._T, None, step_size)
+            v, f, n, _ = _mesh.filter_components(v, f, n, min_faces=self.min_component_faces)
+            self._vertices, self._faces, self._normals = v.cpu().numpy(), f.cpu().numpy(), n.cpu().numpy()
         if self._verbose:
             print("Marching Cubes result: number of extracted vertices is %d" % (len(self._vertices)))
 

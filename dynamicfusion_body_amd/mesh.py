@@ -5,6 +5,8 @@
 has skimage's call shape: (verts, faces, normals, values), with `level=None` meaning
 (min + max) / 2 (skimage's documented default, which is what the reference's `marching_cubes()`
 gets since it passes no level)."""
+import ctypes
+
 import numpy as np
 import torch
 
@@ -508,3 +510,126 @@ def compare_meshes(verts_a, faces_a, verts_b, faces_b):
     va, _ = _mesh_arrays(verts_a, faces_a)
     vb, _ = _mesh_arrays(verts_b, faces_b)
     return {"accuracy": stats(surface_distance(va, verts_b, faces_b)), "completeness": stats(surface_distance(vb, verts_a, faces_a))}
+
+
+# ---------------------------------------------------------------------------------------------------------------- K23
+# Connected components of a mesh (csrc/dfh_mesh_components.hip; every output is defined in include/dfusion_hip.h): labels, the
+# per-component table and the compaction run on the device; which components to keep is decided from the table with torch.
+
+class MeshComponents:
+    """connected_components' result, CUDA tensors: n components; vert_comp (V,) / face_comp (F,) int32 component ids; per
+    component root, n_verts, n_faces (int32), area (float64), bbox_min / bbox_max ((n, 3) float64).  vert_root (V,) int32 is
+    the lowest vertex index of each vertex's component."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def _components_args(verts, faces):
+    v = verts if isinstance(verts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(verts))
+    f = faces if isinstance(faces, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(faces))
+    if v.dim() != 2 or v.shape[1] != 3 or v.dtype not in (torch.float32, torch.float64):
+        raise ValueError("verts must be (V, 3) float32 or float64")
+    if f.dim() != 2 or f.shape[1] != 3 or f.dtype not in (torch.int32, torch.int64):
+        raise ValueError("faces must be (F, 3) int32 or int64")
+    if f.dtype == torch.int64 and f.numel() and (int(f.min()) < -(1 << 31) or int(f.max()) >= (1 << 31)):
+        raise ValueError("faces hold an index that does not fit 32 bits")
+    require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return dev, v.to(dev).contiguous(), f.to(device=dev, dtype=torch.int32).contiguous()
+
+
+def _components_workspace(lib, V, F, dev):
+    nbytes = lib.dfh_mesh_components_workspace_bytes(V, F)
+    return torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+
+
+def _ptr(t):
+    return t.data_ptr() if t.numel() else None
+
+
+def connected_components(verts, faces):
+    """The connected components of a triangle mesh (two vertices are connected when a face names both): verts (V, 3) float32 /
+    float64, faces (F, 3) integer, numpy arrays or tensors (moved to the current device) -> MeshComponents.  Component ids run in
+    ascending order of the component's lowest vertex index; an unreferenced vertex is a component without faces.  A face index
+    outside [0, V) raises ValueError.  The call waits for the label pass (it reads the component count back)."""
+    lib = _lib.load()
+    dev, v, f = _components_args(verts, faces)
+    V, F = v.shape[0], f.shape[0]
+    with torch.cuda.device(dev):
+        ws = _components_workspace(lib, V, F, dev)
+        root = torch.empty(V, dtype=torch.int32, device=dev)
+        vert_comp = torch.empty(V, dtype=torch.int32, device=dev)
+        face_comp = torch.empty(F, dtype=torch.int32, device=dev)
+        n = ctypes.c_long(0)
+        _lib.check(lib.dfh_mesh_components(_ptr(f), V, F, _ptr(root), _ptr(vert_comp), _ptr(face_comp), ctypes.byref(n), _ptr(ws),
+                                           ws.numel() * 8, current_stream_ptr()), "dfh_mesh_components")
+        C = int(n.value)
+        croot = torch.empty(C, dtype=torch.int32, device=dev)
+        nv = torch.empty(C, dtype=torch.int32, device=dev)
+        nf = torch.empty(C, dtype=torch.int32, device=dev)
+        bmin = torch.empty((C, 3), dtype=torch.float64, device=dev)
+        bmax = torch.empty((C, 3), dtype=torch.float64, device=dev)
+        area = torch.empty(C, dtype=torch.float64, device=dev)
+        _lib.check(lib.dfh_mesh_component_table(_ptr(v), dtype_code(v), V, _ptr(f), F, _ptr(root), _ptr(vert_comp), _ptr(face_comp), C,
+                                                _ptr(croot), _ptr(nv), _ptr(nf), _ptr(bmin), _ptr(bmax), _ptr(area), _ptr(ws), ws.numel() * 8,
+                                                current_stream_ptr()), "dfh_mesh_component_table")
+    return MeshComponents(n=C, vert_comp=vert_comp, face_comp=face_comp, vert_root=root, root=croot, n_verts=nv, n_faces=nf, area=area,
+                          bbox_min=bmin, bbox_max=bmax, verts=v, faces=f)
+
+
+def compact_components(comps, keep, drop_unreferenced=True):
+    """The mesh of `comps` (a MeshComponents) cut down to the components with keep[c] != 0 ((n,) bool / uint8): (kept_vert_idx
+    (V',) int32 = the surviving vertices' old indices, ascending; vert_map (V,) int32 = old -> new index, -1 for a dropped vertex;
+    faces (F', 3) int32 = the surviving faces in their order, renumbered).  drop_unreferenced also removes the vertices of kept
+    components that no surviving face names.  The call waits for the device (it reads the two counts back)."""
+    lib = _lib.load()
+    f, dev = comps.faces, comps.faces.device
+    V, F, C = comps.vert_comp.shape[0], f.shape[0], comps.n
+    k = keep if isinstance(keep, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(keep))
+    k = (k.to(dev) != 0).to(torch.uint8).contiguous()
+    if tuple(k.shape) != (C,):
+        raise ValueError("keep must have one entry per component (%d), got shape %s" % (C, tuple(k.shape)))
+    with torch.cuda.device(dev):
+        ws = _components_workspace(lib, V, F, dev)
+        kept = torch.empty(V, dtype=torch.int32, device=dev)
+        vmap = torch.empty(V, dtype=torch.int32, device=dev)
+        fout = torch.empty((F, 3), dtype=torch.int32, device=dev)
+        counts = (ctypes.c_long * 2)(0, 0)
+        _lib.check(lib.dfh_mesh_compact(_ptr(f), V, F, _ptr(comps.vert_comp), _ptr(comps.face_comp), _ptr(k), C, int(bool(drop_unreferenced)),
+                                        _ptr(kept), _ptr(vmap), _ptr(fout), counts, _ptr(ws), ws.numel() * 8, current_stream_ptr()),
+                   "dfh_mesh_compact")
+    return kept[:counts[0]], vmap, fout[:counts[1]]
+
+
+def keep_mask(comps, min_faces=0, min_area=0.0, keep_largest=None):
+    """Which components filter_components keeps, (n,) bool on the device: n_faces >= min_faces, area not below min_area and, with
+    keep_largest = k, among the k components with the most faces (ties go to the lower id)."""
+    keep = (comps.n_faces >= int(min_faces)) & ~(comps.area < float(min_area))        # (a NaN area is not below the bound)
+    if keep_largest is not None:
+        k = int(keep_largest)
+        if k < 0:
+            raise ValueError("keep_largest must be >= 0, got %d" % k)
+        order = torch.sort(comps.n_faces, descending=True, stable=True).indices[:k]
+        top = torch.zeros_like(keep)
+        top[order] = True
+        keep = keep & top
+    return keep
+
+
+def filter_components(verts, faces, *attrs, min_faces=0, min_area=0.0, keep_largest=None, drop_unreferenced=True):
+    """Drop the fragments of a mesh: keeps the components keep_mask() selects and returns (verts, faces, *attrs, kept_vert_idx)
+    as CUDA tensors -- vertex and face order preserved, faces renumbered, every per-vertex attribute in `attrs` ((V, ...) arrays or
+    tensors: normals, values, colours, canonical positions) gathered with kept_vert_idx (int64 here, ready to index with).
+    drop_unreferenced also removes the vertices no surviving face names."""
+    comps = connected_components(verts, faces)
+    V = comps.vert_comp.shape[0]
+    kept, _, f2 = compact_components(comps, keep_mask(comps, min_faces, min_area, keep_largest), drop_unreferenced)
+    idx = kept.long()
+    out = []
+    for a in attrs:
+        t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+        if t.shape[0] != V:
+            raise ValueError("an attribute has %d rows for %d vertices" % (t.shape[0], V))
+        out.append(t.to(comps.verts.device)[idx])
+    return (comps.verts[idx], f2, *out, idx)

@@ -1395,6 +1395,58 @@ int dfh_mesh_sdf_points(const dfh_mesh_sdf *m, const double *points, long n, dou
                         float *closest, int *face, void *stream);
 int dfh_mesh_sdf_grid(const dfh_mesh_sdf *m, const dfh_mesh_sdf_grid_params *g, void *stream);
 
+/* ---- K23  mesh connected components: label, measure, compact --------------------------------------------------------------------
+ * No reference counterpart.  verts: DEVICE (V, 3) float32 or float64 (dtype DFH_F32 / DFH_F64; float32 is widened, exactly, before
+ * anything is computed); faces: DEVICE (F, 3) int32.  Every output is a function of the mesh alone: the order in which the
+ * kernels' integer atomics land shows in none of them.
+ *
+ * Connectivity.  Two vertices are connected when some face names both; components are the classes of the transitive closure; a
+ *   face belongs to the component of its vertices.  A degenerate face (a == b) still connects what it names, duplicate faces
+ *   count once each, a vertex that no face names is a component of its own with 0 faces.
+ * Labels.  root[v] = the lowest vertex index of v's component.  Component ids are 0 .. C-1 in ascending order of root:
+ *   vert_comp[v] = the number of roots below root[v], face_comp[f] = vert_comp[faces[f][0]].
+ * Table, per component c.  comp_root[c]; n_verts[c]; n_faces[c]; the box; the area.
+ *   Box.  key(x) for a double x that is not a NaN: its 64 bits b as an unsigned integer, ~b if the sign bit is set, else
+ *   b | 2^63 (so key(x) < key(y) <=> x < y, and -0.0 lies below +0.0).  bbox_min[c][a] = the coordinate with the smallest key
+ *   over the component's vertices, bbox_max[c][a] the one with the largest; if any of those coordinates is a NaN the entry is
+ *   the NaN with bits 0x7ff8000000000000.
+ *   Area of a face (A, B, C), fp64, one rounding per operation, no contraction: e1 = B - A, e2 = C - A; cx = e1y*e2z - e1z*e2y,
+ *   cy = e1z*e2x - e1x*e2z, cz = e1x*e2y - e1y*e2x (two rounded products and one subtraction each);
+ *   s = (cx*cx + cy*cy) + cz*cz; area = 0.5*sqrt(s).
+ *   Area of a component, the order of the additions.  Chunk j = the faces [256 j, 256 j + 256).  P(j, c) = the areas of chunk
+ *   j's faces of component c, added in ascending face index starting from the first.  area[c] = the P(j, c) of the chunks that
+ *   hold a face of c, added in ascending j starting from the first; +0.0 for a component without faces.  No float atomics.
+ *   Coordinates that are not finite reach the box and the area of their own component only: labels and counts read no coordinate.
+ * Compaction.  keep: DEVICE uint8 per component.  A face survives when keep[face_comp[f]] != 0.  A vertex survives when
+ *   keep[vert_comp[v]] != 0 and, with drop_unreferenced = 1, some surviving face names it.  kept_vert_idx: the surviving
+ *   vertices' old indices, ascending (V entries of room); vert_map[v] = the new index, -1 for a dropped vertex; faces_out: the
+ *   surviving faces in their original order, indices through vert_map (F x 3 of room).  counts_out: HOST long[2] = (vertices,
+ *   faces) that survive.  Per-vertex attributes are gathered by the caller with kept_vert_idx.
+ *
+ * workspace: dfh_mesh_components_workspace_bytes(V, F) bytes of device memory, 8-byte aligned, the same size for the three
+ * calls (0 for counts the calls refuse); its contents carry nothing from one call to the next.
+ * dfh_mesh_components and dfh_mesh_compact do not only enqueue: each queues its kernels on `stream`, synchronises `stream`, and
+ * has written n_components / counts_out (HOST pointers) when it returns -- the caller sizes what follows from them.  Like
+ * dfh_radius_sample they cannot be captured into a graph.  dfh_mesh_component_table only enqueues.
+ * Bad indices.  A face index outside [0, V) touches no memory: the face joins nothing, face_comp[f] = -1, a device flag is
+ * raised and dfh_mesh_components returns DFH_E_BADARG once it has synchronised (root / vert_comp then describe the mesh without
+ * those faces).  dfh_mesh_compact does the same for a face index outside [0, V) or a component id outside [0, C); the table
+ * call skips such faces and vertices.
+ * V == 0 or F == 0 are valid and launch nothing they do not need; V == 0 and F == 0 launches nothing.  DFH_E_BADARG before any
+ * HIP call: V or F negative or >= 2^31; C < 0 or C > V; a null n_components / counts_out; a null array of a non-zero count
+ * (keep with C > 0); a dtype other than DFH_F32 / DFH_F64; drop_unreferenced other than 0 / 1; a null workspace, one that is not
+ * 8-byte aligned or one smaller than dfh_mesh_components_workspace_bytes(V, F). */
+size_t dfh_mesh_components_workspace_bytes(long n_verts, long n_faces);
+int dfh_mesh_components(const int *faces, long n_verts, long n_faces, int *root, int *vert_comp, int *face_comp,
+                        long *n_components, void *workspace, size_t workspace_bytes, void *stream);
+int dfh_mesh_component_table(const void *verts, int dtype, long n_verts, const int *faces, long n_faces, const int *root,
+                             const int *vert_comp, const int *face_comp, long n_components, int *comp_root, int *comp_n_verts,
+                             int *comp_n_faces, double *bbox_min, double *bbox_max, double *area, void *workspace,
+                             size_t workspace_bytes, void *stream);
+int dfh_mesh_compact(const int *faces, long n_verts, long n_faces, const int *vert_comp, const int *face_comp,
+                     const unsigned char *keep, long n_components, int drop_unreferenced, int *kept_vert_idx, int *vert_map,
+                     int *faces_out, long *counts_out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
