@@ -310,6 +310,15 @@ _SIGNATURES = {
                                         _vp, ctypes.c_size_t, _vp]),
     "dfh_mesh_compact": (_int, [_vp, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, ctypes.c_long, _int, _vp, _vp, _vp,
                                 ctypes.POINTER(ctypes.c_long), _vp, ctypes.c_size_t, _vp]),
+    "dfh_mesh_simplify_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long]),
+    "dfh_mesh_simplify_keys": (_int, [_vp, _int, ctypes.c_long, _vp, ctypes.c_long, _dbl, _c_double_p, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dfh_mesh_simplify_group": (_int, [_vp, _vp, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_long), _vp,
+                                       ctypes.c_size_t, _vp]),
+    "dfh_mesh_simplify_clusters": (_int, [_vp, _int, ctypes.c_long, _vp, ctypes.c_long, _dbl, _c_double_p, _int, _dbl, _vp, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, ctypes.c_long, _vp, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dfh_mesh_simplify_attr": (_int, [_vp, _int, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, ctypes.c_long, _vp, _vp]),
+    "dfh_mesh_simplify_faces": (_int, [_vp, ctypes.c_long, ctypes.c_long, _vp, ctypes.c_long, _int, _vp, _vp, _vp, _vp, _vp,
+                                       ctypes.POINTER(ctypes.c_long), _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

@@ -54,6 +54,7 @@ class Fusion:
         self._correspondences = []
         self.landmark_weight = 0.0               # > 0: solve() also uses the correspondences as POINTS (WarpSolver.set_landmarks)
         self.min_component_faces = None          # a number: marching_cubes() drops the components with fewer faces from the stored mesh
+        self.simplify_cell = None                # a number: write_canonical_mesh() writes the mesh clustered at that cell size (voxels)
         self._vertices = None
         self._normals = None
         self._kdtree = None
@@ -587,6 +588,15 @@ class Fusion:
     def write_canonical_mesh(self, path, filename):
         """Reference core/fusion.py:577-587: index-space OBJ, `v` / `vn` / `f a b c` (1-based)."""
         self._ensure_volumes()
+        if self.simplify_cell is not None:   # a coarser file (mesh.simplify); the stored mesh and the graph are not touched
+            verts, faces, normals, _ = _mesh.marching_cubes(self._T, None, 1)
+            verts, faces, normals, _ = _mesh.simplify_with_normals(verts, faces, normals, self.simplify_cell)
+            colors = None
+            if self._C is not None:      # the colour volume sampled at the new vertices, not an average of the old colours
+                rgb, valid = kernels.sample_colors(self._C, verts.double())
+                colors = _mesh.obj_colors(rgb.cpu().numpy(), valid.cpu().numpy(), len(verts))
+            self._write_mesh_file(os.path.join(path, filename), verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), colors)
+            return
         if self._C is not None:          # vertex colours (not in the reference): the colour volume sampled at the vertices
             verts, faces, normals, values = _mesh.marching_cubes(self._T, None, 1)
             rgb, valid = kernels.sample_colors(self._C, verts.double())

@@ -66,6 +66,7 @@ class FusionDM:
         self._correspondences = []
         self._corridx = []
         self.min_component_faces = None          # a number: marching_cubes() drops the components with fewer faces from the stored mesh
+        self.simplify_cell = None                # a number: write_canonical_mesh() writes the mesh clustered at that cell size (voxels)
         self._vertices = None
         self._normals = None
         self._kdtree = None
@@ -299,6 +300,15 @@ class FusionDM:
         """OBJ file of the canonical surface in world coordinates; reference core/fusion_dm.py:339-354
         (level 0, step 1, degenerate faces dropped; `v` / `vn` / `f a//a b//b c//c`, 1-based)."""
         self._ensure_volumes()
+        if self.simplify_cell is not None:   # a coarser file (mesh.simplify); the stored mesh and the graph are not touched
+            verts, faces, normals, _ = _mesh.marching_cubes(self._T, 0.0, 1)
+            verts, faces, normals, _ = _mesh.simplify_with_normals(verts, faces, normals, self.simplify_cell)
+            extra = {}
+            if self._C is not None:      # the colour volume sampled at the new vertices, not an average of the old colours
+                rgb, valid = kernels.sample_colors(self._C, verts.double())
+                extra = dict(colors=rgb.cpu().numpy(), valid=valid.cpu().numpy())
+            _mesh.write_obj(os.path.join(path, filename), verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), ind=self._IND, **extra)
+            return
         if self._C is not None:          # vertex colours (not in the reference): the colour volume sampled at the vertices
             verts, faces, normals, values = _mesh.marching_cubes(self._T, 0.0, 1)
             rgb, valid = kernels.sample_colors(self._C, verts.double())

@@ -633,3 +633,99 @@ def filter_components(verts, faces, *attrs, min_faces=0, min_area=0.0, keep_larg
             raise ValueError("an attribute has %d rows for %d vertices" % (t.shape[0], V))
         out.append(t.to(comps.verts.device)[idx])
     return (comps.verts[idx], f2, *out, idx)
+
+
+# ---------------------------------------------------------------------------------------------------------------- K24
+# Simplification by vertex clustering with quadrics (csrc/dfh_mesh_simplify.hip; every output is defined in include/dfusion_hip.h).
+# The two groupings are stable torch.sorts (the int64 cell keys; the 3F corner entries by the vertex they name), plumbing as
+# graph.py's; keys, cluster ids, quadrics, the solve, the face tests and the compaction run in the kernels.
+
+_SIMPLIFY_MODES = {"quadric": 0, "mean": 1}
+
+
+def _simplify_attr(a, V):
+    t = a if isinstance(a, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(a))
+    if t.dtype not in (torch.float32, torch.float64):
+        raise ValueError("a per-vertex attribute must be float32 or float64, got %s" % t.dtype)
+    if t.dim() < 1 or t.shape[0] != V:
+        raise ValueError("an attribute has %d rows for %d vertices" % (t.shape[0] if t.dim() else 0, V))
+    return t
+
+
+def simplify(verts, faces, *attrs, cell, origin=None, mode="quadric", reg=1e-3, drop_unreferenced=True):
+    """A coarser mesh by vertex clustering: the vertices that share a cell of the grid (origin, cell) become one vertex -- the
+    minimiser of the cluster's summed face-plane quadric, regularised by reg towards the cluster's mean and kept inside the cell
+    (mode "quadric": sharp features survive), or the mean itself (mode "mean") -- faces are remapped, those that collapse or
+    repeat an earlier face's vertex triple are dropped.  verts (V, 3) float32 / float64, faces (F, 3) int32 / int64, numpy arrays
+    or tensors; attrs: per-vertex (V, ...) float32 / float64 arrays, averaged per cluster in fp64; origin: 3 numbers, default the
+    per-axis minimum of verts.  -> (verts', faces', *attrs', info) as CUDA tensors; info: vert_map (V,) int64 old vertex -> new
+    vertex (-1 where dropped), face_idx (F',) int64 old face indices, n_clusters (before drop_unreferenced removes the clusters no
+    surviving face names), n_fallback (the clusters whose quadric solve was refused and that took the mean).
+    The result is a function of the inputs alone, bit for bit.  It is not guaranteed manifold or consistently oriented where
+    sheets thinner than a cell collapse: two sides of a thin sheet become the same triangle twice, with opposite orientation, and
+    the one with the lower index survives.  A coordinate that is not finite, a vertex further than 2^21 cells from the origin (or
+    below it) and a face index outside [0, V) raise ValueError.  The call waits for the device three times (it reads counts)."""
+    if mode not in _SIMPLIFY_MODES:
+        raise ValueError("mode must be 'quadric' or 'mean', got %r" % (mode,))
+    cell, reg = float(cell), float(reg)
+    if not (np.isfinite(cell) and cell > 0.0):
+        raise ValueError("cell must be a finite number above 0, got %r" % cell)
+    if not (np.isfinite(reg) and reg >= 0.0):
+        raise ValueError("reg must be a finite number that is not negative, got %r" % reg)
+    V = verts.shape[0] if hasattr(verts, "shape") and len(verts.shape) else 0
+    attrs = [_simplify_attr(a, V) for a in attrs]
+    lib = _lib.load()
+    dev, v, f = _components_args(verts, faces)
+    V, F = v.shape[0], f.shape[0]
+    attrs = [a.to(dev).contiguous() for a in attrs]
+    if origin is None:
+        o = v.double().amin(dim=0).cpu().numpy() if V else np.zeros(3)
+    else:
+        o = np.asarray(origin, dtype=np.float64).reshape(-1)
+        if o.shape != (3,):
+            raise ValueError("origin must be 3 numbers")
+    org = (ctypes.c_double * 3)(*[float(x) for x in o])
+    i32 = lambda *shape: torch.empty(shape, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        stream = current_stream_ptr()
+        nbytes = lib.dfh_mesh_simplify_workspace_bytes(V, F)
+        ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+        wsb = ws.numel() * 8
+        keys = torch.empty(V, dtype=torch.int64, device=dev)
+        _lib.check(lib.dfh_mesh_simplify_keys(_ptr(v), dtype_code(v), V, _ptr(f), F, cell, org, _ptr(keys), _ptr(ws), wsb, stream),
+                   "dfh_mesh_simplify_keys")
+        skeys, order = torch.sort(keys, stable=True)
+        scv, corder = torch.sort(f.reshape(-1), stable=True)
+        vclus, cstart, ccount, cbeg, cend = i32(V), i32(V), i32(V), i32(V), i32(V)
+        n = ctypes.c_long(0)
+        _lib.check(lib.dfh_mesh_simplify_group(_ptr(skeys), _ptr(order), V, _ptr(scv), F, _ptr(vclus), _ptr(cstart), _ptr(ccount), _ptr(cbeg),
+                                               _ptr(cend), ctypes.byref(n), _ptr(ws), wsb, stream), "dfh_mesh_simplify_group")
+        C = int(n.value)
+        cverts = torch.empty((C, 3), dtype=v.dtype, device=dev)
+        nfb = torch.zeros(1, dtype=torch.int32, device=dev)
+        _lib.check(lib.dfh_mesh_simplify_clusters(_ptr(v), dtype_code(v), V, _ptr(f), F, cell, org, _SIMPLIFY_MODES[mode], reg, _ptr(keys),
+                                                  _ptr(order), _ptr(corder), _ptr(cbeg), _ptr(cend), _ptr(cstart), _ptr(ccount), C, _ptr(cverts),
+                                                  _ptr(nfb), _ptr(ws), wsb, stream), "dfh_mesh_simplify_clusters")
+        cattrs = []
+        for a in attrs:
+            out = torch.empty((C,) + tuple(a.shape[1:]), dtype=a.dtype, device=dev)
+            K = a.numel() // V if V else 0
+            _lib.check(lib.dfh_mesh_simplify_attr(_ptr(a), dtype_code(a), V, K, _ptr(order), _ptr(cstart), _ptr(ccount), C, _ptr(out), stream),
+                       "dfh_mesh_simplify_attr")
+            cattrs.append(out)
+        fout, fidx, cmap, kept, vmap = i32(F, 3), i32(F), i32(C), i32(C), i32(V)
+        counts = (ctypes.c_long * 2)(0, 0)
+        _lib.check(lib.dfh_mesh_simplify_faces(_ptr(f), V, F, _ptr(vclus), C, int(bool(drop_unreferenced)), _ptr(fout), _ptr(fidx), _ptr(cmap),
+                                               _ptr(kept), _ptr(vmap), counts, _ptr(ws), wsb, stream), "dfh_mesh_simplify_faces")
+        idx = kept[:counts[0]].long()
+        info = {"vert_map": vmap.long(), "face_idx": fidx[:counts[1]].long(), "n_clusters": C, "n_fallback": int(nfb.item())}
+    return (cverts[idx], fout[:counts[1]], *[a[idx] for a in cattrs], info)
+
+
+def simplify_with_normals(verts, faces, normals, cell, **kw):
+    """simplify() for a mesh that carries vertex normals: the normals are averaged per cluster as an attribute and brought back to
+    unit length (a normal that averages to zero stays zero) -> (verts', faces', normals', info).  What the simplify_cell hooks of
+    Fusion / FusionDM.write_canonical_mesh and SlabFrame.colored_mesh run."""
+    v, f, n, info = simplify(verts, faces, normals, cell=cell, **kw)
+    length = torch.linalg.vector_norm(n, dim=1, keepdim=True)
+    return v, f, torch.where(length > 0, n / length, torch.zeros_like(n)), info

@@ -1447,6 +1447,81 @@ int dfh_mesh_compact(const int *faces, long n_verts, long n_faces, const int *ve
                      const unsigned char *keep, long n_components, int drop_unreferenced, int *kept_vert_idx, int *vert_map,
                      int *faces_out, long *counts_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- K24  mesh simplification: vertex clustering with quadric error metrics --------------------------------------------------------
+ * No reference counterpart.  verts: DEVICE (V, 3) float32 or float64 (dtype DFH_F32 / DFH_F64; float32 is widened, exactly, before
+ * anything is computed); faces: DEVICE (F, 3) int32; cell > 0; origin: HOST double[3]; mode DFH_SIMPLIFY_QUADRIC / _MEAN; reg >= 0.
+ * All arithmetic is fp64, one rounding per operation, no contraction; every sum starts at 0.0 and adds one term after the other
+ * in the stated order.  Every output is a function of the mesh and the parameters alone: the order in which the kernels'
+ * integer atomics land shows in none of them, and there is no float atomic.
+ *
+ * Cells.  c_a = floor((p_a - origin_a) / cell) per axis (one subtraction, one division).  key = c0 2^42 + c1 2^21 + c2.  The
+ *   centre of the cell is ctr_a = origin_a + (c_a + 0.5) * cell.
+ * Clusters.  A cluster is the set of vertices with one key, referenced by a face or not.  Cluster ids are 0 .. C-1 in ascending
+ *   order of the cluster's lowest vertex index; vert_cluster[v] is v's.  Its members in ascending vertex index are
+ *   order[cluster_start[c] .. + cluster_count[c]), order being the stable ascending sort of the keys that the caller supplies.
+ * Mean.  S = the sum of (p - ctr) over the members in ascending vertex index, per axis; m = S / double(count).
+ * Vertex quadric.  For face f = (a, b, c): e1 = p_b - p_a, e2 = p_c - p_a, n = e1 x e2 with n0 = e1y*e2z - e1z*e2y,
+ *   n1 = e1z*e2x - e1x*e2z, n2 = e1x*e2y - e1y*e2x (two rounded products and a subtraction each).  For the corner of f at vertex
+ *   v: q = p_a - ctr(cluster of v), d = -((n0*q0 + n1*q1) + n2*q2), and the ten numbers (n0n0, n0n1, n0n2, n1n1, n1n2, n2n2,
+ *   d n0, d n1, d n2, d d).  Q_v = their sums over the (face, corner) entries that name v, in ascending face then corner order
+ *   (corner_order[corner_begin[v] .. corner_end[v]) holds those entries as 3 f + corner: the stable ascending sort of the 3F
+ *   corner entries by the vertex they name, supplied by the caller).  The weight of a face is its area squared times four: no
+ *   square root, no division.
+ * Cluster quadric.  Q_C = the sum of Q_v over the members in ascending vertex index; A = its first six numbers as a symmetric
+ *   3 x 3 matrix (A00 A01 A02 A11 A12 A22), b = the next three.
+ * Representative x, relative to ctr.  mode MEAN: x = m.  mode QUADRIC: t = (A00 + A11) + A22; if !(t > 0), x = m.  Otherwise
+ *   lam = reg * t, M = A + lam I, r_a = lam * m_a - b_a, and M x = r is solved by LDL^T in this order:
+ *     d0 = M00;  l10 = M10 / d0;  l20 = M20 / d0;  d1 = M11 - l10*M10;  t21 = M21 - l20*M10;  l21 = t21 / d1;
+ *     d2 = (M22 - l20*M20) - l21*t21;  y0 = r0;  y1 = r1 - l10*y0;  y2 = (r2 - l20*y0) - l21*y1;
+ *     x2 = y2 / d2;  x1 = y1 / d1 - l21*x2;  x0 = (y0 / d0 - l10*x1) - l20*x2.
+ *   If a pivot d0, d1, d2 is !(> 0) (tested as it is formed, before it divides), or unless every |x_a| <= cell / 2, x = m and
+ *   the cluster counts as fallen back.  n_fallback: DEVICE int, the clusters that fell back (0 in mode MEAN).
+ *   verts_out[c][a] = ctr_a + x_a, cast to the dtype of verts ((C, 3) of room).
+ * Attributes.  attr: DEVICE (V, width) of dtype; out[c][k] = the fp64 sum of attr[v][k] over the members in ascending vertex
+ *   index, divided by double(count), cast to dtype.
+ * Faces.  A face is remapped through vert_cluster; it is dropped if two of its corners are equal; among the faces with the same
+ *   unordered triple the one with the lowest index survives.  With drop_unreferenced = 1 a cluster survives when a surviving face
+ *   names it, otherwise every cluster does.  cluster_map[c] = the survivors in front of c, -1 for a dropped cluster;
+ *   kept_cluster_idx = the survivors' ids, ascending (C of room); faces_out = the surviving faces in their order, corner order
+ *   kept, ids through cluster_map (F x 3 of room); face_idx = their old indices, ascending (F of room); vert_map[v] =
+ *   cluster_map[vert_cluster[v]].  counts_out: HOST long[2] = (clusters, faces) that survive.  The result is not guaranteed
+ *   manifold or consistently oriented where sheets thinner than a cell collapse.
+ *
+ * The calls, in order: _keys (keys per vertex; the caller sorts them, and the flattened faces, stably), _group (clusters and
+ * corner lists from the two sorted arrays), _clusters (positions), _attr (once per attribute), _faces.
+ * workspace: dfh_mesh_simplify_workspace_bytes(V, F) bytes of device memory, 8-byte aligned, the same size for the four calls
+ * that take one (0 for counts the calls refuse); its contents carry nothing from one call to the next.
+ * _keys, _group and _faces do not only enqueue: each queues its kernels on `stream`, synchronises `stream`, and has written
+ * n_clusters / counts_out (HOST pointers) when it returns.  Like dfh_mesh_components they cannot be captured into a graph.
+ * _clusters and _attr only enqueue.
+ * Refused on the device.  _keys raises a device flag and returns DFH_E_BADARG once it has synchronised for a coordinate that is
+ * not finite, a c_a outside [0, 2^21) or a face index outside [0, V) (such a vertex's key is -1; nothing is addressed through a
+ * bad index).  Every later call range-checks each index it addresses memory with -- a face's corners, the entries of order and
+ * corner_order, cluster ids, segments -- skips what fails, and _group / _faces return DFH_E_BADARG for it.
+ * V == 0 or F == 0 are valid and launch nothing they do not need.  DFH_E_BADARG before any HIP call: V negative or >= 2^31; F
+ * negative or above (2^31 - 1) / 3; a width negative or >= 2^31; C < 0 or C > V; faces without vertices or clusters; a cell
+ * that is not finite or not above 0; an origin or reg that is not finite, a negative reg; a mode or dtype that is not one of
+ * the two; drop_unreferenced other than 0 / 1; a null origin, n_clusters, n_fallback or counts_out; a null array of a non-zero
+ * count; a null workspace, one that is not 8-byte aligned or one smaller than dfh_mesh_simplify_workspace_bytes(V, F). */
+#define DFH_SIMPLIFY_QUADRIC 0
+#define DFH_SIMPLIFY_MEAN 1
+size_t dfh_mesh_simplify_workspace_bytes(long n_verts, long n_faces);
+int dfh_mesh_simplify_keys(const void *verts, int dtype, long n_verts, const int *faces, long n_faces, double cell,
+                           const double *origin, long long *keys, void *workspace, size_t workspace_bytes, void *stream);
+int dfh_mesh_simplify_group(const long long *sorted_keys, const long long *order, long n_verts, const int *sorted_corner_vert,
+                            long n_faces, int *vert_cluster, int *cluster_start, int *cluster_count, int *corner_begin,
+                            int *corner_end, long *n_clusters, void *workspace, size_t workspace_bytes, void *stream);
+int dfh_mesh_simplify_clusters(const void *verts, int dtype, long n_verts, const int *faces, long n_faces, double cell,
+                               const double *origin, int mode, double reg, const long long *keys, const long long *order,
+                               const long long *corner_order, const int *corner_begin, const int *corner_end,
+                               const int *cluster_start, const int *cluster_count, long n_clusters, void *verts_out,
+                               int *n_fallback, void *workspace, size_t workspace_bytes, void *stream);
+int dfh_mesh_simplify_attr(const void *attr, int dtype, long n_verts, long width, const long long *order, const int *cluster_start,
+                           const int *cluster_count, long n_clusters, void *out, void *stream);
+int dfh_mesh_simplify_faces(const int *faces, long n_verts, long n_faces, const int *vert_cluster, long n_clusters,
+                            int drop_unreferenced, int *faces_out, int *face_idx, int *cluster_map, int *kept_cluster_idx,
+                            int *vert_map, long *counts_out, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
