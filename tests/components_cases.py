@@ -48,6 +48,9 @@ def _cases():
     c["strip_permuted"] = (_verts(n + 2, 6), strip(n, np.random.default_rng(7).permutation(n + 2)))
     c["fan_hub_last"] = (_verts(5002, 8), fan(5000))
     c["isolated_3000"] = (_verts(9000, 9), isolated(3000))
+    # one table entry per face, and cc_table_rank_kernel strides 2048 workgroups x 4 waves over the entries: at 8193 the first wave
+    # takes a second entry
+    c["isolated_8193"] = (_verts(3 * 8193, 60), isolated(8193))
     for k in (255, 256, 257, 1023, 1024, 1025):
         c["soup_%d" % k] = (_verts(k, 10 + k), soup(k, k, 20 + k))              # V = F = k
         c["strip_F%d" % k] = (_verts(k + 2, 30 + k), strip(k))                  # F = k, one component

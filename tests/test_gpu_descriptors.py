@@ -70,6 +70,22 @@ def test_shapes_at_the_kernels_edges(dim, path):
         check(q, b, path, (dim, nq, nb))
 
 
+def test_a_score_workgroup_walks_a_second_base_chunk():
+    """nd_score_kernel's grid is (query tiles, base splits) with splits = min(ceil(2048 / query tiles), base chunks): a workgroup
+    walks the chunks y, y + splits, ... and takes a second one only when query tiles x chunks > 2048.  8193 queries (65 tiles, the
+    last of one query: 32 splits) against 4160 base rows (33 chunks, the last of 64 rows): the first split's workgroups reload
+    their LDS chunk and carry their running minimum -- and, emitting, their candidate slots -- into chunk 32.  The fast path."""
+    dim, nq, nb = 4, 64 * TILE_Q + 1, 32 * TILE_B + 64
+    q_tiles, chunks = -(-nq // TILE_Q), -(-nb // TILE_B)
+    splits = min(-(-2048 // q_tiles), chunks)
+    assert (q_tiles, chunks, splits) == (65, 33, 32) and chunks > splits
+    rng = np.random.default_rng(65)
+    q = rng.standard_normal((nq, dim)).astype(np.float32)
+    b = rng.standard_normal((nb, dim)).astype(np.float32)
+    idx, _, _ = check(q, b, 2, (dim, nq, nb))
+    assert (idx >= splits * TILE_B).sum() > 10                       # nearest rows in the chunk only the second turn reaches
+
+
 @pytest.mark.parametrize("path", PATHS)
 def test_exact_ties_go_to_the_lowest_index(path):
     rng = np.random.default_rng(7)

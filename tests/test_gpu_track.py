@@ -10,7 +10,12 @@ exactly, two runs to the same bits.  xi is bit for bit the restated Cholesky on 
 sums per entry).  End to end the poses are held to that per-step bound times the number of iterations wherever the track
 converges (measured: 7e-16 and 3e-16 against a bound of 1.35e-13).  The single fine level of the qualitative bar does not: it slides
 along the wall through a nearly singular system, where the device's and numpy's orders of summation end 9e-11 apart; that pose is
-held to the bar only (it must end above the applied motion), and the figure is printed."""
+held to the bar only (it must end above the applied motion), and the figure is printed.
+
+Past the first pass.  icp_rows_kernel runs 256 workgroups per view; the maps of tests/track_cases.PASS_SHAPES have 255, 256, 257, 513,
+289 and 561 tiles, so that a workgroup walks a second and a third tile with its accumulator alive (measured: worst error 2.4e-4
+of the bound at up to 110 422 rows per view); sixteen views with sixteen T; min_count at equality and one above; the exponential
+on either side of its series threshold."""
 import json
 import math
 import os
@@ -275,6 +280,168 @@ def test_refusals_leave_T_untouched(scene_frame):
     assert stats[0, 0, 28] == 24 * 32 and stats[0, 0, 27] > 0 and not stats[0, :, 29:].any()
     assert TN.icp_solve(stats[0, 0, :29], T0[0], 0.0, 6, math.inf, math.inf)[0] == 0
     assert_same_bits(T1, T0, "T of the singular system")
+
+
+# ---- past the first pass of the rows grid: a workgroup walks a second and a third tile -----------------------------------------
+
+def assert_sums_within_bound(rec, want_rows, what):
+    """One (view, iteration) record against the restatement's rows: the count exactly, the 28 sums within (n + 4) 2^-53 sum |term|."""
+    exact, mag = TN.icp_sums(want_rows)
+    n = int(exact[28])
+    assert rec[28] == n, "%s: count %r, restated %d" % (what, rec[28], n)
+    err = np.abs(rec[:28] - exact[:28])
+    bound = (n + 4) * EPS * mag[:28]
+    print(what, "rows", n, "worst error / bound", float((err / bound).max()) if n else 0.0)
+    assert np.all(err <= bound), what
+    return n
+
+
+@pytest.mark.parametrize("size", list(TC.PASS_SHAPES))
+def test_rows_and_sums_past_the_first_pass(size):
+    """255, 256, 257, 513, 289 and 561 tiles against the grid's 256 workgroups per view: zero or one tile each, exactly one, one
+    workgroup two, one three, a two-dimensional map, and a partial third pass that ends in a one-pixel-high tile row.  The MFMA
+    accumulator lives across the passes and the LDS rows are rewritten for every tile behind a wave barrier only: rows bit for bit,
+    the count exactly, the sums within the bound, a second run to the same bits, xi bit for bit on the device's sums.
+    tests/test_track_np.py::test_pass_cases_reach_every_pass_of_the_rows_grid holds the maps to their purpose (a row in every
+    pass, pass 0 alone outside this bound)."""
+    H, W = size
+    tiles, passes = TC.PASS_SHAPES[size]
+    assert TC.n_tiles(H, W) == tiles and -(-tiles // TC.ICP_GRID) == passes
+    c = TC.pass_case(H, W)
+    kw = dict(TC.PASS_GATES, lm_rel=1e-3)
+    args = (c["Dl"], c["Nl"], c["Dm"], c["Nm"], c["K"], c["Ts"])
+    T1, stats, rows = run_icp(*args, 1, **kw)
+    assert_same_bits(rows, c["rows"], "rows")
+    for v in range(2):
+        assert assert_sums_within_bound(stats[v, 0], c["rows"][v], "%r view %d" % (size, v)) > 0.5 * H * W
+        status, xi, Tn = TN.icp_solve(stats[v, 0, :29], c["Ts"][v], 1e-3, 6, math.inf, math.inf)
+        assert status == 1 and stats[v, 0, 29] == 1.0 and not stats[v, 0, 36:].any()
+        assert_same_bits(stats[v, 0, 30:36], xi, "xi")
+        assert float(np.abs(T1[v] - Tn).max()) <= 64 * EPS * max(1.0, float(np.abs(Tn).max()))
+    T2, stats2, rows2 = run_icp(*args, 1, **kw)
+    assert_same_bits(stats2, stats, "stats of a second run")
+    assert_same_bits(T2, T1, "T of a second run")
+    assert_same_bits(rows2, rows, "rows of a second run")
+
+
+def test_chained_iterations_past_the_first_pass():
+    """Three iterations in one call on the 289-tile map, no rows written: record i is the first record of a fresh one-iteration
+    call started from the T the records before it left (the partial sets and the accumulators carry nothing from one iteration
+    to the next), and each record's sums are within the bound of the restatement's rows at that T."""
+    c = TC.pass_case(272, 272)
+    kw = dict(TC.PASS_GATES, lm_rel=1e-3, min_count=100, max_rot=0.5, max_trans=0.5)
+    args = (c["Dl"], c["Nl"], c["Dm"], c["Nm"], c["K"])
+    T3, stats3, none = run_icp(*args, c["Ts"], 3, want_rows=False, **kw)
+    assert none is None and np.all(stats3[:, :, 29] == 1.0)
+    T = c["Ts"]
+    for i in range(3):
+        want = np_rows(*args, T, **TC.PASS_GATES)
+        for v in range(2):
+            assert_sums_within_bound(stats3[v, i], want[v], "iteration %d view %d" % (i, v))
+        T, stats, _ = run_icp(*args, T, 1, want_rows=False, **kw)
+        assert_same_bits(stats[:, 0], stats3[:, i], "record %d" % i)
+    assert_same_bits(T, T3, "T after three iterations")
+    assert not np.array_equal(stats3[:, 0, :28], stats3[:, 1, :28]) and not np.array_equal(stats3[:, 1, :28], stats3[:, 2, :28])
+
+
+# ---- sixteen views ---------------------------------------------------------------------------------------------------------------
+
+def test_sixteen_views_each_with_its_own_maps_and_T():
+    """The view index scales the maps' base, T, the partial sets and the records: sixteen views of 34 x 50 (3 x 4 tiles, the last
+    row and column of tiles two pixels wide), every map drawn on its own, sixteen different T, one view without a live measurement.
+    Rows bit for bit, counts exactly, sums within the bound per view, xi bit for bit on each view's own sums; seventeen views are
+    refused by icp_track and by icp_track_scratch."""
+    V, H, W, BLANK = 16, 34, 50, 11
+    K = np.array([[0.9 * W, 0.01, (W - 1) / 2.0], [0.0, 0.8 * W, (H - 1) / 2.0], [0.0, 0.0, 1.0]])
+    Dl, Nl, Dm, Nm, Ts = [], [], [], [], []
+    for v in range(V):
+        rng = np.random.default_rng(7000 + v)
+        Dl.append(special_depth(rng, H, W)); Dm.append(special_depth(rng, H, W))
+        Nl.append(special_normals(rng, H, W)); Nm.append(special_normals(rng, H, W))
+        Ts.append(TN.apply_twist(rng.normal(scale=[0.03] * 3 + [0.05] * 3), TC.IDENT))
+    Dl, Nl, Dm, Nm, Ts = (np.stack(a) for a in (Dl, Nl, Dm, Nm, Ts))
+    Dl[BLANK] = 0.0
+    assert len({T.tobytes() for T in Ts}) == V
+    kw = dict(max_dist=0.6, min_cos=0.3, huber=0.05)
+    want = np_rows(Dl, Nl, Dm, Nm, K, Ts, **kw)
+    T1, stats, rows = run_icp(Dl, Nl, Dm, Nm, K, Ts, 1, lm_rel=1e-3, **kw)
+    assert_same_bits(rows, want, "rows")
+    counts = []
+    for v in range(V):
+        counts.append(assert_sums_within_bound(stats[v, 0], want[v], "view %d" % v))
+        status, xi, Tn = TN.icp_solve(stats[v, 0, :29], Ts[v], 1e-3, 6, math.inf, math.inf)
+        assert stats[v, 0, 29] == status
+        assert_same_bits(stats[v, 0, 30:36], xi, "xi of view %d" % v)
+        assert float(np.abs(T1[v] - Tn).max()) <= 64 * EPS * max(1.0, float(np.abs(Tn).max()))
+    assert counts[BLANK] == 0 and not stats[BLANK].any()
+    assert_same_bits(T1[BLANK], Ts[BLANK], "T of the view without a live map")
+    stepped = [v for v in range(V) if stats[v, 0, 29] == 1.0]
+    assert len(stepped) >= 12 and len(set(counts)) >= 12                  # (the views do differ: a view reading another's maps shows)
+    for v in stepped:
+        assert not np.array_equal(T1[v], Ts[v])
+    with pytest.raises(ValueError):
+        kernels.icp_track_scratch(V + 1)
+    more = [np.concatenate([a, a[:1]]) for a in (Dl, Nl, Dm, Nm, Ts)]
+    with pytest.raises(ValueError):                                      # (its own scratch: icp_track_scratch refuses first)
+        run_icp(*more[:4], K, more[4], 1, **kw)
+    T17 = dev(more[4])
+    with pytest.raises(ValueError, match="views"):                       # (a scratch that exists: the library refuses)
+        kernels.icp_track(dev(more[0]), dev(more[1]), dev(more[2]), dev(more[3]), K, np.linalg.inv(K), T17, 1,
+                          scratch=kernels.icp_track_scratch(V), **kw)
+    assert_same_bits(T17.cpu().numpy(), more[4], "T of a refused call")
+
+
+# ---- the finish kernel's two decisions at their edges -------------------------------------------------------------------------
+
+def test_min_count_at_its_edge(scene_frame):
+    """sv[28] >= min_count decides per view: with min_count equal to a view's count that view steps (the record is the unconstrained
+    run's, bit for bit), with one more it is refused (T untouched, the record zero from index 29 on).  The two views' counts
+    differ, so one call holds a view that steps beside one that is refused."""
+    Dl, Nl, Dm, Nm, Ts = scene_frame
+    base = dict(max_dist=0.1, min_cos=0.8, huber=0.01, lm_rel=1e-3)
+    T_free, free, _ = run_icp(Dl, Nl, Dm, Nm, TC.K, Ts, 1, want_rows=False, **base)
+    n = [int(free[v, 0, 28]) for v in range(2)]
+    assert n[0] != n[1] and min(n) > 5000 and np.all(free[:, 0, 29] == 1.0)
+    lo, hi = (0, 1) if n[0] < n[1] else (1, 0)
+    for min_count, steps in ((n[lo], (lo, hi)), (n[lo] + 1, (hi,)), (n[hi], (hi,)), (n[hi] + 1, ())):
+        T1, stats, _ = run_icp(Dl, Nl, Dm, Nm, TC.K, Ts, 1, want_rows=False, min_count=min_count, **base)
+        assert_same_bits(stats[:, 0, :29], free[:, 0, :29], "sums at min_count %d" % min_count)
+        for v in range(2):
+            if v in steps:
+                assert stats[v, 0, 29] == 1.0
+                assert_same_bits(stats[v, 0], free[v, 0], "record of the stepping view %d at min_count %d" % (v, min_count))
+                assert_same_bits(T1[v], T_free[v], "T of the stepping view")
+            else:
+                assert not stats[v, 0, 29:].any(), (v, min_count)
+                assert_same_bits(T1[v], Ts[v], "T of the refused view")
+            assert TN.icp_solve(stats[v, 0, :29], Ts[v], 1e-3, min_count, math.inf, math.inf)[0] == (1 if v in steps else 0)
+
+
+def test_small_angle_branch_of_the_exponential():
+    """The model as the live map under a prior that is a pure rotation: of 5e-5 rad in view 0, whose step lands below the series
+    branch's ww < 1e-8, and of 2e-4 rad in view 1, above it (ww read from the device's xi).  xi bit for bit on the device's sums,
+    T within 64 * 2^-53 * max(1, max |T|) of the restated exponential on either branch, and bit for bit through the series branch.
+    (At ww = 4e-8 the two branches' a, b, c agree to ww^2 / 120 = 1e-17, below an ulp: moving the threshold there changes T by
+    rounding only, which the bound allows -- a threshold of 1e-7 is not told from 1e-8 by any bound on T.)"""
+    md, mn = TC.render(TC.IDENT)
+    axis = np.array([0.3, 1.0, 0.2]) / np.linalg.norm([0.3, 1.0, 0.2])
+    Ts = np.stack([TN.apply_twist(np.concatenate([a * axis, np.zeros(3)]), TC.IDENT) for a in (5e-5, 2e-4)])
+    D, N = np.stack([md, md]), np.stack([mn, mn])
+    kw = dict(max_dist=0.1, min_cos=0.8, huber=0.01, lm_rel=1e-3, min_count=100, max_rot=0.5, max_trans=0.5)
+    T1, stats, _ = run_icp(D, N, D, N, TC.K, Ts, 1, want_rows=False, **kw)
+    ww = [float((stats[v, 0, 30] * stats[v, 0, 30] + stats[v, 0, 31] * stats[v, 0, 31]) + stats[v, 0, 32] * stats[v, 0, 32]) for v in range(2)]
+    print("ww", ww)
+    assert 0.0 < ww[0] < 1e-8 < ww[1]
+    for v in range(2):
+        status, xi, Tn = TN.icp_solve(stats[v, 0, :29], Ts[v], 1e-3, 100, 0.5, 0.5)
+        assert status == 1 and stats[v, 0, 29] == 1.0 and stats[v, 0, 28] > 15000
+        assert_same_bits(stats[v, 0, 30:36], xi, "xi")
+        err = float(np.abs(T1[v] - Tn).max())
+        bound = 64 * EPS * max(1.0, float(np.abs(Tn).max()))
+        print("view", v, "T error", err, "bound", bound, "same bits", bool(np.array_equal(T1[v], Tn)))
+        assert err <= bound and not np.array_equal(T1[v], Ts[v])
+    # the series branch calls neither sin nor cos: every operation of it rounds once, in the stated order
+    assert_same_bits(T1[0], TN.icp_solve(stats[0, 0, :29], Ts[0], 1e-3, 100, 0.5, 0.5)[2], "T through the series branch")
 
 
 def test_no_iterations_launch_nothing(scene_frame):

@@ -178,6 +178,48 @@ def test_refused_steps_repeat(frame):
     assert np.array_equal(stats[0], stats[1]) and np.array_equal(stats[1], stats[2])
 
 
+@pytest.mark.parametrize("size", list(TC.PASS_SHAPES))
+def test_pass_cases_reach_every_pass_of_the_rows_grid(size):
+    """The maps of tests/test_gpu_track.py::test_rows_and_sums_past_the_first_pass really make a workgroup of icp_rows_kernel walk
+    a second and a third tile.  Asserted on the restatement, per view: the tile count is of the class the shape was chosen for;
+    every pass holds a row that adds to the sums (w > 0, r != 0) and a pixel without a row, and so do both tiles of most workgroups
+    that take two (in view 0); the one-pixel-high last tile row of (257, 528) holds such a row too; and the sums of pass 0 ALONE
+    lie more than 100 of the GPU test's bounds away in every one of the 28 entries (measured: 1.6e8 at the least), and differ in the
+    count: a kernel that dropped the later passes (or reset its accumulator between them) cannot pass."""
+    H, W = size
+    tiles, passes = TC.PASS_SHAPES[size]
+    assert TC.n_tiles(H, W) == tiles and -(-tiles // TC.ICP_GRID) == passes
+    c = TC.pass_case(H, W)
+    assert c["tile"].max() == tiles - 1 and np.array_equal(np.unique(c["tile"]), np.arange(tiles))
+    p_of = c["tile"] // TC.ICP_GRID
+    for v in range(2):
+        rows = c["rows"][v]
+        live = (rows[..., 7] > 0) & (rows[..., 6] != 0)
+        for p in range(passes):
+            assert live[p_of == p].any() and not (rows[..., 7] > 0)[p_of == p].all(), (v, p)
+        assert (rows[..., 7] < 1.0)[live].sum() > 100                              # Huber weights take part
+        if passes > 1 and v == 0:
+            # most workgroups that take two tiles find such a row in BOTH (view 0's T is the identity: no pixel leaves the map), and
+            # one that takes three in all three: an accumulator that forgot a tile on the way to the next loses something
+            has = np.bincount(c["tile"][live], minlength=tiles) > 0
+            two = [has[t] and has[t + TC.ICP_GRID] for t in range(tiles - TC.ICP_GRID)]
+            three = [has[t] and has[t + TC.ICP_GRID] and has[t + 2 * TC.ICP_GRID] for t in range(max(0, tiles - 2 * TC.ICP_GRID))]
+            print(size, "workgroups with a row in each of two tiles", sum(two), "of", len(two), "of three", sum(three), "of", len(three))
+            assert sum(two) >= 0.8 * len(two) and (not three or sum(three) >= 1)
+        if size == (257, 528):
+            assert H % 16 == 1 and live[H - 1].any() and p_of[H - 1].min() == 2     # the last tile row: one pixel high, in the partial pass
+        exact, mag = TN.icp_sums(rows)
+        n = int(exact[28])
+        print(size, "view", v, "rows", n, "of", H * W)
+        assert n > 0.5 * H * W
+        if passes > 1:
+            first, _ = TN.icp_sums(np.where((p_of == 0)[..., None], rows, 0.0))
+            assert first[28] < n
+            miss = np.abs(first[:28] - exact[:28]) / ((n + 4) * 2.0 ** -53 * mag[:28])
+            print("pass 0 alone: smallest error / bound", float(miss.min()))
+            assert miss.min() > 100.0
+
+
 def test_recorded_recovery_and_the_qualitative_bar():
     """There is a motion for which three levels end below 1 % of the applied motion while one level at the fine gate ends above
     the applied motion.  The restatement's normals are depth_prep's, not the prototype's finite differences, and its scene is its

@@ -101,6 +101,72 @@ def track_np_pyramid(live_depth, lw_prev, levels, gates, cosines, iters, huber=0
     return T, stats
 
 
+# ---- maps with more tiles than the rows kernel has workgroups -------------------------------------------------------------------
+# icp_rows_kernel runs ICP_GRID workgroups per view; workgroup b walks the 16 x 16-pixel tiles b, b + ICP_GRID, ...  A "pass" p is
+# the tiles 256 p .. 256 p + 255 that exist: what the grid does in one turn of that loop.  The shapes are chosen by tile count.
+ICP_GRID = 256
+PASS_SHAPES = {                         # (H, W): (tiles, passes)
+    (16, 4080): (255, 1),               # one below the grid
+    (16, 4096): (256, 1),               # exactly the grid
+    (16, 4112): (257, 2),               # one workgroup takes two tiles
+    (16, 8208): (513, 3),               # one workgroup takes three tiles
+    (272, 272): (289, 2),               # two-dimensional, full tiles
+    (257, 528): (561, 3),               # 2 * 256 + 49: a partial third pass whose last tile row is one pixel high
+}
+PASS_GATES = dict(max_dist=0.1, min_cos=0.8, huber=0.01)
+NO_MEASUREMENT = (np.nan, np.inf, -np.inf, -0.0, 0.0, 2.5)     # the classes of tests/test_gpu_track.special_depth
+
+
+def n_tiles(h, w):
+    return ((w + 15) // 16) * ((h + 15) // 16)
+
+
+def tile_index(h, w):
+    """(h, w) int: the index of the 16 x 16 tile a pixel lies in, row-major over tiles (the kernel's tile -> pixel map, inverted)."""
+    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    return (y // 16) * ((w + 15) // 16) + x // 16
+
+
+def pass_intrinsics(h, w):
+    return np.array([[0.9 * w, 0.0, (w - 1) / 2.0], [0.0, 0.9 * w, (h - 1) / 2.0], [0.0, 0.0, 1.0]])
+
+
+def sprinkle(rng, depth, normals):
+    """Every class of 'no measurement', and pixels without a normal, over a diagonal band that crosses every tile (in place)."""
+    h, w = depth.shape
+    y, x = np.meshgrid(np.arange(h), np.arange(w), indexing="ij")
+    band = (x + 3 * y) % 16 < 3
+    pick = rng.random((h, w))
+    for k, v in enumerate(NO_MEASUREMENT):
+        depth[band & (pick >= 0.04 * k) & (pick < 0.04 * (k + 1))] = v
+    normals[band & (rng.random((h, w)) < 0.1)] = 0.0
+
+
+_PASS_CASES = {}
+
+
+def pass_case(h, w):
+    """The scene through pass_intrinsics(h, w): the model from the identity, the live map from motion(0.3), both sprinkled; two
+    views of the same maps with different T (the identity; a small twist); the restatement's rows under
+    PASS_GATES.  Built once per shape and shared, CPU and GPU tests alike: nobody writes to it."""
+    if (h, w) not in _PASS_CASES:
+        Kp = pass_intrinsics(h, w)
+        rng = np.random.default_rng(1000 * h + w)
+        md, mn = render(IDENT, Kp, h, w)
+        ld, ln = render(motion(0.3), Kp, h, w)
+        sprinkle(rng, md, mn)
+        sprinkle(rng, ld, ln)
+        # (a 16-row map through f = 0.9 w: a prior that moved the projection by more than a few rows would leave no row at all;
+        # the second view's turns about y and moves along x and z, which shift it along the rows, inwards at the last tile)
+        Ts = np.stack([IDENT, track_np.apply_twist(np.array([2e-4, -4e-3, 1e-3, -0.01, 2e-4, 0.005]), IDENT)])
+        Dl, Nl, Dm, Nm = np.stack([ld, ld]), np.stack([ln, ln]), np.stack([md, md]), np.stack([mn, mn])
+        rows = np.stack([track_np.icp_rows(Dl[v], Nl[v], Dm[v], Nm[v], Kp, np.linalg.inv(Kp), Ts[v], **PASS_GATES) for v in range(2)])
+        for a in (Dl, Nl, Dm, Nm, Ts, rows):
+            a.setflags(write=False)
+        _PASS_CASES[(h, w)] = dict(K=Kp, Dl=Dl, Nl=Nl, Dm=Dm, Nm=Nm, Ts=Ts, rows=rows, tile=tile_index(h, w))
+    return _PASS_CASES[(h, w)]
+
+
 def pose_error(T, lw_prev, lw_true):
     """(degrees, metres) between the tracked camera T^-1 lw_prev and the true one."""
     lw = track_np.compose(track_np.invert_rigid(T), lw_prev)
