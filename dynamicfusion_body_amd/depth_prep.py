@@ -5,11 +5,10 @@ pixels, grazing angles).  One kernel launch for all views of a frame (kernels.de
 The cleaned maps keep the convention every other entry point reads (negative depth, 0 = no measurement), so a DepthPrep can be
 put in front of anything that takes depth maps: FusionDM.depth_prep / Fusion.depth_prep / SlabFrame(depth_prep=...) do so for
 the methods that sweep a list of maps.  Nothing uses it unless asked to."""
-import numpy as np
 import torch
 
 from . import kernels
-from .device import f32_exact, to_device
+from .device import depths_to_device
 
 
 class DepthPrep:
@@ -45,11 +44,8 @@ class DepthPrep:
 
     @staticmethod
     def _to_device(depths):
-        """fuseDepths' dtype rule for a list: float32 on the device unless a float64 map is not float32-exact (then all float64)."""
-        def exact32(d):
-            return (d.dtype == torch.float32) if isinstance(d, torch.Tensor) else f32_exact(np.asarray(d))
-        dt = torch.float32 if all(exact32(d) for d in depths) else torch.float64
-        return [to_device(d if isinstance(d, torch.Tensor) else np.asarray(d), dtype=dt) for d in depths]
+        """fuseDepths' dtype rule for a list (device.depths_to_device)."""
+        return depths_to_device(depths)
 
     def __call__(self, depths, Kinv, want_normals=True, out=None):
         """depths: list of (H, W) maps of one shape (CUDA tensors, or numpy arrays that are uploaded); Kinv: inverse intrinsics.

@@ -115,3 +115,17 @@ def f32_exact(a):
     if a.dtype == np.float32:
         return True
     return bool(np.array_equal(a.astype(np.float32).astype(a.dtype), a))
+
+
+def depths_dtype(depths):
+    """The one dtype all maps of a call travel as: float32 unless some map is not float32-exact (a tensor: is not float32) --
+    then every map goes as float64, so that no visibility mask can flip (a multi-view sweep wants one dtype per call)."""
+    def as_f32(d):
+        return (d.dtype == torch.float32) if isinstance(d, torch.Tensor) else f32_exact(np.asarray(d))
+    return torch.float32 if all(as_f32(d) for d in depths) else torch.float64
+
+
+def depths_to_device(depths):
+    """A list of depth maps (tensors or arrays) -> contiguous device tensors of depths_dtype(depths)."""
+    dt = depths_dtype(depths)
+    return [to_device(d if isinstance(d, torch.Tensor) else np.asarray(d), dtype=dt) for d in depths]

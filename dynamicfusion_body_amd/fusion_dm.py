@@ -24,29 +24,21 @@ import torch
 from numpy import linalg as la
 
 from . import kernels, mesh as _mesh, solve as _solve
-from .device import f32_exact, require_gpu, to_device, torch_dtype
+from .canonical import CanonicalModel, _is_tensor
+from .device import depths_to_device, require_gpu, to_device
 
 
-def _is_tensor(a):
-    return isinstance(a, torch.Tensor)
-
-
-class FusionDM:
-    ingest = None                # an ingest.RGBDIngest: compute_live_tsdf then takes the sensor's RAW frames (uint16 depth maps, raw colour
-                                 # images) and runs them through the stage first, in front of depth_prep; set on an instance
-    depth_prep = None            # a depth_prep.DepthPrep: compute_live_tsdf cleans its list of maps with it first; set on an instance
+class FusionDM(CanonicalModel):
+    _mc_level = 0.0              # write_canonical_mesh / live_frame_mesh extract the zero level set (core/fusion_dm.py:341)
+    _live_tensor_error = 'Only accept 3D array as tsdf'
+    _weight_arg = 'tsdf_w'
+    _unit_weight_samples = False  # surface_samples gates on the fused weights as they are (Fusion: see there)
 
     def __init__(self, trunc_distance, K, tsdf_res=256, subsample_rate=5.0, knn=4, marching_cubes_step_size=3,
                  verbose=False, write_warpfield=True, volume_dtype=np.float32):
         # attribute set of the reference ctor, core/fusion_dm.py:57-81
-        self._itercounter = 0
-        self._curr_tsdf = None
-        self._tdist = abs(trunc_distance)
+        self._init_model(trunc_distance, subsample_rate, knn, marching_cubes_step_size, verbose, write_warpfield, volume_dtype)
         self._tsdf_res = tsdf_res
-        self._vol_dtype = torch_dtype(volume_dtype)
-        self._T = None          # device volumes, allocated lazily (ctor must work without a GPU)
-        self._Wt = None
-        self._C = None          # the colour volume (kernels.color_volume): set by the calls that are given colour images
         self._lw = np.array([1, 0, 0, 0, 0, 0, 0, 0], dtype=np.float32)
 
         K = np.asarray(K, dtype=np.float64)
@@ -57,21 +49,7 @@ class FusionDM:
 
         self._IND = np.eye(4)
         self._INDinv = la.inv(self._IND)
-
-        self._knn = knn
-        self._marching_cubes_step_size = marching_cubes_step_size
-        self._subsample_rate = subsample_rate
-        self._nodes = []
-        self._neighbor_look_up = []
-        self._correspondences = []
         self._corridx = []
-        self.min_component_faces = None          # a number: marching_cubes() drops the components with fewer faces from the stored mesh
-        self.simplify_cell = None                # a number: write_canonical_mesh() writes the mesh clustered at that cell size (voxels)
-        self._vertices = None
-        self._normals = None
-        self._kdtree = None
-        self._verbose = verbose
-        self._write_warpfield = write_warpfield
 
     def verbose_gpu(self):
         """What the reference's device plug-in prints about its OpenCL devices (FusionDM_GPU.verbose_gpu, core/fusion_dm.py:576-598),
@@ -106,30 +84,6 @@ class FusionDM:
             self._T = T if self._T is None else self._T
             self._Wt = Wt if self._Wt is None else self._Wt
 
-    @property
-    def _tsdf(self):
-        self._ensure_volumes()
-        return self._T.cpu().numpy().astype(np.float64)
-
-    @_tsdf.setter
-    def _tsdf(self, value):
-        self._T = to_device(value, dtype=self._vol_dtype)
-
-    @property
-    def _tsdfw(self):
-        self._ensure_volumes()
-        return self._Wt.cpu().numpy().astype(np.float64)
-
-    @_tsdfw.setter
-    def _tsdfw(self, value):
-        self._Wt = to_device(value, dtype=self._vol_dtype)
-
-    @property
-    def tsdf_device(self):
-        """The resident TSDF / weight tensors (no copy)."""
-        self._ensure_volumes()
-        return self._T, self._Wt
-
     # ------------------------------------------------------------------ A1
     def _depth_to_device(self, dm):
         if _is_tensor(dm):
@@ -140,8 +94,7 @@ class FusionDM:
         dm = np.asarray(dm)
         if dm.ndim != 2:
             raise ValueError('depth map must be 2-D')
-        # float32 on device unless that would change a value (then masks could flip)
-        return to_device(dm, dtype=torch.float32 if f32_exact(dm) else torch.float64)
+        return depths_to_device([dm])[0]        # float32 on device unless that would change a value (then masks could flip)
 
     def fuseDepths_ocl(self, dm, lw, tsdf, tsdf_w, wmax=100.0):
         """The reference's OTHER fuseDepths: FusionDM_GPU's OpenCL kernel (core/fusion_dm.py:600-737), whose arithmetic differs
@@ -185,34 +138,9 @@ class FusionDM:
         lw = np.asarray(lw, dtype=np.float64)
         if lw.shape != (3, 4):
             raise ValueError('lw must be a 3x4 camera extrinsic')
-        depth = self._depth_to_device(dm)
-        if _is_tensor(tsdf) != _is_tensor(tsdf_w):
-            raise ValueError('tsdf and tsdf_w must both be numpy arrays or both CUDA tensors')
-        if _is_tensor(tsdf):
-            kernels.integrate_depth(tsdf, tsdf_w, depth, self._K, self._Kinv, lw, scale, center, self._tdist,
-                                    wmax, tsdf_res=self._tsdf_res)
-            return (tsdf, tsdf_w)
-        if tsdf.ndim != 3 or tsdf.shape != tsdf_w.shape:
-            raise ValueError('tsdf and tsdf_w must be 3-D arrays of the same shape')
-        T = to_device(tsdf, dtype=self._vol_dtype)
-        Wt = to_device(tsdf_w, dtype=self._vol_dtype)
-        kernels.integrate_depth(T, Wt, depth, self._K, self._Kinv, lw, scale, center, self._tdist, wmax,
-                                tsdf_res=self._tsdf_res)
-        tsdf[...] = T.cpu().numpy()
-        tsdf_w[...] = Wt.cpu().numpy()
-        return (tsdf, tsdf_w)
+        return self._fuse_depth_into(self._depth_to_device(dm), lw, tsdf, tsdf_w, scale, center, wmax, self._tsdf_res)
 
     # ------------------------------------------------------------------ A3
-    def _live_to_device(self, curr_tsdf):
-        if _is_tensor(curr_tsdf):
-            if curr_tsdf.dim() != 3:
-                raise ValueError('Only accept 3D array as tsdf')
-            t = curr_tsdf if curr_tsdf.dtype in (torch.float32, torch.float64) else curr_tsdf.to(torch.float32)
-            return to_device(t)
-        if type(curr_tsdf) is not np.ndarray or curr_tsdf.ndim != 3:
-            raise ValueError('Only accept 3D np array as tsdf')
-        return to_device(curr_tsdf, dtype=torch.float32 if f32_exact(curr_tsdf) else torch.float64)
-
     def updateTSDF(self, curr_tsdf, wmax=100.0):
         """Rigidly warp every canonical voxel by `_lw` into the live TSDF, sample it and fuse;
         reference core/fusion_dm.py:300-316.  Mutates `_tsdf` / `_tsdfw` (on the GPU)."""
@@ -245,19 +173,7 @@ class FusionDM:
         default (min + max) / 2 applies -- reproduced).  With `tsdf` returns (verts, faces, normals,
         values) as numpy arrays; without, fills `_vertices` / `_faces` / `_normals` from the canonical
         volume.  Runs on the GPU (csrc/dfh_mesh.hip); conventions and what is pinned: mesh.py."""
-        if step_size < 1:
-            step_size = self._marching_cubes_step_size
-        if tsdf is not None:
-            return _mesh.marching_cubes(self._live_to_device(tsdf), None, step_size, as_numpy=True)
-        self._ensure_volumes()
-        if self.min_component_faces is None:
-            self._vertices, self._faces, self._normals, values = _mesh.marching_cubes(self._T, None, step_size, as_numpy=True)
-        else:                                    # the mesh without its fragments (mesh.filter_components), cleaned on the device
-            v, f, n, _ = _mesh.marching_cubes(self._T, None, step_size)
-            v, f, n, _ = _mesh.filter_components(v, f, n, min_faces=self.min_component_faces)
-            self._vertices, self._faces, self._normals = v.cpu().numpy(), f.cpu().numpy(), n.cpu().numpy()
-        if self._verbose:
-            print("Marching Cubes result: number of extracted vertices is %d" % (len(self._vertices)))
+        return self._marching_cubes(tsdf, step_size)
 
     def render_model(self, lws, H, W, K=None, scale=1.0, center=np.zeros(3), **kw):
         """KinectFusion's surface prediction (not in the reference): the canonical volume ray-cast into the views `lws` (one 3x4
@@ -266,12 +182,7 @@ class FusionDM:
         convention, .normals, and .color when there is a colour volume `_C`); **kw goes to kernels.raycast (step, min_weight,
         refine, z_near, z_far, want, table, ...).  No mesh is built."""
         K = self._K if K is None else np.asarray(K, dtype=np.float64)
-        self._ensure_volumes()
-        lws = [lws] if np.asarray(lws[0]).ndim == 1 else list(lws)
-        if self._C is not None:
-            kw.setdefault("colors", self._C)
-            kw.setdefault("want", ("depth", "normals", "color"))
-        return kernels.raycast(self._T, self._Wt, K, la.inv(K), lws, H, W, scale, center, tsdf_res=self._tsdf_res, **kw)
+        return self._raycast_canonical(lws, H, W, K, scale, center, self._tsdf_res, **kw)
 
     def track_frame(self, depths, lws_prev, tracker, scale=1.0, center=np.zeros(3), **kw):
         """KinectFusion's pose estimation (not in the reference): the cameras of the depth maps `depths`, found by the
@@ -283,64 +194,13 @@ class FusionDM:
             return r.depth, r.normals
         return tracker.track(depths, lws_prev, model)
 
-    def surface_samples(self, tsdf=None, band=1.0):
-        """Dense alternative to the mesh vertices for the solve (not in the reference): every band
-        voxel moved onto the zero level set along the TSDF gradient (csrc/dfh_extract.hip), with the
-        normalised gradient as normal.  Same shapes as marching_cubes, faces / values = None."""
-        from .pipeline import extract_surface_samples
-        if tsdf is not None:
-            live = self._live_to_device(tsdf)
-            pos, nrm = extract_surface_samples(live, torch.ones_like(live), band)
-            return pos.cpu().numpy(), None, nrm.cpu().numpy(), None
-        self._ensure_volumes()
-        pos, nrm = extract_surface_samples(self._T, self._Wt, band)
-        self._vertices, self._faces, self._normals = pos.cpu().numpy(), None, nrm.cpu().numpy()
-
-    def write_canonical_mesh(self, path, filename):
-        """OBJ file of the canonical surface in world coordinates; reference core/fusion_dm.py:339-354
-        (level 0, step 1, degenerate faces dropped; `v` / `vn` / `f a//a b//b c//c`, 1-based)."""
-        self._ensure_volumes()
-        if self.simplify_cell is not None:   # a coarser file (mesh.simplify); the stored mesh and the graph are not touched
-            verts, faces, normals, _ = _mesh.marching_cubes(self._T, 0.0, 1)
-            verts, faces, normals, _ = _mesh.simplify_with_normals(verts, faces, normals, self.simplify_cell)
-            extra = {}
-            if self._C is not None:      # the colour volume sampled at the new vertices, not an average of the old colours
-                rgb, valid = kernels.sample_colors(self._C, verts.double())
-                extra = dict(colors=rgb.cpu().numpy(), valid=valid.cpu().numpy())
-            _mesh.write_obj(os.path.join(path, filename), verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), ind=self._IND, **extra)
-            return
-        if self._C is not None:          # vertex colours (not in the reference): the colour volume sampled at the vertices
-            verts, faces, normals, values = _mesh.marching_cubes(self._T, 0.0, 1)
-            rgb, valid = kernels.sample_colors(self._C, verts.double())
-            _mesh.write_obj(os.path.join(path, filename), verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), ind=self._IND,
-                            colors=rgb.cpu().numpy(), valid=valid.cpu().numpy())
-            return
-        verts, faces, normals, values = _mesh.marching_cubes(self._T, 0.0, 1, as_numpy=True)
-        _mesh.write_obj(os.path.join(path, filename), verts, faces, normals, ind=self._IND)
-
-    def write_warp_field(self, path, filename):
-        """Reference core/fusion_dm.py:334-336: pickle of `_nodes` into <path>/<filename>__<itercounter>.p."""
-        from . import io as _io
-        return _io.write_warp_field(self._nodes, path, filename, self._itercounter)
-
-    def _canonical_mesh_device(self):
-        """The extraction of write_canonical_mesh, left on the device: (verts, faces, normals)."""
-        verts, faces, normals, _ = _mesh.marching_cubes(self._T, 0.0, 1)
-        return verts, faces, normals
-
-    def write_live_frame_mesh(self, path, filename, warpfield_path):
-        """Reference core/fusion_dm.py:356-358 ("Process a warp field file and write the live frame mesh"; an empty stub there):
-        live_frame_mesh with the nodes of `warpfield_path` (a file of write_warp_field; None / "" = the current `_nodes`), written
-        like write_canonical_mesh (world coordinates through `_IND`).  Returns the file path."""
-        from . import io as _io
-        nodes = _io.read_warp_field(warpfield_path) if warpfield_path else None
-        verts, faces, normals = self.live_frame_mesh(nodes)
-        fpath = os.path.join(path, filename)
-        _mesh.write_obj(fpath, verts.cpu().numpy(), faces.cpu().numpy(), normals.cpu().numpy(), ind=self._IND)
-        return fpath
+    def _write_mesh(self, fpath, verts, faces, normals, colors=None, valid=None):
+        """World coordinates through `_IND`, `v` / `vn` / `f a//a b//b c//c` (core/fusion_dm.py:339-354)."""
+        _mesh.write_obj(fpath, verts, faces, normals, ind=self._IND, colors=colors, valid=valid)
 
     def average_edge_dist_in_face(self, f):
-        """Reference core/fusion_dm.py:360-364."""
+        """Reference core/fusion_dm.py:360-364.  (Not shared with Fusion: this one measures in the vertices' own dtype, that one
+        in float64, and the results differ in the last bits.)"""
         v1, v2, v3 = (np.asarray(self._vertices[i]) for i in f[:3])
         d = lambda a, b: np.linalg.norm(a - b)
         return (d(v1, v2) + d(v1, v3) + d(v2, v3)) / 3
@@ -410,11 +270,7 @@ class FusionDM:
                 raise ValueError('colors cannot be fused with useICP=True: every view gets a rigid alignment of its own there')
             if len(colors) != len(depths):
                 raise ValueError('one colour image per depth map')
-        color_depths = None
-        if self.ingest is not None and len(depths) > 0:              # raw frames in; the colour fusion reads the colour-only maps
-            depths, colors, color_depths = self.ingest.frame(depths, colors, K=self._K)
-        if self.depth_prep is not None and len(depths) > 0:          # (the single-map fuseDepths stays raw: the reference's meaning)
-            depths = self.depth_prep(depths, self._Kinv, want_normals=False)[0]
+        depths, colors, color_depths = self._prepare_depths(depths, colors)   # (the single-map fuseDepths stays raw)
         avg = np.array([-0.03, -0.43, -5.6], dtype='float32')       # :106-107
         std = 1.3
         if UseAutoAlignment:
