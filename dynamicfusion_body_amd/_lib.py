@@ -319,6 +319,11 @@ _SIGNATURES = {
     "dfh_mesh_simplify_attr": (_int, [_vp, _int, ctypes.c_long, ctypes.c_long, _vp, _vp, _vp, ctypes.c_long, _vp, _vp]),
     "dfh_mesh_simplify_faces": (_int, [_vp, ctypes.c_long, ctypes.c_long, _vp, ctypes.c_long, _int, _vp, _vp, _vp, _vp, _vp,
                                        ctypes.POINTER(ctypes.c_long), _vp, ctypes.c_size_t, _vp]),
+    "dfh_mesh_smooth_workspace_bytes": (ctypes.c_size_t, [ctypes.c_long, ctypes.c_long]),
+    "dfh_mesh_smooth_prepare": (_int, [_vp, _int, ctypes.c_long, _vp, ctypes.c_long, _vp, _vp, _int, _vp, _vp, ctypes.c_size_t, _vp]),
+    "dfh_mesh_smooth_run": (_int, [_vp, _int, ctypes.c_long, ctypes.c_long, ctypes.c_long, _int, _int, _int, _int, _dbl, _dbl, _vp, _vp,
+                                   ctypes.c_size_t, _vp]),
+    "dfh_mesh_vertex_normals": (_int, [_vp, _int, ctypes.c_long, ctypes.c_long, _dbl, _vp, _vp, ctypes.c_size_t, _vp]),
 }
 
 _lib = None

@@ -49,6 +49,7 @@ class CanonicalModel:
         self._correspondences = []
         self.min_component_faces = None          # a number: marching_cubes() drops the components with fewer faces from the stored mesh
         self.simplify_cell = None                # a number: write_canonical_mesh() writes the mesh clustered at that cell size (voxels)
+        self.smooth_iters = None                 # a number: write_canonical_mesh() writes the mesh after that many Taubin iterations
         self._vertices = None
         self._normals = None
         self._kdtree = None
@@ -180,6 +181,8 @@ class CanonicalModel:
         world coordinates, `v` / `vn` / `f a//a b//b c//c`.  The stored mesh and the graph are not touched."""
         self._ensure_volumes()
         verts, faces, normals = self._canonical_mesh_device()
+        if self.smooth_iters is not None:        # without the voxel-scale ripple (mesh.smooth), normals from the moved faces
+            verts, normals = _mesh.smooth_with_normals(verts, faces, self.smooth_iters)
         if self.simplify_cell is not None:       # a coarser file (mesh.simplify)
             verts, faces, normals, _ = _mesh.simplify_with_normals(verts, faces, normals, self.simplify_cell)
         colors = valid = None

@@ -729,3 +729,122 @@ def simplify_with_normals(verts, faces, normals, cell, **kw):
     v, f, n, info = simplify(verts, faces, normals, cell=cell, **kw)
     length = torch.linalg.vector_norm(n, dim=1, keepdim=True)
     return v, f, torch.where(length > 0, n / length, torch.zeros_like(n)), info
+
+
+# ---------------------------------------------------------------------------------------------------------------- K25
+# Smoothing by Taubin's lambda|mu filter over a fixed Laplacian, and area-weighted vertex normals (csrc/dfh_mesh_smooth.hip;
+# every output is defined in include/dfusion_hip.h).  The grouping is K24's stable torch.sort of the 3F corner entries by the
+# vertex they name, plumbing; the neighbour lists, the boundary flags, the weights and every pass run in the kernels.
+
+_SMOOTH_WEIGHTS = {"uniform": 0, "cotangent": 1}
+_SMOOTH_BOUNDARY = {"fixed": 0, "free": 1}
+_SMOOTH_LAYOUTS = {"rows": 0, "planes": 1}
+
+
+def taubin_mu(lam, pass_band):
+    """The negative factor of Taubin's filter for a positive factor lam and a pass-band frequency: 1 / (pass_band - 1 / lam), in
+    Python floats (fp64)."""
+    lam, pass_band = float(lam), float(pass_band)
+    if not (np.isfinite(lam) and lam != 0.0 and np.isfinite(pass_band)) or pass_band - 1.0 / lam == 0.0:
+        raise ValueError("mu = 1 / (pass_band - 1 / lam) needs a finite lam that is not 0 and pass_band != 1 / lam, got lam %r, pass_band %r"
+                         % (lam, pass_band))
+    return 1.0 / (pass_band - 1.0 / lam)
+
+
+class MeshLaplacian:
+    """A triangle mesh on the device with its prepared adjacency: per vertex the list of its faces' other two corners, the
+    boundary flags and (weights "cotangent") the cotangent weights of the positions given here, clamped at 0.  verts (V, 3)
+    float32 / float64, faces (F, 3) int32 / int64, numpy arrays or tensors (moved to the current device).  weights "uniform": a
+    neighbour counts once per face sharing the edge (the umbrella operator on a closed manifold).  boundary "fixed": a flagged
+    vertex never moves; "free": it moves like any other (and an open rim shrinks).  .boundary: (V,) bool, True where the vertex
+    lies on an open, non-manifold or repeated edge.  The operator is fixed: smooth() never recomputes the weights.  A coordinate
+    that is not finite and a face index outside [0, V) raise ValueError.  The constructor waits for the device once."""
+
+    layout = "rows"                      # how the fp64 values lie between passes ("rows" / "planes": the same bits; profiles/r29_smooth.txt)
+
+    def __init__(self, verts, faces, weights="uniform", boundary="fixed"):
+        if weights not in _SMOOTH_WEIGHTS:
+            raise ValueError("weights must be 'uniform' or 'cotangent', got %r" % (weights,))
+        if boundary not in _SMOOTH_BOUNDARY:
+            raise ValueError("boundary must be 'fixed' or 'free', got %r" % (boundary,))
+        self.lib = lib = _lib.load()
+        self.device, self.verts, self.faces = dev, v, f = _components_args(verts, faces)
+        self.weights, self.boundary_mode = weights, boundary
+        self.n_verts, self.n_faces = V, F = v.shape[0], f.shape[0]
+        with torch.cuda.device(dev):
+            scv, corder = torch.sort(f.reshape(-1), stable=True)
+            nbytes = lib.dfh_mesh_smooth_workspace_bytes(V, F)
+            if F and not nbytes:
+                raise ValueError("a mesh of %d vertices and %d faces is too large (3F must fit an int)" % (V, F))
+            self._ws = torch.empty((nbytes + 7) // 8, dtype=torch.int64, device=dev)
+            flags = torch.zeros(V, dtype=torch.uint8, device=dev)
+            _lib.check(lib.dfh_mesh_smooth_prepare(_ptr(v), dtype_code(v), V, _ptr(f), F, _ptr(scv), _ptr(corder), _SMOOTH_WEIGHTS[weights],
+                                                   _ptr(flags), _ptr(self._ws), self._ws.numel() * 8, current_stream_ptr()),
+                       "dfh_mesh_smooth_prepare")
+        self.boundary = flags.bool()
+
+    def _rows(self, x, what):
+        t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x))
+        if t.dtype not in (torch.float32, torch.float64):
+            raise ValueError("%s must be float32 or float64, got %s" % (what, t.dtype))
+        if t.dim() not in (1, 2) or t.shape[0] != self.n_verts:
+            raise ValueError("%s must have one row per vertex (%d), got shape %s" % (what, self.n_verts, tuple(t.shape)))
+        return t.to(self.device).contiguous()
+
+    def smooth(self, x=None, iters=10, lam=0.5, mu=None, pass_band=0.1):
+        """iters times (a pass with factor lam, then one with factor mu) over x: None = the vertices given to the constructor, or
+        a per-vertex attribute (V,) / (V, K), K <= 4, float32 / float64, filtered by the same operator.  mu None: Taubin's
+        1 / (pass_band - 1 / lam), which keeps the volume; mu = 0: plain Laplacian smoothing, which shrinks.  -> a CUDA tensor of
+        x's shape and dtype (fp64 inside, rounded once).  The call only enqueues."""
+        iters, lam = int(iters), float(lam)
+        mu = taubin_mu(lam, pass_band) if mu is None else float(mu)
+        if iters < 0:
+            raise ValueError("iters must not be negative, got %d" % iters)
+        if not (np.isfinite(lam) and np.isfinite(mu)):
+            raise ValueError("lam and mu must be finite, got %r and %r" % (lam, mu))
+        t = self.verts if x is None else self._rows(x, "x")
+        K = 1 if t.dim() == 1 else t.shape[1]
+        if not 1 <= K <= 4:
+            raise ValueError("x must have 1 to 4 columns, got %d" % K)
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(t)
+            _lib.check(self.lib.dfh_mesh_smooth_run(_ptr(t), dtype_code(t), self.n_verts, self.n_faces, K, _SMOOTH_WEIGHTS[self.weights],
+                                                    _SMOOTH_BOUNDARY[self.boundary_mode], _SMOOTH_LAYOUTS[self.layout], iters, lam, mu, _ptr(out),
+                                                    _ptr(self._ws), self._ws.numel() * 8, current_stream_ptr()), "dfh_mesh_smooth_run")
+        return out
+
+    def vertex_normals(self, verts=None, sign=1.0):
+        """Area-weighted unit vertex normals of `verts` (None: the constructor's; or moved ones, e.g. smooth()'s) over this mesh's
+        faces: the sum of the faces' (p_a - p_v) x (p_b - p_v) at each vertex, times sign, normalised; zero where that sum is
+        zero.  sign = +1: the winding's right-hand normal.  -> (V, 3) CUDA tensor of the verts' dtype.  The call only enqueues."""
+        sign = float(sign)
+        if not np.isfinite(sign):
+            raise ValueError("sign must be finite, got %r" % sign)
+        t = self.verts if verts is None else self._rows(verts, "verts")
+        if t.dim() != 2 or t.shape[1] != 3:
+            raise ValueError("verts must be (V, 3)")
+        with torch.cuda.device(self.device):
+            out = torch.empty_like(t)
+            _lib.check(self.lib.dfh_mesh_vertex_normals(_ptr(t), dtype_code(t), self.n_verts, self.n_faces, sign, _ptr(out), _ptr(self._ws),
+                                                        self._ws.numel() * 8, current_stream_ptr()), "dfh_mesh_vertex_normals")
+        return out
+
+
+def smooth(verts, faces, iters=10, weights="uniform", boundary="fixed", **kw):
+    """The vertices of a mesh after `iters` Taubin iterations (MeshLaplacian(verts, faces, weights, boundary).smooth(None, iters,
+    **kw)): voxel-scale ripple goes, the volume stays.  -> (V, 3) CUDA tensor of the verts' dtype; the faces are unchanged."""
+    return MeshLaplacian(verts, faces, weights, boundary).smooth(None, iters, **kw)
+
+
+def vertex_normals(verts, faces, sign=1.0):
+    """Area-weighted unit vertex normals recomputed from the faces (MeshLaplacian.vertex_normals) -> (V, 3) CUDA tensor."""
+    return MeshLaplacian(verts, faces).vertex_normals(None, sign)
+
+
+def smooth_with_normals(verts, faces, iters, **kw):
+    """smooth() for a mesh that carries vertex normals: -> (verts', normals'), the normals recomputed from the moved vertices
+    with sign = -1 (this project's marching-cubes normals point against the winding's right-hand normal).  What the smooth_iters
+    hooks of Fusion / FusionDM.write_canonical_mesh and SlabFrame.colored_mesh run."""
+    lap = MeshLaplacian(verts, faces, kw.pop("weights", "uniform"), kw.pop("boundary", "fixed"))
+    moved = lap.smooth(None, iters, **kw)
+    return moved, lap.vertex_normals(moved, -1.0)

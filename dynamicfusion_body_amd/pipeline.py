@@ -608,11 +608,13 @@ class SlabFrame:
         return kernels.raycast(self.T, self.Wt, K, np.linalg.inv(K), lws, H, W, self.scale, self.center, tsdf_res=R, res=(R, R, R),
                                x_range=(self.a, self.b), **kw)
 
-    def colored_mesh(self, min_component_faces=None, simplify_cell=None):
+    def colored_mesh(self, min_component_faces=None, simplify_cell=None, smooth_iters=None):
         """The canonical mesh with vertex colours: marching cubes of T at level 0 and the colour volume sampled at its vertices
         (kernels.sample_colors) -> (verts, faces, normals, rgb (n, 3) float32 in [0, 255], valid (n,) bool).  Single rank only, as
         render_live.  min_component_faces: drop the connected components with fewer faces (mesh.filter_components).  simplify_cell:
-        then cluster the vertices at that cell size in voxels (mesh.simplify); the colours are sampled at the new vertices."""
+        then cluster the vertices at that cell size in voxels (mesh.simplify); the colours are sampled at the new vertices.
+        smooth_iters: that many Taubin iterations (mesh.smooth_with_normals) after the component filter and before the
+        simplification; the colours are sampled at the moved vertices."""
         if self.ws > 1:
             raise ValueError("colored_mesh extracts one rank's whole grid; the %d-rank slab partition is not supported" % self.ws)
         if self.C is None:
@@ -621,6 +623,8 @@ class SlabFrame:
         verts, faces, normals, _ = _mesh.marching_cubes(self.T, 0.0, 1)
         if min_component_faces is not None:      # without the fragments: components with fewer faces are dropped first
             verts, faces, normals, _ = _mesh.filter_components(verts, faces, normals, min_faces=min_component_faces)
+        if smooth_iters is not None:
+            verts, normals = _mesh.smooth_with_normals(verts, faces, smooth_iters)
         if simplify_cell is not None:
             verts, faces, normals, _ = _mesh.simplify_with_normals(verts, faces, normals, simplify_cell)
         rgb, valid = kernels.sample_colors(self.C, verts.double())

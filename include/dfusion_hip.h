@@ -1522,6 +1522,68 @@ int dfh_mesh_simplify_faces(const int *faces, long n_verts, long n_faces, const 
                             int drop_unreferenced, int *faces_out, int *face_idx, int *cluster_map, int *kept_cluster_idx,
                             int *vert_map, long *counts_out, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- K25  mesh smoothing (Taubin's lambda|mu filter over a fixed Laplacian) and area-weighted vertex normals ----------------------
+ * No reference counterpart.  verts: DEVICE (V, 3) float32 or float64 (dtype DFH_F32 / DFH_F64; float32 is widened, exactly, before
+ * anything is computed); faces: DEVICE (F, 3) int32.  All arithmetic is fp64, one rounding per operation, no contraction; every
+ * sum starts at 0.0 and adds one term after the other in the stated order.  Every output is a function of the mesh and the
+ * parameters alone: there is no float atomic, and the only integer atomic is the error flag.
+ *
+ * Lists.  sorted_corner_vert (3F int32) and corner_order (3F int64) are the values and the indices of the stable ascending sort
+ *   of the 3F corner entries faces[f][c] (entry 3 f + c) by the vertex they name, supplied by the caller (K24's grouping).
+ *   Sorted entry i, naming corner c of face f and so vertex v = f[c], has the neighbour pair a = f[(c + 1) % 3], b = f[(c + 2) % 3].
+ *   The list of v is the sorted entries [corner_begin[v], corner_end[v]): ascending face, then corner.  A vertex no face names
+ *   has an empty list.  A face may name a vertex twice; its entries are listed like any other (a or b is then v itself).
+ * Boundary flag.  Vertex v is flagged when, for some u != v, the number of entries equal to u among the 2 (end - begin) neighbour
+ *   entries of v is not 2: an open edge (1), a non-manifold edge (3 or more), a repeated face (4).  A vertex with an empty list
+ *   is not flagged.  boundary_out: DEVICE V bytes, 0 / 1, or null.
+ * Weights.  DFH_SMOOTH_UNIFORM: w_a = w_b = 1 for every entry, and W_v = double(2 (end - begin)), exact.  DFH_SMOOTH_COTANGENT,
+ *   from the positions given to _prepare, per entry: e1 = p_a - p_v, e2 = p_b - p_v, n0 = e1y*e2z - e1z*e2y, n1 = e1z*e2x - e1x*e2z,
+ *   n2 = e1x*e2y - e1y*e2x, A2 = sqrt((n0*n0 + n1*n1) + n2*n2);  with d = p_v - p_b, g = p_a - p_b:
+ *   q_a = ((d0*g0 + d1*g1) + d2*g2) / A2, w_a = q_a if q_a > 0, otherwise 0;  with d = p_v - p_a, g = p_b - p_a: q_b, w_b alike;
+ *   w_a = w_b = 0 when !(A2 > 0).  w_a is the cotangent of the face's angle at b, the one opposite the edge (v, a).  A negative
+ *   cotangent is clamped to 0 (an obtuse angle would make the operator pull away from a neighbour).  W_v = the sum over the
+ *   list, in its order, W += w_a then W += w_b.  The weights are NOT recomputed between passes: the operator is fixed, the
+ *   filter linear.
+ * Pass.  For a value row x (V, width), width 1 .. 4, with a factor: acc_k = 0.0; for every entry of v's list in order,
+ *   acc_k += w_a * (x_a,k - x_v,k), then acc_k += w_b * (x_b,k - x_v,k) (uniform: the product with 1 is the difference itself);
+ *   x'_v,k = x_v,k + factor * (acc_k / W_v).  x'_v = x_v where !(W_v > 0) and, with DFH_SMOOTH_FIXED, for a flagged vertex.
+ *   Every vertex of a pass reads the values of the pass before (two buffers).
+ * Run.  x is widened to fp64; iters times: a pass with factor lam, then a pass with factor mu (skipped when mu == 0.0); the
+ *   result is cast to dtype, once.  iters = 0 returns x's bits.  out may be x.  layout DFH_SMOOTH_ROWS / _PLANES chooses how the
+ *   fp64 values lie in the workspace between passes (rows of four doubles, or one plane a column); the result's bits do not
+ *   depend on it.
+ * Vertex normals.  s = the sum over v's list, in order, of (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x) with
+ *   e1 = p_a - p_v, e2 = p_b - p_v, taken from the verts given to THIS call (area weighting); m = sign * s;
+ *   len = sqrt((m0*m0 + m1*m1) + m2*m2); normals[v] = m / len cast to dtype, or 0 where !(len > 0).  No angle weighting is
+ *   offered: it needs acos, whose bits the device and a host restatement do not share.
+ *
+ * workspace: dfh_mesh_smooth_workspace_bytes(V, F) bytes of device memory, 32-byte aligned, a function of (V, F) alone (0 for
+ *   counts the calls refuse).  _prepare writes the lists, the flags and the weights into it; _run and _vertex_normals read them
+ *   from the SAME workspace, which the caller keeps for as long as it uses the mesh.  A workspace that was not prepared, or was
+ *   prepared with other weights than _run is given, yields undefined values but addresses nothing outside itself and the V rows.
+ * _prepare does not only enqueue: it queues its kernels on `stream`, synchronises `stream` once and reads the flag.  _run and
+ *   _vertex_normals only enqueue: all passes of a call in one host call, no synchronisation.
+ * Refused on the device: _prepare returns DFH_E_BADARG once it has synchronised for a coordinate that is not finite, a face index
+ *   outside [0, V), or lists that are not the sort of the faces (nothing is addressed through a bad index).
+ * V == 0 or F == 0 are valid and launch nothing they do not need.  DFH_E_BADARG before any HIP call: V negative or >= 2^31; F
+ *   negative or above (2^31 - 1) / 3 (3F must fit an int); faces without vertices; width outside 1 .. 4; iters < 0; lam, mu or
+ *   sign not finite; a dtype, weights, boundary or layout that is not one of the two; a null array of a non-zero count; a null
+ *   workspace, one that is not 32-byte aligned or one smaller than dfh_mesh_smooth_workspace_bytes(V, F). */
+#define DFH_SMOOTH_UNIFORM 0
+#define DFH_SMOOTH_COTANGENT 1
+#define DFH_SMOOTH_FIXED 0
+#define DFH_SMOOTH_FREE 1
+#define DFH_SMOOTH_ROWS 0
+#define DFH_SMOOTH_PLANES 1
+size_t dfh_mesh_smooth_workspace_bytes(long n_verts, long n_faces);
+int dfh_mesh_smooth_prepare(const void *verts, int dtype, long n_verts, const int *faces, long n_faces,
+                            const int *sorted_corner_vert, const long long *corner_order, int weights,
+                            unsigned char *boundary_out, void *workspace, size_t workspace_bytes, void *stream);
+int dfh_mesh_smooth_run(const void *x, int dtype, long n_verts, long n_faces, long width, int weights, int boundary, int layout,
+                        int iters, double lam, double mu, void *out, void *workspace, size_t workspace_bytes, void *stream);
+int dfh_mesh_vertex_normals(const void *verts, int dtype, long n_verts, long n_faces, double sign, void *normals, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
